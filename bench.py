@@ -10,6 +10,8 @@ the 1M-person problem is fixed, every rank owns N / world persons).
     python bench.py --gpus N --steps K --warmup W            # N > 1, no launcher around it: starts its N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W               # under a launcher: one rank per GPU, RCCL
+    python bench.py --full ...                               # + the figures that take runs of their own (see --full)
+    python bench.py --dump-outputs DIR ...                   # + the last timed step's outputs as DIR/<name>.npy
 
 Prints ONE JSON line on rank 0 (see the field notes in DESIGN.md section "Measurement").
 """
@@ -304,6 +306,30 @@ def cpu_baseline(J, D, H, n_sample, min_seconds=6.0):
             "torch_sec": torch_sec, "torch_n": n_torch, "torch_b100": torch_b100}
 
 
+DUMP_MAX_ELEMENTS = 1 << 20        # --dump-outputs: values per array (4 MB in float32); a larger array is written as a row sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, eng, loss):
+    """--dump-outputs: what the last timed step hands its caller -- the loss it returns and every parameter after its optimiser
+    update, as pyro.param(name) returns it (constrained; per-person rows: this rank's shard) -- one .npy per array (the loss
+    float64, the parameters float32).  An array of more than DUMP_MAX_ELEMENTS values is written as a fixed, seeded sample of
+    its rows: the same rows on every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([float(loss.item())], dtype=np.float64)}
+    for name in eng.all_names():
+        arrays["param." + name.replace("$$$", ".")] = eng.param(name).to(torch.float32).cpu().numpy()
+    total = 0
+    for key, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMENTS:
+            n_rows = max(1, DUMP_MAX_ELEMENTS // (a.size // a.shape[0]))
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], n_rows, replace=False))]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit("bench.py: --dump-outputs would write more than %d bytes" % DUMP_MAX_BYTES)
+        np.save(os.path.join(out_dir, key + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks as CHILDREN (one process per
     GPU, torch.distributed.run on 127.0.0.1) before this process touches the GPU, relay rank 0's JSON line and exit
@@ -337,7 +363,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="default: 5 for the headline, 50 for the secondary workloads")
     ap.add_argument("--workload", default="irt2pl_100d_amortized_1Mx500", choices=sorted(WORKLOADS))
     ap.add_argument("--persons", type=int, default=None, help="override N (debug only; makes the line non-headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also what takes runs of its own: the eager pass with HIP events behind a "
+                         "replayed timed region (phase_ms, kernel_ms, roofline), graph_replay_ms_per_step, the board probe, "
+                         "the reference's B = 100 step on the GPU and the CPU baselines.  Off: the line carries the timed "
+                         "steps and what the timed region itself measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and parameters as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--graph", default="auto", choices=["auto", "0", "1"],
                     help="timed region replays the step's HIP graph (1) or launches kernel by kernel with HIP events around the "
                          "large kernels (0); auto = 0 for the judged headline run on one GPU (its roofline must be measured "
@@ -350,7 +383,8 @@ def main():
     ap.add_argument("--baseline", default="avg", choices=["none", "avg"],
                     help="control variate of --estimator score: per-person decaying average (pyro's use_decaying_avg_baseline) or none")
     ap.add_argument("--no-board-probe", action="store_true",
-                    help="skip the ~1.6 s of further steps behind the timed region during which board power / clock are sampled")
+                    help="with --full: skip the ~1.6 s of further steps behind the timed region during which board power / clock "
+                         "are sampled")
     ap.add_argument("--event-every", type=int, default=5,
                     help="kernel-by-kernel timed region: HIP events on every n-th step of it (1 = on all)")
     ap.add_argument("--dist-backend", default=os.environ.get("VX_DIST_BACKEND", "nccl"), choices=["nccl", "gloo"],
@@ -364,6 +398,8 @@ def main():
         args.steps = 50 if headline else 200
     if args.warmup is None:
         args.warmup = 5 if headline else 50
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args, sys.argv[1:]))
@@ -483,7 +519,9 @@ def main():
     dt = time.perf_counter() - t0
     loss_v = float(loss.item())
     loss_first_v = float(loss_first.item())
-    if graphed:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss)          # (before anything else steps the engine)
+    if graphed and args.full:
         # the timed region replayed the graph: per-phase and per-kernel durations from an eager pass AFTER it
         eng.events = ev
         _hip.lib().vx_prof_enable(1)
@@ -504,7 +542,7 @@ def main():
                 kernel_units[nm.value.decode()] = int(un.value)
     _hip.lib().vx_prof_enable(0)
     graph_ms = None
-    if not graphed and world == 1 and eng._graphable():
+    if args.full and not graphed and world == 1 and eng._graphable():
         # the line above was timed kernel by kernel (HIP events inside the timed region); for comparison the same step replayed
         # from its HIP graph, after the timed region (the first call of the form runs eagerly, the second captures)
         ng = min(args.steps, 20)
@@ -515,7 +553,7 @@ def main():
         sync()
         graph_ms = 1e3 * (time.perf_counter() - tg) / ng
     board = None
-    if world == 1 and not args.no_board_probe:
+    if args.full and world == 1 and not args.no_board_probe:
         def run_more(n):
             for _ in range(n):
                 eng.step(lrs)
@@ -565,9 +603,10 @@ def main():
             if args.dist_backend != "nccl":
                 out["metric"] += " [REHEARSAL over %s on %d visible device(s): not an %d-GPU result]" % (args.dist_backend, n_dev, world)
                 out["rehearsal"] = True
-        out["config"]["launch"] = ("whole step replayed from HIP graphs (one; two around the eager all-reduce when sharded); "
-                                   "phase_ms / kernel_ms / roofline.avg_launch_ms from an eager pass with HIP events AFTER the "
-                                   "timed region") if graphed else "kernel by kernel, HIP events around the large kernels inside the timed region"
+        out["config"]["launch"] = ("whole step replayed from HIP graphs (one; two around the eager all-reduce when sharded)" +
+                                   ("; phase_ms / kernel_ms / roofline.avg_launch_ms from an eager pass with HIP events AFTER the "
+                                    "timed region" if args.full else "")) if graphed else \
+            "kernel by kernel, HIP events around the large kernels inside the timed region"
         if getattr(eng, "graph_fallback", None):             # capture beside the live communicator failed: said in the line
             out["config"]["launch"] = ("kernel by kernel -- HIP graph capture of the sharded step failed on this rank (%s); same "
                                        "kernels, launched one by one" % eng.graph_fallback[:160])
@@ -648,7 +687,7 @@ def main():
             if graphed:
                 out["roofline"]["avg_launch_ms_source"] = ("HIP events around the kernel in an eager pass after the "
                                                            "timed region (the timed region replays a graph)")
-        if world == 1 and not args.no_cpu_baseline and D > 1:
+        if args.full and world == 1 and not args.no_cpu_baseline and D > 1:
             # the reference's own usage (subsample_size = 100) on the same engine, outside the timed region
             rg = np.random.Generator(np.random.PCG64(7))
             def draw():                                     # host indices, as the fit loop draws them (vipsy_amd/vi.py::_subsample)

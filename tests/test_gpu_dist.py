@@ -77,7 +77,7 @@ def test_bench_self_launch_four_ranks_of_125k():
     import torch
     backend = "nccl" if torch.cuda.device_count() >= 4 else "gloo"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "3",
-                        "--persons", "500000", "--no-cpu-baseline", "--dist-backend", backend],
+                        "--persons", "500000", "--full", "--no-cpu-baseline", "--dist-backend", backend],
                        capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stderr[-3000:]
