@@ -103,3 +103,77 @@ def test_loss_reaches_the_ring_without_an_optimiser_launch():
     eng.per_person = False                                     # ... and no per-person one: apply_optim launches nothing
     eng.apply_optim(LrSpec(1e-2))
     assert float(eng.step_loss()) == want and float(eng.loss_ring[eng.t % LOSS_RING]) == want
+
+
+def test_graph_replay_forms_per_engine():
+    """Which steps of each engine replay from a captured HIP graph (_graph_mode), and which IrtEngine steps fuse the optimiser
+    into the step kernel (_fused_tail_args).  A stub HipBackend: building an engine and asking for its form call no library."""
+    from vipsy_amd.engine import (HipBackend, LrSpec, HoDinaEngine, CcdmEngine, VaeCcdmEngine, CdmSfEngine)
+
+    class _Stub(HipBackend):
+        def __init__(self):
+            pass
+
+    n, J, K, b = 64, 8, 3, 100
+    rng = np.random.RandomState(4)
+    y = torch.from_numpy(rng.randint(0, 2, size=(n, J)).astype(np.uint8))
+    q = np.zeros((K, J), dtype=np.float32)
+    q[np.arange(J) % K, np.arange(J)] = 1
+    rows = torch.arange(10, dtype=torch.int64)
+    nb = int(rows.numel())
+
+    def irt(**kw):
+        return IrtEngine(y, model="irt_2pl", backend=_Stub(), **kw)
+
+    replays_all = {
+        "irt_d1": irt(D=1),
+        "irt_d1_amortized": irt(D=1, amortized=True, H=64),
+        "irt_d4_amortized": irt(D=4, amortized=True, H=64),
+        "irt_d3_bbvi": irt(D=3),
+        "hodina_amortized": HoDinaEngine(y, q, amortized=True, H=64, backend=_Stub()),
+        "ccdm": CcdmEngine(y, q, backend=_Stub()),
+        "vaeccdm": VaeCcdmEngine(y, q, backend=_Stub()),
+        "cdm_sf": CdmSfEngine(y, q, backend=_Stub()),
+    }
+    for tag, eng in replays_all.items():
+        assert eng._graph_mode(None, None, None, 1) == ("full", n, n), tag
+        assert eng._graph_mode(rows, b, None, 1) == ("rows", nb, b), tag
+        assert eng._graph_mode([rows, rows], b, None, 2) == ("rows", nb, b, 2), tag
+        assert eng._graph_mode(None, b, None, 1) is None, tag
+        assert eng._graphable(), tag
+        # a one-element list with S = 1, the caller's draws, phase events or graphs switched off: an eager step
+        assert eng._graph_mode([rows], b, None, 1) is None, tag
+        assert eng._graph_mode(None, None, torch.zeros(n), 1) is None, tag
+        eng.events = []
+        assert eng._graph_mode(None, None, None, 1) is None, tag
+        eng.events, eng.use_graph = None, False
+        assert eng._graph_mode(None, None, None, 1) is None, tag
+        assert eng._graph_mode(rows, b, None, 1) is None, tag
+
+    never = {
+        "irt_score": irt(D=1, estimator="score"),
+        "cdm_sf_loo": CdmSfEngine(y, q, baseline="loo", backend=_Stub()),
+        "vaeccdm_group": VaeCcdmEngine(y, q, group=object(), backend=_Stub()),
+    }
+    for tag, eng in never.items():
+        assert eng._graph_mode(None, None, None, 1) is None, tag
+        assert eng._graph_mode(rows, b, None, 1) is None, tag
+        assert eng._graph_mode([rows, rows], b, None, 2) is None, tag
+        assert eng._graph_mode(None, b, None, 1) is None, tag
+
+    hd = HoDinaEngine(y, q, backend=_Stub())                   # the per-person guide: full batches only
+    assert hd._graph_mode(None, None, None, 1) == ("full", n, n)
+    assert hd._graph_mode(rows, b, None, 1) is None
+    assert hd._graph_mode([rows, rows], b, None, 2) is None
+    assert hd._graph_mode(None, b, None, 1) is None
+
+    big = irt(D=4, amortized=True, H=64)
+    big.graph_max_persons = n - 1                              # a shard above the switch: its full batch runs eagerly
+    assert big._graph_mode(None, None, None, 1) is None
+    assert big._graph_mode(rows, b, None, 1) == ("rows", nb, b)
+
+    assert irt(D=1)._fused_tail_args(LrSpec(1e-2), None, None, 1) is not None
+    assert irt(D=1, amortized=True, H=64)._fused_tail_args(LrSpec(1e-2), None, None, 1) is None
+    assert irt(D=1, estimator="score")._fused_tail_args(LrSpec(1e-2), None, None, 1) is None
+
+    assert IrtEngine.step.__qualname__ == "IrtEngine.step"     # the step written in the class is the one that runs

@@ -45,6 +45,13 @@ class HipBackend(object):
             c.rows_ring, c.rows_ring_stride, c.rows_ring_slots = rows_ring.data_ptr(), rows_ring.shape[1], rows_ring.shape[0]
         return c
 
+    def _size(self, fn, *args):
+        """The answer of a size query of the C ABI; a negative one: the configuration is not supported."""
+        n = getattr(self.L, fn)(*args)
+        if n < 0:
+            raise _hip.VxError("%s: unsupported configuration (code %d)" % (fn, n))
+        return n
+
     def mvn_enc_forward(self, cfg, y, rows, nb, gid0, enc, eps_in, out):
         rc = self.L.vx_mvn_enc_forward(ctypes.byref(cfg), _hip.ptr(y), _hip.ptr(rows), nb, gid0,
                                        _hip.ptr(enc["fc1.weight"]), _hip.ptr(enc["fc1.bias"]),
@@ -58,22 +65,13 @@ class HipBackend(object):
         _hip.check(rc, "vx_mvn_enc_forward")
 
     def mvn_pack_floats(self, cfg):
-        n = self.L.vx_mvn_pack_floats(ctypes.byref(cfg))
-        if n < 0:
-            raise _hip.VxError("vx_mvn_pack_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_mvn_pack_floats", ctypes.byref(cfg))
 
     def lik_ximg_bytes(self, cfg, nb):
-        n = self.L.vx_irt_lik_ximg_bytes(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_irt_lik_ximg_bytes: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_irt_lik_ximg_bytes", ctypes.byref(cfg), nb)
 
     def lik_workspace(self, cfg, nb):
-        n = self.L.vx_irt_lik_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_irt_lik_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_irt_lik_workspace_floats", ctypes.byref(cfg), nb)
 
     def mvn_pack_opmax_offset(self, cfg, nb):
         return int(self.L.vx_mvn_pack_opmax_offset(ctypes.byref(cfg), nb))
@@ -88,10 +86,7 @@ class HipBackend(object):
         _hip.check(rc, "vx_irt_lik_grad")
 
     def mvn_enc_bwd_workspace(self, cfg, nb):
-        n = self.L.vx_mvn_enc_bwd_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_mvn_enc_bwd_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_mvn_enc_bwd_workspace_floats", ctypes.byref(cfg), nb)
 
     def mvn_enc_bwd_layout(self, cfg, nb):
         return int(self.L.vx_mvn_enc_bwd_layout(ctypes.byref(cfg), nb))
@@ -121,14 +116,11 @@ class HipBackend(object):
         _hip.check(rc, "vx_mvn_enc_backward_loss")
 
     def irt1d_workspace(self, cfg, nb):
-        n = self.L.vx_irt1d_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_irt1d_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_irt1d_workspace_floats", ctypes.byref(cfg), nb)
 
     @staticmethod
     def _adam_tail(adam):
-        """struct vx_adam_tail from the engine's description of its optimiser step (_EngineBase._fused_tail_args); the
+        """struct vx_adam_tail from the engine's description of its optimiser step (IrtEngine._fused_tail_args); the
         segment arrays ride along so that they outlive the call."""
         (pA, mA, vA, freeA, nA, segsA), B = adam["A"], adam.get("B")
         arrA = (_hip.AdamSeg * len(segsA))(*[_hip.AdamSeg(b, e, lr, 0.0) for (b, e, lr) in segsA])
@@ -159,10 +151,7 @@ class HipBackend(object):
         _hip.check(rc, "vx_irt1d_grad")
 
     def irt1d_sparse_workspace(self, cfg, n_groups):
-        n = self.L.vx_irt1d_sparse_workspace_floats(ctypes.byref(cfg), n_groups)
-        if n < 0:
-            raise _hip.VxError("vx_irt1d_sparse_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_irt1d_sparse_workspace_floats", ctypes.byref(cfg), n_groups)
 
     def irt1d_sparse_grad(self, cfg, lists, gid0, loc, raw, eps_in, a, b, c_un, d_un, gloc, graw, elbo, gitem, ws,
                           loss=None, step_dev=None, adam=None):
@@ -203,16 +192,10 @@ class HipBackend(object):
         _hip.check(rc, "vx_norm_enc_forward")
 
     def norm_enc_pack_floats(self, cfg):
-        n = self.L.vx_norm_enc_pack_floats(ctypes.byref(cfg))
-        if n < 0:
-            raise _hip.VxError("vx_norm_enc_pack_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_norm_enc_pack_floats", ctypes.byref(cfg))
 
     def norm_enc_bwd_workspace(self, cfg, nb):
-        n = self.L.vx_norm_enc_bwd_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_norm_enc_bwd_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_norm_enc_bwd_workspace_floats", ctypes.byref(cfg), nb)
 
     def norm_enc_backward(self, cfg, y, rows, nb, enc, h, gloc, graw, genc, ws, yT=None):
         rc = self.L.vx_norm_enc_backward(ctypes.byref(cfg), _hip.ptr(y), _hip.ptr(rows), nb,
@@ -227,10 +210,7 @@ class HipBackend(object):
         return _hip.HoDinaCfg(K, J, H, 0, scale, 0.0, seed, step, stream, None if step_dev is None else step_dev.data_ptr())
 
     def hodina_workspace(self, cfg, nb):
-        n = self.L.vx_hodina_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_hodina_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_hodina_workspace_floats", ctypes.byref(cfg), nb)
 
     def hodina_grad(self, cfg, y, rows, nb, gid0, loc, raw, eps_in, q, lam0, lam1, g, s_, gloc, graw, elbo, gitem, ws):
         rc = self.L.vx_hodina_grad(ctypes.byref(cfg), _hip.ptr(y), _hip.ptr(rows), nb, gid0, _hip.ptr(loc),
@@ -240,10 +220,7 @@ class HipBackend(object):
         _hip.check(rc, "vx_hodina_grad")
 
     def ccdm_workspace(self, cfg, nb):
-        n = self.L.vx_ccdm_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_ccdm_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_ccdm_workspace_floats", ctypes.byref(cfg), nb)
 
     def ccdm_grad(self, cfg, dino, y, rows, nb, q, g, s_, elbo, gitem, ws):
         rc = self.L.vx_ccdm_grad(ctypes.byref(cfg), int(dino), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(q), _hip.ptr(g),
@@ -251,10 +228,7 @@ class HipBackend(object):
         _hip.check(rc, "vx_ccdm_grad")
 
     def cdm_sf_workspace(self, cfg, nb):
-        n = self.L.vx_cdm_sf_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_cdm_sf_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_cdm_sf_workspace_floats", ctypes.byref(cfg), nb)
 
     def cdm_sf_grad(self, cfg, dino, clamp_t, prior_p, y, rows, nb, gid0, q, g, s_, u, attr_in, baseline, base_beta,
                     base_by_row, gu, log_r, attr_out, gitem, ws):
@@ -305,10 +279,7 @@ class HipBackend(object):
         _hip.check(rc, "vx_bin_enc_forward")
 
     def bin_enc_bwd_workspace(self, cfg, nb):
-        n = self.L.vx_bin_enc_bwd_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_bin_enc_bwd_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_bin_enc_bwd_workspace_floats", ctypes.byref(cfg), nb)
 
     def bin_enc_backward(self, cfg, y, rows, nb, enc, h, gu, genc, ws):
         rc = self.L.vx_bin_enc_backward(ctypes.byref(cfg), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(enc["fc2.weight"]),
@@ -329,10 +300,7 @@ class HipBackend(object):
         return int(self.L.vx_col_reduce_workspace_floats(nb, int(C)))
 
     def vaeccdm_workspace(self, cfg, nb):
-        n = self.L.vx_vaeccdm_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_vaeccdm_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_vaeccdm_workspace_floats", ctypes.byref(cfg), nb)
 
     def vaeccdm_grad(self, cfg, dino, y, rows, nb, q, g, s_, z, off, elbo, gla, gitem, ws):
         rc = self.L.vx_vaeccdm_grad(ctypes.byref(cfg), int(dino), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(q), _hip.ptr(g),
@@ -341,10 +309,7 @@ class HipBackend(object):
         _hip.check(rc, "vx_vaeccdm_grad")
 
     def sm_enc_bwd_workspace(self, cfg, nb):
-        n = self.L.vx_sm_enc_bwd_workspace_floats(ctypes.byref(cfg), nb)
-        if n < 0:
-            raise _hip.VxError("vx_sm_enc_bwd_workspace_floats: unsupported configuration (code %d)" % n)
-        return n
+        return self._size("vx_sm_enc_bwd_workspace_floats", ctypes.byref(cfg), nb)
 
     def sm_enc_backward(self, cfg, y, rows, nb, enc, h, z, off, T, gla, genc, ws):
         rc = self.L.vx_sm_enc_backward(ctypes.byref(cfg), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(enc["fc2.weight"]),
@@ -439,6 +404,44 @@ class _EngineBase(object):
 
     pp_names = ("x_local", "x_scale")
 
+    def _preamble(self, y_u8, backend, n_global, gid0, seed, group):
+        """What every constructor starts with: the backend, this rank's shard of the responses and where it sits among the
+        n_global persons."""
+        self.be = backend if backend is not None else HipBackend()
+        self.y = y_u8.contiguous()
+        assert self.y.dtype == torch.uint8 and self.y.dim() == 2
+        self.dev = self.y.device
+        self.n_local, self.J = self.y.shape
+        self.y_lik = None                    # the copy the likelihood reads when it is not self.y (IrtEngine.__init__)
+        self.N = int(n_global) if n_global is not None else self.n_local
+        self.gid0 = int(gid0)
+        self.seed, self.group = int(seed), group
+
+    def _q_matrix(self, q, why="the subset tests of vi.py:78-81, 96-100 assume it"):
+        q = torch.as_tensor(q, dtype=torch.float32)
+        assert q.dim() == 2 and q.shape[1] == self.J
+        if not bool(((q == 0) | (q == 1)).all()):
+            raise ValueError("the Q-matrix must be binary (%s)" % why)
+        self.K = int(q.shape[0])
+        self.q = q.to(self.dev).contiguous()
+
+    def _encoder_segments(self, shapes):
+        """The encoder's tensors (`shapes`, in nn.Linear order) behind the item parameters, from a 256-byte boundary on;
+        returns the end of the flat buffer."""
+        o = (self.n_item + 63) // 64 * 64
+        self.enc_shapes, self.enc_off0 = shapes, o
+        for k, shp in shapes.items():
+            self.off["encoder$$$" + k] = o
+            self.shape["encoder$$$" + k] = shp
+            o += int(np.prod(shp))
+        self.n_enc = o - self.enc_off0
+        return o
+
+    def _init_g_s(self):
+        """g = s = 0.1 through the interval(0, 1) transform (vi.py:748-749, 844-845, 875-876, 901-904)."""
+        for nme in ("g", "s"):
+            self.view(nme).fill_(float(np.float32(_logit(np.float32(0.1)))))
+
     def _alloc(self, n_params, n_local, per_person):
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.n_params = n_params
@@ -468,6 +471,25 @@ class _EngineBase(object):
         self.last = {}
         self.events = None               # bench.py: list collecting (phase, start_event, end_event)
         self.t = 0                       # optimiser step counter (Adam bias correction, Philox step)
+        self._step_dev = None            # while a capture records: the device step counter the kernels read
+        self._capture_ring = None        # ... and the pinned rows ring a captured subsampled step may fetch its draw from
+        self._fused_tail = None          # the optimiser step armed for the step kernel's last launch (_grads_and_optim)
+        self._graphs, self._graph = {}, None                 # captured forms (_step_graph), the one last replayed
+        self._ctr = self._pin_ring = None
+        self._n_pad = n_local            # persons the full-batch kernels are launched over (phantoms: IrtEngine._pad_persons)
+        self._yT = self._y_pad = self._y_pad_lik = None      # copies of the responses made on first use
+
+    def _enc(self):
+        return {k: self.view("encoder$$$" + k) for k in self.enc_shapes}
+
+    def all_names(self):
+        return self.names() + (list(self.pp_off) if self.per_person else [])
+
+    def _call(self, rows, b_global):
+        """(persons of this call, plate scale N / global batch, the step_dev argument of a captured step's calls)."""
+        nb = self.n_local if rows is None else int(rows.numel())
+        Bg = int(b_global) if b_global is not None else (self.N if rows is None else nb)
+        return nb, float(self.N) / float(Bg), ({"step_dev": self._step_dev} if self._step_dev is not None else {})
 
     def view(self, name, buf=None):
         buf = self.P if buf is None else buf
@@ -481,87 +503,32 @@ class _EngineBase(object):
             return b[o:o + int(np.prod(self.pp_shape[name]))].reshape(self.pp_shape[name])
         return self.view(name, buf).reshape(self.shape[name])
 
-    def _enc(self):
-        return {k: self.view("encoder$$$" + k) for k in ENC_KEYS}
-
-    def _item_major_y(self, rows):
+    def _item_major_y(self, rows, key="_yT", y=None):
         """Item-major copy of the responses ([J + 1][stride] bytes, stride = n_local rounded up to 64; row J and the
         columns past n_local hold 254 = "outside the problem") for the dimension-major fc1 gradient kernel and the bf16-MFMA
-        likelihood kernel (include/vipsy_amd.h, vx_irt_lik_grad): made once (the responses never change); full batches only."""
+        likelihood kernel (include/vipsy_amd.h, vx_irt_lik_grad): made once (the responses never change) and kept as
+        self.<key>; full batches only.  y: the responses to copy, by default the likelihood's."""
         if rows is not None or self.n_local == 0:
             return None
-        if getattr(self, "_yT", None) is None:
-            y = self._padded_y(lik=True)                     # (the shard's own responses unless persons / items are padded)
+        if getattr(self, key) is None:
+            y = self._padded_y(lik=True) if y is None else y     # (the shard's own responses unless persons / items are padded)
             stride = (y.shape[0] + 63) // 64 * 64
-            yT = torch.full((self.J + 1, stride), 254, dtype=torch.uint8, device=self.dev)
-            yT[:self.J, :y.shape[0]] = y.t()
-            self._yT = yT
-        return self._yT
-
-    def _pad_persons(self, be, cfg, rows):
-        """Persons the full-batch kernels of the amortized multivariate guide are launched over: the shard's own count, or --
-        when that is not a multiple of 8 -- the next one.  The dimension-major operands of the large-batch kernels are rows of
-        `nb` floats (fp16 planes: `nb` halves) read in 16-byte pieces, so a count that is not a multiple of 8 sends the head
-        weight gradient (and, below a multiple of 4, everything) to the fp32-MFMA generation: 13.9 ms a step at 1 000 004
-        persons, 26.3 at 999 999, against 9.1 at 1 000 000.  The 1-7 PHANTOM persons appended instead have every response
-        missing (byte 255: a finite guide sample, no likelihood term) and are taken out of the step behind the likelihood:
-        their columns of gxT / gdT (everything the backward kernels see of a person) and their entries of ll / ent are zeroed,
-        so they add nothing to any gradient or to the loss.  Pathwise estimator, HIP backend, full batch only."""
-        n = self.n_local
-        if (rows is not None or n % 8 == 0 or n < 8 or not isinstance(be, HipBackend)
-                or getattr(self, "estimator", "pathwise") != "pathwise" or not self.pad_persons):
-            return n
-        n_pad = (n + 7) // 8 * 8
-        return n_pad if (be.mvn_enc_bwd_layout(cfg, n_pad) == 1 and be.mvn_enc_bwd_gd_offset(cfg, n_pad) >= 0) else n
-
-    pad_persons = os.environ.get("VX_PAD_PERSONS", "1") != "0"      # test seam: 0 = launch over the shard's own count
+            yT = torch.full((y.shape[1] + 1, stride), 254, dtype=torch.uint8, device=self.dev)
+            yT[:y.shape[1], :y.shape[0]] = y.t()
+            setattr(self, key, yT)
+        return getattr(self, key)
 
     def _padded_y(self, lik=False):
         """The responses with the phantom persons of _pad_persons appended (made once; the responses themselves when none
         are).  lik: the copy the likelihood reads (phantom ITEMS absent instead of zero, IrtEngine.__init__)."""
-        y = self.y_lik if (lik and getattr(self, "y_lik", None) is not None) else self.y
-        n_pad = getattr(self, "_n_pad", self.n_local)
+        y = self.y_lik if (lik and self.y_lik is not None) else self.y
+        n_pad = self._n_pad
         if n_pad == self.n_local:
             return y
         key = "_y_pad_lik" if y is not self.y else "_y_pad"
-        if getattr(self, key, None) is None:
+        if getattr(self, key) is None:
             setattr(self, key, torch.cat([y, torch.full((n_pad - self.n_local, self.J), 255, dtype=torch.uint8, device=self.dev)]))
         return getattr(self, key)
-
-    def _sparse_lists(self, rows):
-        """Observed-cell lists for the D = 1 kernel (include/vipsy_amd.h, vx_irt1d_sparse_grad): built once -- the
-        responses never change -- and only when most cells are missing and the batch is the whole shard.  Persons are
-        placed in slots sorted by list length inside windows of 4096, so the 64 lists a wave walks end together."""
-        if rows is not None or self.n_local == 0 or self.J > 1024 or not self.observed_lists:
-            return None
-        if getattr(self, "_sp", None) is None:
-            y, n, J = (self.y_lik if getattr(self, "y_lik", None) is not None else self.y), self.n_local, self.J
-            frac = float((y == 255).sum().item()) / float(n * J)
-            if frac < 0.5:
-                self._sp = False
-            else:
-                ng = (n + 63) // 64
-                cnt = torch.full((ng * 64,), -1, dtype=torch.int64, device=self.dev)             # -1: empty slot, sorts last
-                cnt[:n] = (y < 254).sum(1)                                                     # (254: a phantom item, absent)
-                slot = torch.arange(ng * 64, device=self.dev)
-                perm = torch.argsort((slot // 4096) * (J + 2) + (J - cnt), stable=True)           # slot -> person
-                cnt_s = cnt[perm].clamp_(min=0)
-                pidx = torch.where(perm < n, perm, torch.full_like(perm, -1)).to(torch.int32).contiguous()
-                Lq = max(1, (int(cnt_s.max().item()) + 3) // 4)
-                W = min(J, 4 * Lq)
-                pent = torch.full((ng * 64, 4 * Lq), -1, dtype=torch.int16, device=self.dev)      # 0xFFFF = past the end
-                ar = torch.arange(W, device=self.dev)[None, :]
-                for lo in range(0, ng * 64, 65536):                                               # bounded temporaries
-                    hi = min(ng * 64, lo + 65536)
-                    yc = y[perm[lo:hi].clamp(max=n - 1)]
-                    order = torch.argsort((yc >= 254).to(torch.uint8), dim=1, stable=True)[:, :W]  # observed items first
-                    code = order.to(torch.int32) | ((torch.gather(yc, 1, order) == 1).to(torch.int32) << 15)
-                    code = torch.where(ar < cnt_s[lo:hi, None], code, torch.full_like(code, 0xFFFF))
-                    pent[lo:hi, :W] = code.to(torch.int16)                                        # wraps: bit pattern kept
-                pent = pent.reshape(ng, 64, Lq, 4).permute(0, 2, 1, 3).contiguous()
-                glen = ((cnt_s.reshape(ng, 64).max(1).values + 3) // 4).to(torch.int32).contiguous()
-                self._sp = {"pent": pent, "glen": glen, "Lq": Lq, "pidx": pidx, "n_groups": ng, "missing": frac}
-        return self._sp or None
 
     def _buf(self, key, n):
         t = self._ws.get(key)
@@ -590,36 +557,43 @@ class _EngineBase(object):
             self.GP[:n].index_add_(0, rows, gloc[:nb])
             self.GP[n:].index_add_(0, rows, graw[:nb])
 
+    def _allreduce(self, t, op=None):
+        """SUM (or `op`) of `t` over the ranks of `group`; nothing without one."""
+        if self.group is not None:
+            op = torch.distributed.ReduceOp.SUM if op is None else op
+            if t.is_cuda and torch.distributed.get_backend(self.group) == "gloo":
+                host = t.cpu()                               # rehearsal of N ranks on fewer GPUs: gloo reduces on the host
+                torch.distributed.all_reduce(host, op=op, group=self.group)
+                t.copy_(host)
+            else:                                            # the product path: RCCL (backend "nccl") on the device buffer
+                torch.distributed.all_reduce(t, op=op, group=self.group)
+
     def allreduce(self):
         """The one exchange of a step: SUM of [gradients | loss] over the ranks that share this problem.  Sharding is
         explicit -- `group` handed to the constructor -- never inferred from global torch.distributed state, so that
         independent problems (replications, vipsy_amd/harness.py) can run side by side under one process group."""
-        if self.group is not None:
-            if self.G.is_cuda and torch.distributed.get_backend(self.group) == "gloo":
-                host = self.G.cpu()                          # rehearsal of N ranks on fewer GPUs: gloo reduces on the host
-                torch.distributed.all_reduce(host, group=self.group)
-                self.G.copy_(host)
-            else:                                            # the product path: RCCL (backend "nccl") on the device buffer
-                torch.distributed.all_reduce(self.G, group=self.group)
+        self._allreduce(self.G)
+
+    def _optim_segments(self, lrs):
+        """The optimiser's (begin, end, lr) segments grouped by (betas, eps): of P, and of PP ({} without per-person rows)."""
+        by_hyper, pp_hyper = {}, {}
+        for name in self.names():
+            o = self.off[name]
+            by_hyper.setdefault(lrs.hyper_of(name), []).append((o, o + int(np.prod(self.shape[name])), float(lrs.lr_of(name))))
+        if self.per_person:
+            for nme, o in self.pp_off.items():
+                pp_hyper.setdefault(lrs.hyper_of(nme), []).append((o, o + int(np.prod(self.pp_shape[nme])), float(lrs.lr_of(nme))))
+        return by_hyper, pp_hyper
 
     def apply_optim(self, lrs):
         """Adam on the unconstrained leaves with the `free` mask (vi.py:508-514)."""
         self.t += 1
-        by_hyper = {}
-        for name in self.names():
-            o = self.off[name]
-            by_hyper.setdefault(lrs.hyper_of(name), []).append(
-                (o, o + int(np.prod(self.shape[name])), float(lrs.lr_of(name))))
-        sd = getattr(self, "_step_dev", None)
+        by_hyper, pp_hyper = self._optim_segments(lrs)
+        sd = self._step_dev
         kw = {"t_dev": sd} if sd is not None else {}         # captured step: Adam's t = the (already advanced) device counter
         hip = isinstance(self.be, HipBackend)
         if hip:                                              # the first optimiser launch also files the step's loss in the ring
             kw["loss"] = (self.G[self.n_params:self.n_params + 1], self.loss_ring)
-        pp_hyper = {}
-        if self.per_person:
-            for nme, o in self.pp_off.items():
-                pp_hyper.setdefault(lrs.hyper_of(nme), []).append(
-                    (o, o + int(np.prod(self.pp_shape[nme])), float(lrs.lr_of(nme))))
         if len(by_hyper) == 1 and len(pp_hyper) == 1 and list(by_hyper) == list(pp_hyper):
             (betas, eps), segs = next(iter(by_hyper.items()))          # the usual case: one launch for both buffers
             self.be.adam2((self.P, self.G, self.M, self.V), self.free, self.n_params, _merge_segments(segs),
@@ -638,33 +612,14 @@ class _EngineBase(object):
             # segment): nothing filed the loss, so it is copied into its slot here
             self.loss_ring[self.t % LOSS_RING] = self.G[self.n_params]
 
-    # -- the optimiser inside the step's last launch (one rank, D = 1 per-person guides) --------------
-    fuse_tail = True
-
     def _fused_tail_args(self, lrs, rows, eps, S):
-        """What vx_irt1d_grad_adam needs to run Adam in the launch that sums the step's slabs -- or None when this step has
-        to keep loss_and_grads | all-reduce | optimiser apart (a process group, an amortized or multivariate guide, a
-        subsample whose gradients are scattered afterwards, the score-function estimator, more than one (betas, eps))."""
-        if not (self.fuse_tail and self.group is None and S == 1 and rows is None and isinstance(self.be, HipBackend)
-                and isinstance(self, IrtEngine) and self.D == 1 and not self.amortized and self.per_person
-                and self.estimator == "pathwise" and self.events is None and self.n_params == 4 * self.J):
-            return None
-        by_hyper, pp_hyper = {}, {}
-        for name in self.names():
-            o = self.off[name]
-            by_hyper.setdefault(lrs.hyper_of(name), []).append((o, o + int(np.prod(self.shape[name])), float(lrs.lr_of(name))))
-        for nme, o in self.pp_off.items():
-            pp_hyper.setdefault(lrs.hyper_of(nme), []).append((o, o + int(np.prod(self.pp_shape[nme])), float(lrs.lr_of(nme))))
-        if not (len(by_hyper) == 1 and len(pp_hyper) == 1 and list(by_hyper) == list(pp_hyper)):
-            return None
-        (betas, eps_), segs = next(iter(by_hyper.items()))
-        return {"A": (self.P, self.M, self.V, self.free, self.n_params, _merge_segments(segs)),
-                "B": (self.PP, self.GP, self.MP, self.VP, self.pp_len, _merge_segments(pp_hyper[(betas, eps_)])),
-                "t": self.t + 1, "betas": betas, "eps": eps_, "loss_ring": self.loss_ring}
+        """The optimiser step for the step kernel's last launch to run (IrtEngine), or None: loss_and_grads | all-reduce |
+        optimiser stay apart."""
+        return None
 
     def _take_fused_tail(self):
         """{'adam': ...} for the step kernel's call when step() armed the fused tail (once: the call consumes it)."""
-        ft, self._fused_tail = getattr(self, "_fused_tail", None), None
+        ft, self._fused_tail = self._fused_tail, None
         if ft is None:
             return {}
         self._fused_done = True
@@ -707,14 +662,11 @@ class _EngineBase(object):
     # build could reach, so it is opt-in, and a capture that fails with a collective inside it RAISES: the communicator may be
     # unusable after a half-recorded collective, so the process must not carry on (no eager retry).
     use_graph = True
-    score_mfma = os.environ.get("VX_SCORE_MFMA", "1") != "0"      # test seam: 0 = the scalar score-operand kernel for every shape
-    graph_max_persons = int(os.environ.get("VX_GRAPH_MAX_PERSONS", str(1 << 40)))
 
     def _graph_mode(self, rows, b_global, eps, S):
         """The captured form this call can replay -- ('full' | 'rows', nb, b_global) and, with S > 1 particles, S as a fourth
         entry -- or None for an eager step."""
-        if not (self.use_graph and eps is None and self.events is None and isinstance(self.be, HipBackend)
-                and getattr(self, "estimator", "pathwise") == "pathwise"):
+        if not (self.use_graph and eps is None and self.events is None and isinstance(self.be, HipBackend)):
             return None
         if S > 1:
             # Trace_ELBO(num_particles = S) (test.py:430: 20, test.py:607: 10): the S passes, their accumulation and the one
@@ -729,75 +681,17 @@ class _EngineBase(object):
                 return None
             base = self._graph_mode(r0, b_global, None, 1)
             return None if base is None else base + (S,)
-        D, amort = getattr(self, "D", 0), getattr(self, "amortized", True)
-        full = rows is None and (b_global is None or int(b_global) == self.N)
-        if D == 1 and not amort and isinstance(self, IrtEngine):
-            if full:
-                return ("full", self.n_local, self.N)
-            if rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())                       # a subsample: the rows' gradients are scattered into zeroed dense ones
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
-            return None
-        if D > 1 and amort and isinstance(self, IrtEngine):
-            if full:
-                # a large shard runs short kernels BESIDE long ones on a second stream (the last chip round of the forward and
-                # the hidden gradient, the fc1 gradient); the capture keeps those branches as graph edges.  Until round 5 the
-                # replayed 1M step was the slower one (10.7 against 10.1 ms) and shards above 300 k ran eagerly; with the
-                # round-6 kernels it is the faster one at every size measured (tools/step_events_cost.py: 8.97 against
-                # 9.00 ms at 1M, 4.53 against 4.65 at 500 k, 1.46 against 1.63 at 125 k), so every shard replays.
-                # VX_GRAPH_MAX_PERSONS remains as the switch back
-                return ("full", self.n_local, self.N) if self.n_local <= self.graph_max_persons else None
-            if rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
-        if D == 1 and amort and isinstance(self, IrtEngine):
-            # the amortized 1-D guide (VaeIRT x_feature == 1; the reference's Irt2PLMissing.test_ai draws 100 rows a step): the
-            # step kernel's slab sum advances the counter, nothing behind it reads it but Adam
-            if full:
-                return ("full", self.n_local, self.N)
-            if rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
-        if D > 1 and not amort and isinstance(self, IrtEngine):
-            # VIRT with x_feature > 1 (vi.py:706-723; the CFA demo of test.py:420-430 draws 100 rows a particle): the backward
-            # kernel scatters the batch's rows into the zeroed per-person gradients itself
-            if full:
-                return ("full", self.n_local, self.N)
-            if rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
-        if isinstance(self, CdmSfEngine) and getattr(self, "baseline", "none") != "loo":
-            # VCDM / VaeCDM (vi.py:733-816; test.py:522-549: 100 or 1000 rows a step): the Bernoulli draws' Philox step and Adam's
-            # t from the device counter that the loss sum advances (k_cdm_sf reads vx_hodina_cfg.step_dev); the per-person
-            # guide's gather / scatter of the batch rows are torch index kernels inside the capture
-            if full:
-                return ("full", self.n_local, self.N)
-            if rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
-        if isinstance(self, VaeCcdmEngine) and self.group is None:
-            # VaeCCDM (vi.py:868-891; test.py:565,629: 100 or 50 rows a step) on one rank: no random numbers; the softmax over
-            # the batch is three column reductions on the device (sharded, they are small all-reduces between kernels: eager)
-            if full:
-                return ("full", self.n_local, self.N)
-            if rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
-        if isinstance(self, CcdmEngine):
-            # VCCDM (vi.py:819-865; test.py:560,585,624: 100-1500 rows a step): no guide, no random numbers -- the pattern
-            # kernel, the loss sum (which advances the counter Adam reads) and the optimiser
-            if full:
-                return ("full", self.n_local, self.N)
-            if rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
-        if isinstance(self, HoDinaEngine):
-            if full:
-                return ("full", self.n_local, self.N)        # the enumerated HO-DINA step (either guide): three or six launches
-            if amort and rows is not None and not isinstance(rows, (list, tuple)) and self.n_local > 0:
-                nb = int(rows.numel())                       # VaeCHoDina on a subsample (test.py:598-607: 20 rows, 10 particles)
-                return ("rows", nb, int(b_global) if b_global is not None else nb)
+        if rows is None:
+            full = b_global is None or int(b_global) == self.N
+            return ("full", self.n_local, self.N) if full and self._replayable(True) else None
+        if not isinstance(rows, (list, tuple)) and self.n_local > 0 and self._replayable(False):
+            nb = int(rows.numel())
+            return ("rows", nb, int(b_global) if b_global is not None else nb)
         return None
+
+    def _replayable(self, full):
+        """Whether this engine's step replays a captured graph: its full batch (full) or a subsample (not full)."""
+        return False
 
     def _graphable(self):
         """Whether the full-batch step of this engine replays a graph (tests, bench.py)."""
@@ -852,7 +746,7 @@ class _EngineBase(object):
         if rows.is_cuda:
             buf.copy_(rows)
             return
-        ring = getattr(self, "_pin_ring", None)
+        ring = self._pin_ring
         if ring is None or ring[0][0].numel() < nb:
             ring = self._pin_ring = [[torch.empty(max(nb, 1024), dtype=torch.int64).pin_memory(), None] for _ in range(8)]
             self._pin_i = 0
@@ -871,7 +765,7 @@ class _EngineBase(object):
         self._graph = st                                     # (the form last replayed: what tests / bench.py look at)
         key = self._graph_key(lrs)
         if st["graph"] is None or st["key"] != key:
-            if getattr(self, "_ctr", None) is None:
+            if self._ctr is None:
                 self._ctr, self._ctr_t = torch.zeros(1, dtype=torch.int32, device=self.dev), None
             rows_buf = None
             ring = None
@@ -957,7 +851,7 @@ class _EngineBase(object):
     def _steps_form(self, lrs, rows_seq, b_global, scheduler):
         """The single-step form whose K-step graph can take the next K = graph_steps steps of a fit loop, or None."""
         K = self.graph_steps
-        if K < 2 or len(rows_seq) < K or not hasattr(self, "_graphs") or not self._one_graph():
+        if K < 2 or len(rows_seq) < K or not self._graphs or not self._one_graph():
             return None
         mode = self._graph_mode(rows_seq[0], b_global, None, 1)
         if mode is None or any(self._graph_mode(r, b_global, None, 1) != mode for r in rows_seq[1:K]):
@@ -1083,23 +977,64 @@ class _EngineBase(object):
                 torch.cuda.current_stream().synchronize()
             st.clear()                                       # releases the CUDAGraph objects (and their pool) and the rows buffer
 
-    def _particles(self, S, rows_of, b_global, eps_of):
-        """S passes of loss_and_grads (particle sidx = Philox stream sidx) and their mean in G / GP: surrogate / num_particles
-        (SURVEY.md App. B.2).  While a capture records, every pass's last launch advances the device step counter: it is set
-        back behind all but the last, so that the S particles share the step and the optimiser sees step + 1."""
+    def _mean_of_passes(self, S, one_pass):
+        """one_pass(sidx) for sidx < S and the mean of the G / GP they leave: surrogate / num_particles,
+        summed into zeroed accumulators with weight 1 / S and copied back."""
         accG = torch.zeros_like(self.G)
         accP = torch.zeros_like(self.GP) if self.per_person else None
-        sd = getattr(self, "_step_dev", None)
         for sidx in range(S):
-            self.loss_and_grads(rows_of(sidx), b_global, eps_of(sidx), sidx)
-            if sd is not None and sidx < S - 1:
-                sd.sub_(1)
+            one_pass(sidx)
             accG.add_(self.G, alpha=1.0 / S)
             if accP is not None:
                 accP.add_(self.GP, alpha=1.0 / S)
         self.G.copy_(accG)
         if accP is not None:
             self.GP.copy_(accP)
+
+    def _particles(self, S, rows_of, b_global, eps_of):
+        """S passes of loss_and_grads (particle sidx = Philox stream sidx) and their mean in G / GP.  While a capture records,
+        every pass's last launch advances the device step counter: it is set back behind all but the last, so that the S
+        particles share the step and the optimiser sees step + 1."""
+        sd = self._step_dev
+
+        def one_pass(sidx):
+            self.loss_and_grads(rows_of(sidx), b_global, eps_of(sidx), sidx)
+            if sd is not None and sidx < S - 1:
+                sd.sub_(1)
+        self._mean_of_passes(S, one_pass)
+
+    def _score_baseline(self, baseline_buf, guide_grads):
+        """(control variate, decay rate or -1, indexed-by-row flag) of the score-function estimator for this pass."""
+        if baseline_buf is not None:
+            return baseline_buf, -1.0, 0
+        if self.baseline == "avg":
+            return self.base, (self.baseline_beta if guide_grads else -1.0), 1
+        return None, -1.0, 0
+
+    def _loo_step(self, lrs, rows, b_global, eps, S):
+        """A step with the leave-one-out control variate of the score-function estimator (baseline 'loo', S >= 2 particles
+        sharing the step's subsample): a first pass records log_r of every particle in self.last_log_r -- the same Philox draws
+        as the second pass: the particle index is the Philox stream -- and the second pass takes each particle's baseline
+        from the others' mean (vx_loo_baseline)."""
+        rows = self._rows_on_device(rows)
+        r = rows[0] if isinstance(rows, (list, tuple)) else rows
+        nb = self.n_local if r is None else int(r.numel())
+
+        def eps_of(sidx):
+            return eps[sidx] if isinstance(eps, (list, tuple)) else eps
+        lr_all = self._buf("loo_lr_all", S * nb)
+        for sidx in range(S):
+            self.loss_and_grads(r, b_global, eps_of(sidx), sidx, guide_grads=False)
+            lr_all[sidx * nb:(sidx + 1) * nb].copy_(self.last_log_r[:nb])
+        loo = self._buf("loo", nb)
+
+        def one_pass(sidx):
+            self.be.loo_baseline(lr_all, S, nb, sidx, loo)
+            self.loss_and_grads(r, b_global, eps_of(sidx), sidx, baseline_buf=loo)
+        self._mean_of_passes(S, one_pass)
+        self.allreduce()
+        self.apply_optim(lrs)
+        return self.step_loss()
 
     def _rows_on_device(self, rows):
         """Host row indices (the fit loop's draw) for an eager step."""
@@ -1116,8 +1051,6 @@ class _EngineBase(object):
         S = int(num_particles)
         mode = self._graph_mode(rows, b_global, eps, S)
         if mode is not None:
-            if not hasattr(self, "_graphs"):
-                self._graphs = {}
             if mode in self._graphs:
                 self._graphs[mode] = self._graphs.pop(mode)  # most recently used last (dicts keep insertion order)
                 try:
@@ -1174,13 +1107,9 @@ class IrtEngine(_EngineBase):
         if baseline not in ("none", "avg", "loo"):
             raise ValueError("baseline must be 'none', 'avg' or 'loo'")
         self.estimator, self.baseline, self.baseline_beta = estimator, baseline, float(baseline_beta)
-        self.be = backend if backend is not None else HipBackend()
+        self._preamble(y_u8, backend, n_global, gid0, seed, group)
         self.observed_lists = bool(observed_lists) and estimator == "pathwise"
-        self.y = y_u8.contiguous()
-        assert self.y.dtype == torch.uint8 and self.y.dim() == 2
-        self.dev = self.y.device
-        self.n_local, self.J_items = self.y.shape
-        self.y_lik = None
+        self.J_items = self.J
         self.H_model = int(H) if amortized else 0                  # the encoder's hidden units; self.H: what the kernels see
         if amortized and 0 < int(H) < 64 and isinstance(self.be, HipBackend) and self.pad_hidden:
             # PHANTOM HIDDEN UNITS up to 64, the width the MFMA kernels are built for (hidden_dim 32: 23.6 ms a step where 64
@@ -1204,8 +1133,6 @@ class IrtEngine(_EngineBase):
             self.y_lik = torch.cat([self.y, torch.full((self.n_local, pad), 254, dtype=torch.uint8, device=self.dev)], 1).contiguous()
             self.y = torch.cat([self.y, torch.zeros((self.n_local, pad), dtype=torch.uint8, device=self.dev)], 1).contiguous()
         self.J = int(self.y.shape[1])                              # items the kernels see (J_items + phantoms)
-        self.N = int(n_global) if n_global is not None else self.n_local
-        self.gid0 = int(gid0)
         self.model, self.D, self.Dc = model, int(D), float(Dc)
         self.D_model = self.D                                      # the model's latent dimensions; self.D: what the kernels see
         if (amortized and self.D > 1 and self.D % 4 != 0 and self.D + 3 <= 124 and int(H) == 64 and isinstance(self.be, HipBackend)
@@ -1220,22 +1147,14 @@ class IrtEngine(_EngineBase):
             # fc22 rows first.  Not visible through unconstrained() / param().
             self.D = (self.D + 3) // 4 * 4
         self.amortized, self.H, self.share_cov = bool(amortized), int(H) if amortized else 0, bool(share_cov)
-        self.seed, self.group = int(seed), group
         J, Dd = self.J, self.D
         self.off = {"a": 0, "b": Dd * J, "c": Dd * J + J, "d": Dd * J + 2 * J}
         self.shape = {"a": (Dd, J), "b": (1, J), "c": (1, J), "d": (1, J)}
         self.n_item = Dd * J + 3 * J
-        o = (self.n_item + 63) // 64 * 64                         # encoder tensors start on 256-byte boundaries
         if self.amortized:
             T = Dd * (Dd + 1) // 2 if Dd > 1 else 1
-            self.enc_shapes = {"fc1.weight": (self.H, J), "fc1.bias": (self.H,), "fc21.weight": (Dd, self.H),
-                               "fc21.bias": (Dd,), "fc22.weight": (T, self.H), "fc22.bias": (T,)}
-            self.enc_off0 = o
-            for k in ENC_KEYS:
-                self.off["encoder$$$" + k] = o
-                self.shape["encoder$$$" + k] = self.enc_shapes[k]
-                o += int(np.prod(self.enc_shapes[k]))
-            self.n_enc = o - self.enc_off0
+            o = self._encoder_segments({"fc1.weight": (self.H, J), "fc1.bias": (self.H,), "fc21.weight": (Dd, self.H),
+                                        "fc21.bias": (Dd,), "fc22.weight": (T, self.H), "fc22.bias": (T,)})
         else:
             o = self.n_item
             if Dd > 1:                                    # VIRT.guide for x_feature > 1 (vi.py:706-723)
@@ -1293,6 +1212,7 @@ class IrtEngine(_EngineBase):
                 self.view("encoder$$$" + k).copy_(w.reshape(-1))
         self.base = (torch.zeros(max(self.n_local, 1), dtype=torch.float32, device=self.dev)
                      if (estimator == "score" and baseline == "avg") else None)
+        self._sp = self._y_ext = self._y_ext_lik = None      # made on first use (_sparse_lists, _pad_batch)
 
     pad_items = os.environ.get("VX_PAD_ITEMS", "1") != "0"          # test seam: 0 = the kernels see the problem's own item count
 
@@ -1304,7 +1224,8 @@ class IrtEngine(_EngineBase):
         shard's own (index n_local of an extended copy of the responses, every response missing), and loss_and_grads takes
         them out behind the likelihood by their index (columns of gxT / gdT, entries of ll / ent times 0), as _pad_persons
         does for a full batch.  The plate scale stays the caller's: b_global is made explicit.  Amortized multivariate guide,
-        pathwise estimator, HIP backend; rows: one tensor or one per particle."""
+        pathwise estimator, HIP backend; rows: one tensor or a list of them.  Only steps() pads: step() launches a subsample
+        over its own size."""
         if (rows is None or eps is not None or not self.pad_batch or not (self.amortized and self.D > 1 and self.H == 64)
                 or not isinstance(self.be, HipBackend) or self.estimator != "pathwise"):
             return rows, b_global
@@ -1319,7 +1240,7 @@ class IrtEngine(_EngineBase):
         cfg = self.be.cfg(self.model, self.D, self.J, self.H, self.Dc, 1.0, self.seed, 0, 0)
         if self.be.mvn_enc_bwd_layout(cfg, n + pad) != 1 or self.be.mvn_enc_bwd_gd_offset(cfg, n + pad) < 0:
             return rows, b_global
-        if getattr(self, "_y_ext", None) is None:
+        if self._y_ext is None:
             miss = torch.full((1, self.J), 255, dtype=torch.uint8, device=self.dev)
             self._y_ext = torch.cat([self.y, miss]).contiguous()
             self._y_ext_lik = self._y_ext if self.y_lik is None else torch.cat([self.y_lik, miss]).contiguous()
@@ -1327,15 +1248,110 @@ class IrtEngine(_EngineBase):
         return (rs if many else rs[0]), (n if b_global is None else b_global)
 
     def step(self, lrs, rows=None, b_global=None, eps=None, num_particles=1):
-        rows, b_global = self._pad_batch(rows, b_global, eps)
-        return super().step(lrs, rows=rows, b_global=b_global, eps=eps, num_particles=num_particles)
+        """The common step (_EngineBase.step), or the two passes over the particles of the leave-one-out control variate
+        (score-function estimator, baseline 'loo', _loo_step).  A subsample is launched over its own size (steps() pads)."""
+        S = int(num_particles)
+        if self.estimator == "score" and self.baseline == "loo" and S >= 2:
+            return self._loo_step(lrs, rows, b_global, eps, S)
+        return super().step(lrs, rows=rows, b_global=b_global, eps=eps, num_particles=S)
 
     def steps(self, lrs, rows_seq, b_global=None, scheduler=False):
+        """_EngineBase.steps over subsamples padded to a multiple of 4 rows (_pad_batch) when all have one size."""
         if rows_seq and all(torch.is_tensor(r) for r in rows_seq) and len({int(r.numel()) for r in rows_seq}) == 1:
             padded, b_global = self._pad_batch(list(rows_seq), b_global, None)   # (a list: the same rule as for particles)
             rows_seq = padded
         return super().steps(lrs, rows_seq, b_global=b_global, scheduler=scheduler)
 
+    def _pad_persons(self, be, cfg, rows):
+        """Persons the full-batch kernels of the amortized multivariate guide are launched over: the shard's own count, or --
+        when that is not a multiple of 8 -- the next one.  The dimension-major operands of the large-batch kernels are rows of
+        `nb` floats (fp16 planes: `nb` halves) read in 16-byte pieces, so a count that is not a multiple of 8 sends the head
+        weight gradient (and, below a multiple of 4, everything) to the fp32-MFMA generation: 13.9 ms a step at 1 000 004
+        persons, 26.3 at 999 999, against 9.1 at 1 000 000.  The 1-7 PHANTOM persons appended instead have every response
+        missing (byte 255: a finite guide sample, no likelihood term) and are taken out of the step behind the likelihood:
+        their columns of gxT / gdT (everything the backward kernels see of a person) and their entries of ll / ent are zeroed,
+        so they add nothing to any gradient or to the loss.  Pathwise estimator, HIP backend, full batch only."""
+        n = self.n_local
+        if (rows is not None or n % 8 == 0 or n < 8 or not isinstance(be, HipBackend)
+                or self.estimator != "pathwise" or not self.pad_persons):
+            return n
+        n_pad = (n + 7) // 8 * 8
+        return n_pad if (be.mvn_enc_bwd_layout(cfg, n_pad) == 1 and be.mvn_enc_bwd_gd_offset(cfg, n_pad) >= 0) else n
+
+    pad_persons = os.environ.get("VX_PAD_PERSONS", "1") != "0"      # test seam: 0 = launch over the shard's own count
+
+    def _sparse_lists(self, rows):
+        """Observed-cell lists for the D = 1 kernel (include/vipsy_amd.h, vx_irt1d_sparse_grad): built once -- the
+        responses never change -- and only when most cells are missing and the batch is the whole shard.  Persons are
+        placed in slots sorted by list length inside windows of 4096, so the 64 lists a wave walks end together."""
+        if rows is not None or self.n_local == 0 or self.J > 1024 or not self.observed_lists:
+            return None
+        if self._sp is None:
+            y, n, J = (self.y_lik if self.y_lik is not None else self.y), self.n_local, self.J
+            frac = float((y == 255).sum().item()) / float(n * J)
+            if frac < 0.5:
+                self._sp = False
+            else:
+                ng = (n + 63) // 64
+                cnt = torch.full((ng * 64,), -1, dtype=torch.int64, device=self.dev)             # -1: empty slot, sorts last
+                cnt[:n] = (y < 254).sum(1)                                                     # (254: a phantom item, absent)
+                slot = torch.arange(ng * 64, device=self.dev)
+                perm = torch.argsort((slot // 4096) * (J + 2) + (J - cnt), stable=True)           # slot -> person
+                cnt_s = cnt[perm].clamp_(min=0)
+                pidx = torch.where(perm < n, perm, torch.full_like(perm, -1)).to(torch.int32).contiguous()
+                Lq = max(1, (int(cnt_s.max().item()) + 3) // 4)
+                W = min(J, 4 * Lq)
+                pent = torch.full((ng * 64, 4 * Lq), -1, dtype=torch.int16, device=self.dev)      # 0xFFFF = past the end
+                ar = torch.arange(W, device=self.dev)[None, :]
+                for lo in range(0, ng * 64, 65536):                                               # bounded temporaries
+                    hi = min(ng * 64, lo + 65536)
+                    yc = y[perm[lo:hi].clamp(max=n - 1)]
+                    order = torch.argsort((yc >= 254).to(torch.uint8), dim=1, stable=True)[:, :W]  # observed items first
+                    code = order.to(torch.int32) | ((torch.gather(yc, 1, order) == 1).to(torch.int32) << 15)
+                    code = torch.where(ar < cnt_s[lo:hi, None], code, torch.full_like(code, 0xFFFF))
+                    pent[lo:hi, :W] = code.to(torch.int16)                                        # wraps: bit pattern kept
+                pent = pent.reshape(ng, 64, Lq, 4).permute(0, 2, 1, 3).contiguous()
+                glen = ((cnt_s.reshape(ng, 64).max(1).values + 3) // 4).to(torch.int32).contiguous()
+                self._sp = {"pent": pent, "glen": glen, "Lq": Lq, "pidx": pidx, "n_groups": ng, "missing": frac}
+        return self._sp or None
+
+    # -- the optimiser inside the step's last launch (one rank, D = 1 per-person guides) --------------
+    fuse_tail = True
+
+    def _fused_tail_args(self, lrs, rows, eps, S):
+        """What vx_irt1d_grad_adam needs to run Adam in the launch that sums the step's slabs -- or None when this step has
+        to keep loss_and_grads | all-reduce | optimiser apart (a process group, an amortized or multivariate guide, a
+        subsample whose gradients are scattered afterwards, the score-function estimator, more than one (betas, eps))."""
+        if not (self.fuse_tail and self.group is None and S == 1 and rows is None and isinstance(self.be, HipBackend)
+                and self.D == 1 and not self.amortized and self.per_person
+                and self.estimator == "pathwise" and self.events is None and self.n_params == 4 * self.J):
+            return None
+        by_hyper, pp_hyper = self._optim_segments(lrs)
+        if not (len(by_hyper) == 1 and len(pp_hyper) == 1 and list(by_hyper) == list(pp_hyper)):
+            return None
+        (betas, eps_), segs = next(iter(by_hyper.items()))
+        return {"A": (self.P, self.M, self.V, self.free, self.n_params, _merge_segments(segs)),
+                "B": (self.PP, self.GP, self.MP, self.VP, self.pp_len, _merge_segments(pp_hyper[(betas, eps_)])),
+                "t": self.t + 1, "betas": betas, "eps": eps_, "loss_ring": self.loss_ring}
+
+    def _replayable(self, full):
+        # the pathwise estimator, every guide.  D = 1 per-person guide: a full batch is a handful of 10-100 us kernels; a
+        # subsample's gradients are scattered into zeroed dense ones.  The amortized 1-D guide (VaeIRT x_feature == 1; the
+        # reference's Irt2PLMissing.test_ai draws 100 rows a step): the step kernel's slab sum advances the counter, nothing
+        # behind it reads it but Adam.  VIRT with x_feature > 1 (vi.py:706-723; the CFA demo of test.py:420-430 draws 100
+        # rows a particle): the backward kernel scatters the batch's rows into the zeroed per-person gradients itself.
+        # The amortized multivariate guide: a large shard runs short kernels BESIDE long ones on a second stream (the last
+        # chip round of the forward and the hidden gradient, the fc1 gradient); the capture keeps those branches as graph
+        # edges.  Until round 5 the replayed 1M step was the slower one (10.7 against 10.1 ms) and shards above 300 k ran
+        # eagerly; with the round-6 kernels it is the faster one at every size measured (tools/step_events_cost.py: 8.97
+        # against 9.00 ms at 1M, 4.53 against 4.65 at 500 k, 1.46 against 1.63 at 125 k), so every shard replays.
+        # VX_GRAPH_MAX_PERSONS remains as the switch back for its full batch
+        if self.estimator != "pathwise":
+            return False
+        return not (full and self.amortized and self.D > 1 and self.n_local > self.graph_max_persons)
+
+    score_mfma = os.environ.get("VX_SCORE_MFMA", "1") != "0"      # test seam: 0 = the scalar score-operand kernel for every shape
+    graph_max_persons = int(os.environ.get("VX_GRAPH_MAX_PERSONS", str(1 << 40)))
     pad_hidden = os.environ.get("VX_PAD_HIDDEN", "1") != "0"        # test seam: 0 = the kernels see the encoder's own width
     pad_dims = os.environ.get("VX_PAD_DIMS", "1") != "0"            # test seam: 0 = the kernels see the model's own dimensions
 
@@ -1382,9 +1398,6 @@ class IrtEngine(_EngineBase):
             out.append("x_scale")
         return out
 
-    def all_names(self):
-        return self.names() + (list(self.pp_off) if self.per_person else [])
-
     def param(self, name):
         u = self.unconstrained(name)
         if name in ("c", "d"):
@@ -1397,24 +1410,12 @@ class IrtEngine(_EngineBase):
         return u.clone()
 
     # -- one ELBO-gradient step ------------------------------------------------------------------
-    def _score_baseline(self, baseline_buf, guide_grads):
-        """(control variate, decay rate or -1, indexed-by-row flag) of the score-function estimator for this pass."""
-        if baseline_buf is not None:
-            return baseline_buf, -1.0, 0
-        if self.baseline == "avg":
-            return self.base, (self.baseline_beta if guide_grads else -1.0), 1
-        return None, -1.0, 0
-
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, guide_grads=True):
         """Fills self.G (flat grads + loss slot) and per-person grads for ONE particle.
         rows: int64 device tensor of LOCAL row indices (None = all local rows, i.e. full batch).
         baseline_buf / guide_grads: the 'loo' mode of the score-function estimator (step())."""
         be = self.be
-        nb = self.n_local if rows is None else int(rows.numel())
-        Bg = int(b_global) if b_global is not None else (self.N if rows is None else nb)
-        scale = float(self.N) / float(Bg)
-        sd = getattr(self, "_step_dev", None)               # captured step: the step count lives in device memory
-        sdc = {"step_dev": sd} if sd is not None else {}
+        nb, scale, sdc = self._call(rows, b_global)       # (sdc: a captured step's count lives in device memory)
         cfg = be.cfg(self.model, self.D, self.J, self.H, self.Dc, scale, self.seed, self.t, stream_id, **sdc)
         c_un = self.view("c") if self.model in ("irt_3pl", "irt_4pl") else None
         d_un = self.view("d") if self.model == "irt_4pl" else None
@@ -1464,7 +1465,7 @@ class IrtEngine(_EngineBase):
                 eps = e_p
             n_valid, y_k, y_l = nb, self.y, (self.y_lik if self.y_lik is not None else self.y)
             keep = None
-            if rows is not None and getattr(self, "_y_ext", None) is not None:
+            if rows is not None and self._y_ext is not None:
                 # rows of a padded subsample may point at the phantom person behind the shard's own (_pad_batch)
                 y_k, y_l = self._y_ext, self._y_ext_lik
                 keep = (rows != self.n_local).to(torch.float32)
@@ -1495,12 +1496,12 @@ class IrtEngine(_EngineBase):
                 fw["hs"] = encb_ws[hs_off:hs_off + nb * 64]
             with self._phase("guide_forward"):
                 cfg_f = cfg
-                ring = getattr(self, "_capture_ring", None)
-                if ring is not None and rows is not None and sd is not None and isinstance(be, HipBackend):
+                ring = self._capture_ring
+                if ring is not None and rows is not None and self._step_dev is not None and isinstance(be, HipBackend):
                     # a captured subsampled step: the forward call's first launch fetches the step's draw from the pinned
                     # host ring (vx_irt_cfg.rows_ring) -- no copy in front of every replay
                     cfg_f = be.cfg(self.model, self.D, self.J, self.H, self.Dc, scale, self.seed, self.t, stream_id,
-                                   step_dev=sd, rows_ring=ring)
+                                   step_dev=self._step_dev, rows_ring=ring)
                     self._capture_ring_used = True
                 be.mvn_enc_forward(cfg_f, y_k, rows, nb, self.gid0, enc, eps, fw)
             gd_off = be.mvn_enc_bwd_gd_offset(cfg, nb)     # the backward's DIAG-row operand, made in the likelihood's last pass
@@ -1586,16 +1587,15 @@ class IrtEngine(_EngineBase):
             else:
                 loc, raw, gloc, graw = self._gather_pp(rows, nb)
             lists = self._sparse_lists(rows)
-            sdk = sdc                                              # captured step: the step count lives in device memory
             with self._phase("irt1d"):
                 if lists is not None:                      # mostly-missing responses: observed cells only
                     sp_ws = self._buf("i1d_sp_ws", be.irt1d_sparse_workspace(cfg, lists["n_groups"]))
                     be.irt1d_sparse_grad(cfg, lists, self.gid0, loc, raw, eps, a, self.view("b"), c_un, d_un,
-                                         gloc, graw, elbo, g1d, sp_ws, loss=lossslot, **sdk, **self._take_fused_tail())
+                                         gloc, graw, elbo, g1d, sp_ws, loss=lossslot, **sdc, **self._take_fused_tail())
                 else:
                     be.irt1d_grad(cfg, self.y_lik if self.y_lik is not None else self.y, rows, nb, self.gid0, loc, raw, eps, a,
                                   self.view("b"), c_un, d_un,
-                                  gloc, graw, elbo, g1d, i1d_ws, loss=lossslot, **sdk, **self._take_fused_tail())
+                                  gloc, graw, elbo, g1d, i1d_ws, loss=lossslot, **sdc, **self._take_fused_tail())
             if self.estimator == "score":
                 # score-function gradient of the guide in place of the pathwise one (the step kernel's item gradients and
                 # loss stand); the draws are the step's own Philox normals, keyed by the global person id
@@ -1624,42 +1624,6 @@ class IrtEngine(_EngineBase):
             self.last = {"elbo": elbo, "nb": nb}                # the loss itself came out of the kernel's reduction
 
 
-def _irt_step(self, lrs, rows=None, b_global=None, eps=None, num_particles=1):
-    """IrtEngine.step: the leave-one-out control variate of the score-function estimator needs two passes over the
-    particles (log_r of every particle first; the same Philox draws both times: the particle index is the Philox stream);
-    everything else is the common step."""
-    S = int(num_particles)
-    if self.estimator != "score" or self.baseline != "loo" or S < 2:
-        return _EngineBase.step(self, lrs, rows=rows, b_global=b_global, eps=eps, num_particles=S)
-    rows = self._rows_on_device(rows)
-    r = rows[0] if isinstance(rows, (list, tuple)) else rows
-    nb = self.n_local if r is None else int(r.numel())
-    lr_all = self._buf("sf_lr_all", S * nb)
-    for sidx in range(S):
-        e = eps[sidx] if isinstance(eps, (list, tuple)) else eps
-        self.loss_and_grads(r, b_global, e, sidx, guide_grads=False)
-        lr_all[sidx * nb:(sidx + 1) * nb].copy_(self.last_log_r[:nb])
-    accG = torch.zeros_like(self.G)
-    accP = torch.zeros_like(self.GP) if self.per_person else None
-    loo = self._buf("sf_loo", nb)
-    for sidx in range(S):
-        e = eps[sidx] if isinstance(eps, (list, tuple)) else eps
-        self.be.loo_baseline(lr_all, S, nb, sidx, loo)
-        self.loss_and_grads(r, b_global, e, sidx, baseline_buf=loo)
-        accG.add_(self.G, alpha=1.0 / S)
-        if accP is not None:
-            accP.add_(self.GP, alpha=1.0 / S)
-    self.G.copy_(accG)
-    if accP is not None:
-        self.GP.copy_(accP)
-    self.allreduce()
-    self.apply_optim(lrs)
-    return self.step_loss()
-
-
-IrtEngine.step = _irt_step
-
-
 class HoDinaEngine(_EngineBase):
     """HO-DINA ELBO-gradient step with exact enumeration (VCHoDina / VaeCHoDina, vi.py:894-981).
 
@@ -1670,19 +1634,8 @@ class HoDinaEngine(_EngineBase):
 
     def __init__(self, y_u8, q, n_global=None, gid0=0, amortized=False, H=64, encoder_init=None, seed=1234,
                  group=None, backend=None):
-        self.be = backend if backend is not None else HipBackend()
-        self.y = y_u8.contiguous()
-        assert self.y.dtype == torch.uint8 and self.y.dim() == 2
-        self.dev = self.y.device
-        self.n_local, self.J = self.y.shape
-        self.N = int(n_global) if n_global is not None else self.n_local
-        self.gid0 = int(gid0)
-        q = torch.as_tensor(q, dtype=torch.float32)
-        assert q.dim() == 2 and q.shape[1] == self.J
-        if not bool(((q == 0) | (q == 1)).all()):
-            raise ValueError("the Q-matrix must be binary (the subset test of vi.py:78-81 assumes it)")
-        self.K = int(q.shape[0])
-        self.q = q.to(self.dev).contiguous()
+        self._preamble(y_u8, backend, n_global, gid0, seed, group)
+        self._q_matrix(q, "the subset test of vi.py:78-81 assumes it")
         self.amortized, self.H = bool(amortized), int(H) if amortized else 0
         # The amortized guide's ENCODER on the MFMA kernels whatever the item count and width (the reference's HO-DINA has 30
         # items: its full-batch step took 0.81 ms at 200 k persons where 32 items take 0.24, tools/hodina_cliffs.py): the
@@ -1698,26 +1651,18 @@ class HoDinaEngine(_EngineBase):
                 self.J_enc = (self.J + 3) // 4 * 4
                 self.y_enc = torch.cat([self.y, torch.zeros((self.n_local, self.J_enc - self.J), dtype=torch.uint8,
                                                             device=self.dev)], 1).contiguous()
-        self.seed, self.group = int(seed), group
         J, K = self.J, self.K
         self.off = {"g": 0, "s": J, "lam0": 2 * J, "lam1": 2 * J + K}
         self.shape = {"g": (1, J), "s": (1, J), "lam0": (1, K), "lam1": (1, K)}
         self.n_item = 2 * J + 2 * K
         o = self.n_item
         if self.amortized:
-            o = (self.n_item + 63) // 64 * 64
-            self.enc_shapes = {"fc1.weight": (self.H, self.J_enc), "fc1.bias": (self.H,), "fc21.weight": (1, self.H),
-                               "fc21.bias": (1,), "fc22.weight": (1, self.H), "fc22.bias": (1,)}
-            self.enc_off0 = o
-            for k in ENC_KEYS:
-                self.off["encoder$$$" + k] = o
-                self.shape["encoder$$$" + k] = self.enc_shapes[k]
-                o += int(np.prod(self.enc_shapes[k]))
-            self.n_enc = o - self.enc_off0
+            o = self._encoder_segments({"fc1.weight": (self.H, self.J_enc), "fc1.bias": (self.H,), "fc21.weight": (1, self.H),
+                                        "fc21.bias": (1,), "fc22.weight": (1, self.H), "fc22.bias": (1,)})
         self._alloc(o, self.n_local, per_person=not self.amortized)
+        self._yT_enc = None
         # vi.py:901-904: lam0 = 0, lam1 = 1 (positive -> log 1 = 0), g = s = 0.1 (interval(0,1) -> logit)
-        self.view("g").fill_(float(np.float32(_logit(np.float32(0.1)))))
-        self.view("s").fill_(float(np.float32(_logit(np.float32(0.1)))))
+        self._init_g_s()
         if self.amortized:
             Hm = self.H_model
             if encoder_init is None:
@@ -1747,25 +1692,13 @@ class HoDinaEngine(_EngineBase):
 
     def _item_major_y_enc(self, rows):
         """The encoder's item-major responses (_item_major_y over the encoder's copy: phantom item rows hold byte 0)."""
-        if self.J_enc == self.J:
-            return self._item_major_y(rows)
-        if rows is not None or self.n_local == 0:
-            return None
-        if getattr(self, "_yT_enc", None) is None:
-            stride = (self.n_local + 63) // 64 * 64
-            yT = torch.full((self.J_enc + 1, stride), 254, dtype=torch.uint8, device=self.dev)
-            yT[:self.J_enc, :self.n_local] = self.y_enc.t()
-            self._yT_enc = yT
-        return self._yT_enc
+        return self._item_major_y(rows) if self.J_enc == self.J else self._item_major_y(rows, "_yT_enc", self.y_enc)
 
     def names(self):
         out = ["g", "s", "lam0", "lam1"]
         if self.amortized:
             out += ["encoder$$$" + k for k in ENC_KEYS]
         return out
-
-    def all_names(self):
-        return self.names() + (list(self.pp_names) if self.per_person else [])
 
     def param(self, name):
         u = self.unconstrained(name)
@@ -1775,13 +1708,14 @@ class HoDinaEngine(_EngineBase):
             return torch.exp(u)
         return u.clone()
 
+    def _replayable(self, full):
+        # the enumerated HO-DINA step (either guide): three or six launches; a subsample with the amortized guide
+        # (VaeCHoDina, test.py:598-607: 20 rows, 10 particles)
+        return full or self.amortized
+
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0):
         be = self.be
-        nb = self.n_local if rows is None else int(rows.numel())
-        Bg = int(b_global) if b_global is not None else (self.N if rows is None else nb)
-        scale = float(self.N) / float(Bg)
-        sd = getattr(self, "_step_dev", None)               # captured step: the step count lives in device memory
-        sdc = {"step_dev": sd} if sd is not None else {}
+        nb, scale, sdc = self._call(rows, b_global)       # (sdc: a captured step's count lives in device memory)
         cfg = be.hodina_cfg(self.K, self.J, self.H, scale, self.seed, self.t, stream_id, **sdc)
         elbo = self._buf("elbo", nb)
         ws = self._buf("hd_ws", be.hodina_workspace(cfg, nb))
@@ -1827,45 +1761,30 @@ class CcdmEngine(_EngineBase):
     def __init__(self, y_u8, q, cdm="dina", n_global=None, gid0=0, seed=1234, group=None, backend=None):
         if cdm not in ("dina", "dino"):
             raise ValueError("model must be 'dina' or 'dino' (BaseCDM.CDM_FUN, vi.py:728-731)")
-        self.be = backend if backend is not None else HipBackend()
-        self.y = y_u8.contiguous()
-        assert self.y.dtype == torch.uint8 and self.y.dim() == 2
-        self.dev = self.y.device
-        self.n_local, self.J = self.y.shape
-        self.N = int(n_global) if n_global is not None else self.n_local
-        self.gid0 = int(gid0)
-        q = torch.as_tensor(q, dtype=torch.float32)
-        assert q.dim() == 2 and q.shape[1] == self.J
-        if not bool(((q == 0) | (q == 1)).all()):
-            raise ValueError("the Q-matrix must be binary (the subset tests of vi.py:78-81, 96-100 assume it)")
-        self.K = int(q.shape[0])
-        self.q = q.to(self.dev).contiguous()
+        self._preamble(y_u8, backend, n_global, gid0, seed, group)
+        self._q_matrix(q)
         self.cdm, self.amortized, self.H = cdm, False, 0
-        self.seed, self.group = int(seed), group
         J = self.J
         self.off = {"g": 0, "s": J}
         self.shape = {"g": (1, J), "s": (1, J)}
         self.n_item = 2 * J
         self._alloc(self.n_item, self.n_local, per_person=False)
-        self.view("g").fill_(float(np.float32(_logit(np.float32(0.1)))))      # vi.py:844-845: g = s = 0.1
-        self.view("s").fill_(float(np.float32(_logit(np.float32(0.1)))))
+        self._init_g_s()                                                     # vi.py:844-845: g = s = 0.1
 
     def names(self):
         return ["g", "s"]
 
-    def all_names(self):
-        return self.names()
-
     def param(self, name):
         return torch.sigmoid(self.unconstrained(name))
 
+    def _replayable(self, full):
+        # VCCDM (vi.py:819-865; test.py:560,585,624: 100-1500 rows a step): no guide, no random numbers -- the pattern
+        # kernel, the loss sum (which advances the counter Adam reads) and the optimiser
+        return True
+
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0):
         be = self.be
-        nb = self.n_local if rows is None else int(rows.numel())
-        Bg = int(b_global) if b_global is not None else (self.N if rows is None else nb)
-        scale = float(self.N) / float(Bg)
-        sd = getattr(self, "_step_dev", None)               # captured step: the loss sum advances the device counter
-        sdc = {"step_dev": sd} if sd is not None else {}
+        nb, scale, sdc = self._call(rows, b_global)       # (sdc: a captured step's loss sum advances the device counter)
         cfg = be.hodina_cfg(self.K, self.J, 0, scale, self.seed, self.t, stream_id)
         elbo = self._buf("elbo", nb)
         ws = self._buf("cd_ws", be.ccdm_workspace(cfg, nb))
@@ -1888,37 +1807,17 @@ class VaeCcdmEngine(_EngineBase):
                  backend=None):
         if cdm not in ("dina", "dino"):
             raise ValueError("model must be 'dina' or 'dino' (BaseCDM.CDM_FUN, vi.py:728-731)")
-        self.be = backend if backend is not None else HipBackend()
-        self.y = y_u8.contiguous()
-        assert self.y.dtype == torch.uint8 and self.y.dim() == 2
-        self.dev = self.y.device
-        self.n_local, self.J = self.y.shape
-        self.N = int(n_global) if n_global is not None else self.n_local
-        self.gid0 = int(gid0)
-        q = torch.as_tensor(q, dtype=torch.float32)
-        assert q.dim() == 2 and q.shape[1] == self.J
-        if not bool(((q == 0) | (q == 1)).all()):
-            raise ValueError("the Q-matrix must be binary (the subset tests of vi.py:78-81, 96-100 assume it)")
-        self.K = int(q.shape[0])
+        self._preamble(y_u8, backend, n_global, gid0, seed, group)
+        self._q_matrix(q)
         self.C = 1 << self.K
-        self.q = q.to(self.dev).contiguous()
         self.cdm, self.amortized, self.H = cdm, True, int(H)
-        self.seed, self.group = int(seed), group
         J, C = self.J, self.C
         self.off = {"g": 0, "s": J}
         self.shape = {"g": (1, J), "s": (1, J)}
         self.n_item = 2 * J
-        o = (self.n_item + 63) // 64 * 64
-        self.enc_shapes = {"fc1.weight": (self.H, J), "fc1.bias": (self.H,), "fc2.weight": (C, self.H), "fc2.bias": (C,)}
-        self.enc_off0 = o
-        for k in BIN_ENC_KEYS:
-            self.off["encoder$$$" + k] = o
-            self.shape["encoder$$$" + k] = self.enc_shapes[k]
-            o += int(np.prod(self.enc_shapes[k]))
-        self.n_enc = o - self.enc_off0
+        o = self._encoder_segments({"fc1.weight": (self.H, J), "fc1.bias": (self.H,), "fc2.weight": (C, self.H), "fc2.bias": (C,)})
         self._alloc(o, self.n_local, per_person=False)
-        self.view("g").fill_(float(np.float32(_logit(np.float32(0.1)))))      # vi.py:875-876
-        self.view("s").fill_(float(np.float32(_logit(np.float32(0.1)))))
+        self._init_g_s()                                                     # vi.py:875-876
         if encoder_init is None:
             encoder_init = default_bin_encoder_init(J, C, self.H, seed)       # same nn.Linear shapes with C outputs
         for k in BIN_ENC_KEYS:
@@ -1927,32 +1826,21 @@ class VaeCcdmEngine(_EngineBase):
     def names(self):
         return ["g", "s"] + ["encoder$$$" + k for k in BIN_ENC_KEYS]
 
-    def all_names(self):
-        return self.names()
-
     def param(self, name):
         u = self.unconstrained(name)
         return torch.sigmoid(u) if name in ("g", "s") else u.clone()
 
-    def _allreduce_small(self, t, op):
-        if self.group is not None:
-            if t.is_cuda and torch.distributed.get_backend(self.group) == "gloo":
-                host = t.cpu()
-                torch.distributed.all_reduce(host, op=op, group=self.group)
-                t.copy_(host)
-            else:
-                torch.distributed.all_reduce(t, op=op, group=self.group)
+    def _replayable(self, full):
+        # on one rank (VaeCCDM, vi.py:868-891; test.py:565,629: 100 or 50 rows a step): no random numbers; the softmax over
+        # the batch is three column reductions on the device (sharded, they are small all-reduces between kernels: eager)
+        return self.group is None
 
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0):
         be = self.be
-        nb = self.n_local if rows is None else int(rows.numel())
-        Bg = int(b_global) if b_global is not None else (self.N if rows is None else nb)
-        scale = float(self.N) / float(Bg)
+        nb, scale, sdc = self._call(rows, b_global)       # (sdc: a captured step's loss sum advances the device counter)
         C, H = self.C, self.H
-        sd = getattr(self, "_step_dev", None)               # captured step: the loss sum advances the device counter
-        sdc = {"step_dev": sd} if sd is not None else {}
         cfg = be.hodina_cfg(self.K, self.J, H, scale, self.seed, self.t, stream_id)
-        enc = {k: self.view("encoder$$$" + k) for k in BIN_ENC_KEYS}
+        enc = self._enc()
         h, z, gla = self._buf("vc_h", nb * H), self._buf("vc_z", nb * C), self._buf("vc_gla", nb * C)
         m, Z, T = self._buf("vc_m", C), self._buf("vc_Z", C), self._buf("vc_T", C)
         cws = self._buf("vc_cws", be.col_reduce_workspace(max(nb, 1), C))
@@ -1961,9 +1849,9 @@ class VaeCcdmEngine(_EngineBase):
         with self._phase("guide_forward"):
             be.sm_enc_forward(cfg, self.y, rows, nb, enc, h, z)
             be.col_reduce(0, z, nb, C, None, m, cws)                      # column maximum over the batch ...
-            self._allreduce_small(m[:C], torch.distributed.ReduceOp.MAX)  # ... of every rank
+            self._allreduce(m[:C], torch.distributed.ReduceOp.MAX)       # ... of every rank
             be.col_reduce(1, z, nb, C, m, Z, cws)
-            self._allreduce_small(Z[:C], torch.distributed.ReduceOp.SUM)
+            self._allreduce(Z[:C])
             off = self._buf("vc_off", C)
             torch.add(m[:C], torch.log(Z[:C]), out=off[:C])               # attr_p = exp(z - off)
         with self._phase("vaeccdm"):
@@ -1971,7 +1859,7 @@ class VaeCcdmEngine(_EngineBase):
                             gla, self.G[:self.n_item], ws)
         with self._phase("guide_backward"):
             be.col_reduce(2, gla, nb, C, None, T, cws)
-            self._allreduce_small(T[:C], torch.distributed.ReduceOp.SUM)
+            self._allreduce(T[:C])
             bws = self._buf("vc_bws", be.sm_enc_bwd_workspace(cfg, nb))
             be.sm_enc_backward(cfg, self.y, rows, nb, enc, h, z, off, T, gla,
                                self.G[self.enc_off0:self.enc_off0 + self.n_enc], bws)
@@ -2000,24 +1888,12 @@ class CdmSfEngine(_EngineBase):
             raise ValueError("model must be 'dina' or 'dino' (BaseCDM.CDM_FUN, vi.py:728-731)")
         if baseline not in ("none", "avg", "loo"):
             raise ValueError("baseline must be 'none', 'avg' or 'loo'")
-        self.be = backend if backend is not None else HipBackend()
-        self.y = y_u8.contiguous()
-        assert self.y.dtype == torch.uint8 and self.y.dim() == 2
+        self._preamble(y_u8, backend, n_global, gid0, seed, group)
         if bool((self.y > 1).any()):
             raise ValueError("VCDM / VaeCDM need complete 0/1 responses: the reference hands them to the likelihood "
                              "unmasked (vi.py:756), a missing cell makes its loss NaN")
-        self.dev = self.y.device
-        self.n_local, self.J = self.y.shape
-        self.N = int(n_global) if n_global is not None else self.n_local
-        self.gid0 = int(gid0)
-        q = torch.as_tensor(q, dtype=torch.float32)
-        assert q.dim() == 2 and q.shape[1] == self.J
-        if not bool(((q == 0) | (q == 1)).all()):
-            raise ValueError("the Q-matrix must be binary (the subset tests of vi.py:78-81, 96-100 assume it)")
-        self.K = int(q.shape[0])
-        self.q = q.to(self.dev).contiguous()
+        self._q_matrix(q)
         self.cdm, self.amortized, self.H = cdm, bool(amortized), int(H) if amortized else 0
-        self.seed, self.group = int(seed), group
         self.attr_prior = CDM_REF_PRIOR if attr_prior is None else float(attr_prior)
         self.baseline, self.baseline_beta = baseline, float(baseline_beta)
         J, K = self.J, self.K
@@ -2026,18 +1902,10 @@ class CdmSfEngine(_EngineBase):
         self.n_item = 2 * J
         o = self.n_item
         if self.amortized:
-            o = (self.n_item + 63) // 64 * 64
-            self.enc_shapes = {"fc1.weight": (self.H, J), "fc1.bias": (self.H,), "fc2.weight": (K, self.H), "fc2.bias": (K,)}
-            self.enc_off0 = o
-            for k in BIN_ENC_KEYS:
-                self.off["encoder$$$" + k] = o
-                self.shape["encoder$$$" + k] = self.enc_shapes[k]
-                o += int(np.prod(self.enc_shapes[k]))
-            self.n_enc = o - self.enc_off0
+            o = self._encoder_segments({"fc1.weight": (self.H, J), "fc1.bias": (self.H,), "fc2.weight": (K, self.H), "fc2.bias": (K,)})
         self.pp_shape = {"attr_p": (self.n_local, K)}
         self._alloc(o, self.n_local, per_person=not self.amortized)
-        self.view("g").fill_(float(np.float32(_logit(np.float32(0.1)))))      # vi.py:748-749: g = s = 0.1
-        self.view("s").fill_(float(np.float32(_logit(np.float32(0.1)))))
+        self._init_g_s()                                                     # vi.py:748-749: g = s = 0.1
         if self.amortized:
             if encoder_init is None:
                 encoder_init = default_bin_encoder_init(J, K, self.H, seed)
@@ -2048,9 +1916,6 @@ class CdmSfEngine(_EngineBase):
     def names(self):
         return ["g", "s"] + (["encoder$$$" + k for k in BIN_ENC_KEYS] if self.amortized else [])
 
-    def all_names(self):
-        return self.names() + (list(self.pp_names) if self.per_person else [])
-
     def param(self, name):
         u = self.unconstrained(name)
         if name in ("g", "s"):
@@ -2059,37 +1924,28 @@ class CdmSfEngine(_EngineBase):
             return torch.clamp(torch.sigmoid(u), min=float(np.finfo(np.float32).tiny), max=1.0 - float(np.finfo(np.float32).eps))
         return u.clone()
 
-    def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, grads=True):
+    def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, guide_grads=True):
         """One particle.  `eps`: uint8 (nb, K) attribute draws to replay, or None (drawn in the kernel from Philox, keyed
-        by the global person id).  baseline_buf: explicit control variate in batch order (the 'loo' mode of step())."""
+        by the global person id).  baseline_buf / guide_grads: the 'loo' mode (step(), _loo_step)."""
         be = self.be
-        nb = self.n_local if rows is None else int(rows.numel())
-        Bg = int(b_global) if b_global is not None else (self.N if rows is None else nb)
-        scale = float(self.N) / float(Bg)
+        nb, scale, sdc = self._call(rows, b_global)       # (sdc: a captured step's count lives in device memory)
         K = self.K
-        sd = getattr(self, "_step_dev", None)               # captured step: the step count lives in device memory
-        sdc = {"step_dev": sd} if sd is not None else {}
         cfg = be.hodina_cfg(K, self.J, self.H, scale, self.seed, self.t, stream_id, **sdc)
         ws = self._buf("cs_ws", be.cdm_sf_workspace(cfg, nb))
-        gu, log_r = self._buf("cs_gu", nb * K), self._buf("cs_lr%d" % stream_id if not grads else "cs_lr", nb)
+        gu, log_r = self._buf("cs_gu", nb * K), self._buf("cs_lr%d" % stream_id if not guide_grads else "cs_lr", nb)
         if self.amortized:
-            enc = {k: self.view("encoder$$$" + k) for k in BIN_ENC_KEYS}
+            enc = self._enc()
             h, u = self._buf("cs_h", nb * self.H), self._buf("cs_u", nb * K)
             with self._phase("guide_forward"):
                 be.bin_enc_forward(cfg, self.y, rows, nb, enc, h, u)
         else:
             u = self.PP if rows is None else self.PP.reshape(self.n_local, K)[rows].contiguous().reshape(-1)
-        if baseline_buf is not None:
-            base, beta, by_row = baseline_buf, -1.0, 0
-        elif self.baseline == "avg":
-            base, beta, by_row = self.base, (self.baseline_beta if grads else -1.0), 1
-        else:
-            base, beta, by_row = None, -1.0, 0
+        base, beta, by_row = self._score_baseline(baseline_buf, guide_grads)
         with self._phase("cdm_sf"):
             be.cdm_sf_grad(cfg, self.cdm == "dino", not self.amortized, self.attr_prior, self.y, rows, nb, self.gid0, self.q,
                            self.view("g"), self.view("s"), u, eps, base, beta, by_row, gu, log_r, None,
                            self.G[:self.n_item], ws)
-        if grads:
+        if guide_grads:
             if self.amortized:
                 with self._phase("guide_backward"):
                     bw = self._buf("cs_bws", be.bin_enc_bwd_workspace(cfg, nb))
@@ -2100,39 +1956,23 @@ class CdmSfEngine(_EngineBase):
             else:                                              # dense per-person gradient: zero off the batch (vi.py:811)
                 self.GP.zero_()
                 self.GP.reshape(self.n_local, K).index_add_(0, rows, gu[:nb * K].reshape(nb, K))
-        be.sum_into(log_r, nb, -1.0, self.G[self.n_params:self.n_params + 1], self.sum_ws, **(sdc if grads else {}))
+        be.sum_into(log_r, nb, -1.0, self.G[self.n_params:self.n_params + 1], self.sum_ws, **(sdc if guide_grads else {}))
+        self.last_log_r = log_r
         self.last = {"log_r": log_r, "gu": gu, "nb": nb}
 
     def step(self, lrs, rows=None, b_global=None, eps=None, num_particles=1):
+        """The common step (_EngineBase.step), or the two passes over the particles of the leave-one-out control variate
+        (baseline 'loo', _loo_step)."""
         S = int(num_particles)
-        if self.baseline != "loo" or S < 2:
-            return super().step(lrs, rows=rows, b_global=b_global, eps=eps, num_particles=S)
-        # leave-one-out control variate: a first pass records log_r of every particle (same subsample, the same Philox
-        # draws as the second pass: the particle index is the Philox stream), the second pass uses the means
-        rows = self._rows_on_device(rows)
-        r = rows[0] if isinstance(rows, (list, tuple)) else rows
-        nb = self.n_local if r is None else int(r.numel())
-        lr_all = self._buf("cs_lr_all", S * nb)
-        for sidx in range(S):
-            e = eps[sidx] if isinstance(eps, (list, tuple)) else eps
-            self.loss_and_grads(r, b_global, e, sidx, grads=False)
-            lr_all[sidx * nb:(sidx + 1) * nb].copy_(self.last["log_r"][:nb])
-        accG = torch.zeros_like(self.G)
-        accP = torch.zeros_like(self.GP) if self.per_person else None
-        loo = self._buf("cs_loo", nb)
-        for sidx in range(S):
-            e = eps[sidx] if isinstance(eps, (list, tuple)) else eps
-            self.be.loo_baseline(lr_all, S, nb, sidx, loo)
-            self.loss_and_grads(r, b_global, e, sidx, baseline_buf=loo)
-            accG.add_(self.G, alpha=1.0 / S)
-            if accP is not None:
-                accP.add_(self.GP, alpha=1.0 / S)
-        self.G.copy_(accG)
-        if accP is not None:
-            self.GP.copy_(accP)
-        self.allreduce()
-        self.apply_optim(lrs)
-        return self.step_loss()
+        if self.baseline == "loo" and S >= 2:
+            return self._loo_step(lrs, rows, b_global, eps, S)
+        return super().step(lrs, rows=rows, b_global=b_global, eps=eps, num_particles=S)
+
+    def _replayable(self, full):
+        # VCDM / VaeCDM (vi.py:733-816; test.py:522-549: 100 or 1000 rows a step): the Bernoulli draws' Philox step and Adam's
+        # t from the device counter that the loss sum advances (k_cdm_sf reads vx_hodina_cfg.step_dev); the per-person
+        # guide's gather / scatter of the batch rows are torch index kernels inside the capture.  Not the two passes of 'loo'
+        return self.baseline != "loo"
 
 
 def default_bin_encoder_init(J, K, H, seed):
