@@ -90,13 +90,38 @@ EncDims make_enc_dims(const vx_irt_cfg* cfg, int64_t nb) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// VX_FORCE_GENERIC=1 routes everything through the shape-generic kernels (used by the tests to
-// cross-check the specialised fast paths against them).
-bool force_generic() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VX_FORCE_GENERIC"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
+// The test seams of the library, read from the environment once (tests/test_gpu_parity.py):
+//   VX_FORCE_GENERIC=1  routes everything through the shape-generic kernels (to cross-check the specialised paths);
+//   VX_MFMA16           the 16-bit-MFMA kernels (fp32 operands as fp16 pairs -- f16x2, vx_common.h -- or, in the likelihood
+//                       and the fc1 gradient, as bf16 terms; fp32 accumulate; results at the accuracy of the fp32-MFMA chain)
+//                       are the default (unset or 1); 0 selects the fp32-MFMA kernels, f / w / h / g only the guide forward /
+//                       the head weight gradient / the hidden gradient / the fc1 weight gradient on the 16-bit MFMA;
+//   VX_FWD_RING=0       the large-batch guide forward pulls its head tiles per wave (the form before the shared LDS ring of
+//                       k_mvn_fwd_b2.hip);
+//   VX_SCORE_NO_RING    the score-function heads kernel in its plain form at every batch size.
+struct Seams {
+    bool generic;
+    bool fwd16, w16, h16, fc1_16;                          // VX_MFMA16: f, w, h, g
+    // the side streams of the guide's forward and backward (the forward's and the hidden gradient's short last rounds, the
+    // fc1 and head weight gradients beside the hidden gradient) go with the fc1 seam: VX_MFMA16 = 0 / f / w / h is one stream
+    bool side_streams;
+    bool fwd_ring, score_ring;
+};
+const Seams& seams() {
+    static const Seams s = [] {
+        Seams v;
+        const char *g = getenv("VX_FORCE_GENERIC"), *m = getenv("VX_MFMA16"), *r = getenv("VX_FWD_RING");
+        v.generic = g && g[0] == '1';
+        const int mode = (!m || m[0] == '1') ? 15 : (m[0] == 'f' ? 1 : m[0] == 'w' ? 2 : m[0] == 'h' ? 4 : m[0] == 'g' ? 8 : 0);
+        v.fwd16 = mode & 1; v.w16 = mode & 2; v.h16 = mode & 4; v.fc1_16 = mode & 8;
+        v.side_streams = v.fc1_16;
+        v.fwd_ring = !(r && r[0] == '0');
+        v.score_ring = getenv("VX_SCORE_NO_RING") == nullptr;
+        return v;
+    }();
+    return s;
 }
+bool force_generic() { return seams().generic; }
 
 // shapes of the packed head layout (k_pack.hip); the others keep the reference row order
 bool packed_ok(const vx_irt_cfg* cfg) {
@@ -104,31 +129,9 @@ bool packed_ok(const vx_irt_cfg* cfg) {
            enc_p_lds_floats(cfg->D, cfg->J) * sizeof(float) <= 160 * 1024 &&
            enc_bwdw_fast_lds_floats(cfg->D) * sizeof(float) <= 160 * 1024;
 }
-
-// 16-bit-MFMA kernels (fp32 operands as fp16 pairs -- f16x2, vx_common.h -- or, in the likelihood and the fc1 gradient, as
-// bf16 terms; fp32 accumulate; results at the accuracy of the fp32-MFMA chain): the default.  VX_MFMA16 = 0 selects the
-// fp32-MFMA kernels, f / w / h / g only the guide forward / the head weight gradient / the hidden gradient / the fc1 weight
-// gradient on the 16-bit MFMA (a test seam: tests/test_gpu_parity.py::test_generic_and_fast_kernels_agree).
-int mfma16_mode() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VX_MFMA16");
-        v = (!e || e[0] == '1') ? 15 : (e[0] == 'f' ? 1 : e[0] == 'w' ? 2 : e[0] == 'h' ? 4 : e[0] == 'g' ? 8 : 0);
-    }
-    return v;
-}
-// VX_FWD_RING = 0: the large-batch guide forward pulls its head tiles per wave (the form before the shared LDS ring of
-// k_mvn_fwd_b2.hip; a test seam: tests/test_gpu_parity.py::test_forward_ring_and_plain_forms_agree)
-bool fwd_ring_on() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("VX_FWD_RING");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v != 0;
-}
+// the f16x2 guide forward (k_mvn_fwd_b*.hip) and its fused pack launches (k_pack_fused.hip)
 bool fwb_shape(const vx_irt_cfg* cfg) {
-    return (mfma16_mode() & 1) && packed_ok(cfg) && cfg->D <= 128 && fb_lds_bytes(cfg->D, cfg->J) <= 160 * 1024;
+    return seams().fwd16 && packed_ok(cfg) && cfg->D <= 128 && fb_lds_bytes(cfg->D, cfg->J) <= 160 * 1024;
 }
 
 bool enc_cfg_ok(const vx_irt_cfg* cfg) {
@@ -473,65 +476,154 @@ int vx_adam_step2(float* pA, const float* gA, float* mA, float* vA, const float*
 static bool lik_h_shape(const vx_irt_cfg* cfg) {
     return !force_generic() && cfg->D >= 96 && cfg->D <= 16 * LB_NKS - 1 && cfg->model <= VX_IRT_2PL;
 }
+// bytes of its x image's 64-person tiles: the overflow word stands behind them (vx_irt_lik_ximg_bytes)
+static int64_t lik_ximg_ovf_bytes(int64_t nb) { return (nb + LB_P - 1) / LB_P * (int64_t)LH_XT_BYTES; }
 
-static bool bwhb_shape(const vx_irt_cfg* cfg, int64_t nb);
-static bool bwb_shape(const vx_irt_cfg* cfg, int64_t nb);
-// the f16x2 forward ran its fused pack launches AND the f16x2 hidden-gradient kernel will run in the backward call of the same
-// (cfg, nb): its unit images and the words that collect the step's operand maxima live in packws (k_pack_fused.hip)
-static bool hb_from_forward(const vx_irt_cfg* cfg, int64_t nb) { return fwb_shape(cfg) && bwhb_shape(cfg, nb); }
+// person slices of a grid of `groups` slab groups: as many as fill the chip once (at least one, at most the person tiles)
+static int spread(int64_t n_ptiles, int64_t groups) {
+    int64_t w = num_cu() / groups;
+    if (w < 1) w = 1;
+    return (int)(n_ptiles < 1 ? 1 : (n_ptiles < w ? n_ptiles : w));
+}
 
-// The kernels of the forward; what they leave undone is reported to the entry point below, which finishes it once the
-// kernels have been launched without an error: ximg_done (the likelihood operand image: every forward kernel but
-// k_mvn_enc_fwd_b / _b2 leaves it to a pass over x), hs_done (the fp16 terms of hT, the head weight-gradient kernel's
-// operand: a pass over hT, scaled by *hscale).
-static int mvn_enc_forward_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, int64_t gid0,
-                                   const float* W1, const float* b1, const float* W21, const float* b21, const float* W22,
-                                   const float* b22, const float* eps_in, float* h, float* x, float* eps, float* ldT,
-                                   float* ent, float* hT, float* epsT, float* packws, uint8_t* ximg, uint16_t* hs_out, void* hs,
-                                   bool& ximg_done, bool& hs_done, const float*& hscale, const int64_t*& ring) {
+// The pack buffer of the guide (vx_mvn_pack_floats), float offsets:
+//   Wp | bp | gtab | WpT | f16x2 tile images of the heads (gt2: their OFF group table) | f16x2 k-step images of fc1 | f16x2
+//   unit images of the hidden gradient | the operands' powers of two (sc; hscale: hT's, maxw: the words that collect the
+//   step's operand maxima)
+struct PackLayout { int64_t Rp, bp, gtab, wpT, img, gt2, w1img, himg, sc, hscale, maxw, total; };
+static PackLayout pack_layout(const vx_irt_cfg* cfg) {
+    static_assert(FB_IMG_BYTES % 4 == 0, "the tile images fill whole floats");
+    PackLayout l;
+    l.Rp = pk_rows(cfg->D);
+    l.bp = l.Rp * 64;                      // (Wp at 0)
+    l.gtab = l.bp + l.Rp;
+    l.wpT = l.gtab + l.Rp / 8 + 8;
+    l.img = l.wpT + l.Rp * 64;
+    l.gt2 = l.img + (int64_t)fb_tiles(cfg->D) * (FB_IMG_BYTES / 4);
+    l.w1img = l.img + fb_img_floats(cfg->D);
+    l.himg = l.w1img + fb_w1img_floats(cfg->J);
+    l.sc = l.himg + hb_img_floats(cfg->D);
+    l.hscale = l.sc + 3;
+    l.maxw = l.sc + 11;
+    l.total = l.sc + FB_NSCALES;
+    return l;
+}
+
+// The plan of the guide's forward and backward calls for (cfg, nb): the kernels the shape allows, the grids and the layout of
+// the backward's workspace (vx_mvn_enc_bwd_workspace_floats).  Which kernels a call launches also depends on its pointers
+// (alignment, the optional buffers it passes, the gd_ready bits); the layout depends on (cfg, nb) and the seams alone, as the
+// size and offset queries do.  Workspace, float offsets:
+//   ghpre [nb][H] | weight-gradient slabs [n_prw_ws][lenw] | fc1 slabs [n_prf][lenf] | gdT [D][nb] + 4 | hs: two fp16 copies of
+//   hT [nb][64] | unit images of the hidden gradient | the step's operand maxima [8]
+// gdT exists with the dimension-major kernels (bwt), hs with the bf16 head weight gradient (bwb), the unit images with the
+// f16x2 hidden gradient (bwhb); the offsets of absent regions are -1.
+struct MvnPlan {
+    bool packed;                 // the packed head layout (k_pack.hip)
+    bool fwb;                    // the f16x2 forward (k_mvn_fwd_b*.hip) and its fused pack launches
+    bool encb_fast;              // the person-major backward's fast kernels (k_mvn_enc_bwd_fast.hip)
+    bool bwt;                    // the dimension-major weight gradient (k_mvn_bwd_t.hip)
+    bool bwh_t;                  // ... and hidden gradient: vx_mvn_enc_bwd_layout == 1, the backward reads gxT only
+    bool bwb;                    // the head weight gradient on the bf16 MFMA (k_mvn_bwd_b.hip)
+    bool bwhb;                   // the hidden gradient on the f16x2 MFMA (k_mvn_bwd_hb*.hip)
+    bool hb_fw;                  // fwb && bwhb: the unit images and the operand maxima in packws (k_pack_fused.hip)
+    bool fc1_16, side_streams;   // the seams (Seams)
+    int n_rowslabs, n_prw;       // the person-major weight gradient's grid
+    int n_rowslabs_t, n_prw_t;   // the dimension-major weight gradient's grid
+    int n_jg, n_prf;             // the fc1 gradient's grid
+    int n_prw_ws;                // weight-gradient slabs in the workspace: either of the two grids fits
+    int64_t lenw_ref, lenw, lenf;
+    int64_t slabs_w, slabs_f, gd = -1, hs = -1, himg = -1, maxw, total;
+};
+static MvnPlan mvn_plan(const vx_irt_cfg* cfg, int64_t nb) {
+    const Seams& sm = seams();
+    const int64_t D = cfg->D, J = cfg->J, H = cfg->H, T = tril_len(cfg->D), Rp = pk_rows(cfg->D);
+    MvnPlan p;
+    p.packed = packed_ok(cfg);
+    p.fwb = fwb_shape(cfg);
+    p.encb_fast = !sm.generic && H == 64 && D % 4 == 0 && enc_bwdw_fast_lds_floats(cfg->D) * sizeof(float) <= 160 * 1024;
+    p.bwt = p.packed && nb % 4 == 0 && D <= 124 && bt_lds_bytes(cfg->D) <= 160 * 1024;
+    p.bwh_t = p.bwt && nb >= 4 && bh_lds_bytes(cfg->D) <= 160 * 1024;
+    p.bwb = sm.w16 && p.bwt && nb % 8 == 0 && nb < ((int64_t)1 << 23) && bb_lds_bytes(cfg->D) <= 160 * 1024;
+    p.bwhb = sm.h16 && p.bwt && nb >= 4 && D <= 16 * HB_NS && hb_lds_bytes(cfg->D) <= 160 * 1024;
+    p.hb_fw = p.fwb && p.bwhb;
+    p.fc1_16 = sm.fc1_16;
+    p.side_streams = sm.side_streams;
+    const int rows_per_wg = p.encb_fast ? BWF_ROWS : BW_ROWS;
+    p.n_rowslabs = (int)(((p.packed ? Rp : T + D) + rows_per_wg - 1) / rows_per_wg);
+    p.n_jg = (int)((J + FC1_JG - 1) / FC1_JG);
+    const int64_t n_ptiles = (nb + ENC_P - 1) / ENC_P;
+    p.n_prw = spread(n_ptiles, p.n_rowslabs);
+    p.n_prf = spread(n_ptiles, p.n_jg);
+    p.n_rowslabs_t = (int)((Rp + BT_ROWS - 1) / BT_ROWS);
+    p.n_prw_t = spread((nb + BT_P - 1) / BT_P, p.n_rowslabs_t);
+    p.n_prw_ws = (p.bwt && p.n_prw_t > p.n_prw) ? p.n_prw_t : p.n_prw;
+    p.lenw_ref = D * H + D + T * H + T;
+    p.lenw = (p.packed && Rp * (H + 1) > p.lenw_ref) ? Rp * (H + 1) : p.lenw_ref;
+    p.lenf = H * J + H;
+    p.slabs_w = nb * H;
+    p.slabs_f = p.slabs_w + p.n_prw_ws * p.lenw;
+    int64_t end = p.slabs_f + p.n_prf * p.lenf;
+    if (p.bwt) { p.gd = end; end += nb * D + 4; }
+    if (p.bwb) { p.hs = end; end += nb * 64; }
+    if (p.bwhb) { p.himg = end; end += hb_img_floats(cfg->D); }
+    p.maxw = end;
+    p.total = end + 8;
+    return p;
+}
+
+// fc1's weight gradient from person-major operands with 16-byte loads (k_fc1_bwd)
+static int f1fast_ok(const vx_irt_cfg* cfg, const float* ghpre, const uint8_t* y) {
+    return (!force_generic() && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(ghpre) && aligned16(y)) ? 1 : 0;
+}
+
+// The kernels of the forward (packed: the entry point below found the packed path usable).  The packed path on the f16x2
+// kernels (p.fwb) writes the likelihood's x image and the fp16 terms of hT itself; the entry point makes them behind the
+// other paths.  ring: the step's row indices, left in the pinned host ring for that path only.
+static int mvn_enc_forward_kernels(const vx_irt_cfg* cfg, const MvnPlan& p, bool packed, const uint8_t* y, const int64_t* rows,
+                                   int64_t nb, int64_t gid0, const float* W1, const float* b1, const float* W21, const float* b21,
+                                   const float* W22, const float* b22, const float* eps_in, float* h, float* x, float* eps,
+                                   float* ldT, float* ent, float* hT, float* epsT, float* packws, uint8_t* ximg, uint16_t* hs_out,
+                                   void* hs, const int64_t* ring) {
     EncDims dm = make_enc_dims(cfg, nb);
     const dim3 grid((unsigned)((nb + ENC_P - 1) / ENC_P));
     int rc;
-    if (packed_ok(cfg) && packws && aligned16(packws) && aligned16(y) && aligned16(W1) && aligned16(b1) &&
-        aligned16(W21) && aligned16(W22) && aligned16(h)) {
-        const int Rp = pk_rows(cfg->D);
+    if (packed) {
+        const PackLayout pk = pack_layout(cfg);
         float* Wp = packws;
-        float* bp = Wp + (int64_t)Rp * 64;
-        uint32_t* gtab = (uint32_t*)(bp + Rp);
-        float* WpT = (float*)(gtab + Rp / 8 + 8);
+        float* bp = packws + pk.bp;
+        uint32_t* gtab = (uint32_t*)(packws + pk.gtab);
+        float* WpT = packws + pk.wpT;
         // the powers of two of the f16x2 operands (the backward kernels read them too: pack_scales below)
-        float* sc = packws + vx_mvn_pack_floats(cfg) - FB_NSCALES;
-        hscale = sc + 3;
-        if (!fwb_shape(cfg)) {
-            hipLaunchKernelGGL(k_pack_heads, dim3(Rp), dim3(64), 0, (hipStream_t)hs, (int)cfg->D, 64, W21, b21, W22, b22, Wp,
-                               bp, gtab, WpT);
+        float* sc = packws + pk.sc;
+        if (!p.fwb) {
+            hipLaunchKernelGGL(k_pack_heads, dim3((unsigned)pk.Rp), dim3(64), 0, (hipStream_t)hs, (int)cfg->D, 64, W21, b21, W22, b22,
+                               Wp, bp, gtab, WpT);
             VX_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(64), 0, (hipStream_t)hs, (uint32_t*)(sc + 11), 4);
+            hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(64), 0, (hipStream_t)hs, (uint32_t*)(packws + pk.maxw), 4);
             hipLaunchKernelGGL(k_enc_scales_max, dim3(FB_SC_BLOCKS), dim3(256), 0, (hipStream_t)hs, (int)dm.D, (int)dm.J, W1, b1, W21,
                                b21, W22, b22, sc);
             hipLaunchKernelGGL(k_enc_scales, dim3(1), dim3(64), 0, (hipStream_t)hs, sc);
             VX_CHECK_LAUNCH();
         }
-        if (fwb_shape(cfg)) {
-            uint8_t* img = (uint8_t*)(WpT + (int64_t)Rp * 64);
+        if (p.fwb) {
+            uint8_t* img = (uint8_t*)(packws + pk.img);
             const int n_tiles = fb_tiles(dm.D);
-            uint32_t* gt2 = (uint32_t*)(img + (int64_t)n_tiles * FB_IMG_BYTES);
-            uint8_t* w1img = img + fb_img_floats(dm.D) * 4;
+            uint32_t* gt2 = (uint32_t*)(packws + pk.gt2);
+            uint8_t* w1img = (uint8_t*)(packws + pk.w1img);
             // every weight image of the step in two launches (k_pack_fused.hip).  The unit images of the hidden gradient are
-            // made here too when that kernel will run (hb_from_forward: the backward call then reads them from packws), and
+            // made here too when that kernel will run (p.hb_fw: the backward call then reads them from packws), and
             // WpT only when a kernel of this step reads it (the fp32 hidden-gradient kernel)
-            const bool hb = hb_from_forward(cfg, nb);
-            uint8_t* himg = hb ? (uint8_t*)((float*)sc - hb_img_floats(dm.D)) : nullptr;
+            const bool hb = p.hb_fw;
+            uint8_t* himg = hb ? (uint8_t*)(packws + pk.himg) : nullptr;
             // with the f16x2 hidden gradient (hb) no kernel of the step reads the packed copy Wp / bp / WpT: stage 1 is the maxima
             // alone and stage 2 takes the tile images from the parameters themselves (and writes gtab, which the head weight
             // gradient reads)
             const bool direct = hb;
-            const int n_row_blocks = direct ? 0 : (Rp + 3) / 4, n_w1 = (dm.J + 15) / 16;
+            const int n_row_blocks = direct ? 0 : (int)((pk.Rp + 3) / 4), n_w1 = (dm.J + 15) / 16;
             hipLaunchKernelGGL(k_pack_stage1, dim3(n_row_blocks + FB_SC_BLOCKS + (ring ? 1 : 0)), dim3(256), 0, (hipStream_t)hs,
                                (int)dm.D, (int)dm.J, W1, b1, W21, b21, W22, b22, Wp, bp, gtab, hb ? (float*)nullptr : WpT, sc, ring,
                                (int64_t)cfg->rows_ring_stride, (int)cfg->rows_ring_slots, cfg->step_dev, const_cast<int64_t*>(rows),
                                nb, n_row_blocks);
-            ring = nullptr;                                // (done)
             VX_CHECK_LAUNCH();
             hipLaunchKernelGGL(k_pack_stage2, dim3(n_w1 + n_tiles + (hb ? hb_units(dm.D) : 0)), dim3(256), 0, (hipStream_t)hs,
                                (int)dm.D, (int)dm.J, n_tiles, pk_off_total(dm.D) / 8, W1, W21, W22, (const float*)Wp, (const float*)bp,
@@ -539,8 +631,6 @@ static int mvn_enc_forward_kernels(const vx_irt_cfg* cfg, const uint8_t* y, cons
                                direct ? b22 : (const float*)nullptr, direct ? gtab : (uint32_t*)nullptr);
             VX_CHECK_LAUNCH();
             const size_t ldsb = fb_lds_bytes(dm.D, dm.J);
-            ximg_done = true;
-            hs_done = true;
             if (nb <= FB_SPLIT_MAX) {
                 // small batch: one 32-person tile per workgroup, its four waves share the head tiles
                 ProfScope ps("k_mvn_enc_fwd_b", (hipStream_t)hs);
@@ -582,15 +672,15 @@ static int mvn_enc_forward_kernels(const vx_irt_cfg* cfg, const uint8_t* y, cons
                 VX_CHECK_LAUNCH();
                 return VX_OK;
             };
-            if (n_done > 0 && n_done < nb && (mfma16_mode() & 8) && tail_fork.fork(side_stream(0, (hipStream_t)hs), (hipStream_t)hs)) {
+            if (n_done > 0 && n_done < nb && p.side_streams && tail_fork.fork(side_stream(0, (hipStream_t)hs), (hipStream_t)hs)) {
                 rc = launch_tail(tail_fork.side());
                 if (rc) return rc;                                  // (the scope joins)
             }
             if (n_done > 0) {
                 // the head tiles through the workgroup's LDS ring where the shape allows it: a quarter of the L2 -> CU bytes
-                const bool ring = fwd_ring_on() && fb2s_shape_ok((int)dm.D, (int)dm.J);
-                const size_t lds2 = ring ? fb2s_lds_bytes((int)dm.D) : fb2_lds_bytes(dm.D, dm.J, FNS);
-                rc = ring ? set_lds(k_mvn_enc_fwd_b2<FNS, true>, lds2) : set_lds(k_mvn_enc_fwd_b2<FNS, false>, lds2);
+                const bool tile_ring = seams().fwd_ring && fb2s_shape_ok((int)dm.D, (int)dm.J);
+                const size_t lds2 = tile_ring ? fb2s_lds_bytes((int)dm.D) : fb2_lds_bytes(dm.D, dm.J, FNS);
+                rc = tile_ring ? set_lds(k_mvn_enc_fwd_b2<FNS, true>, lds2) : set_lds(k_mvn_enc_fwd_b2<FNS, false>, lds2);
                 if (rc) return rc;
                 ProfScope ps("k_mvn_enc_fwd_b2", (hipStream_t)hs, n_done);
                 const int wg = FB2_WAVES * 32 * FNS;
@@ -599,7 +689,7 @@ static int mvn_enc_forward_kernels(const vx_irt_cfg* cfg, const uint8_t* y, cons
     hipLaunchKernelGGL((k_mvn_enc_fwd_b2<FNS, SH>), grid2, dim3(FB2_THREADS), lds2, (hipStream_t)hs, dm, y, rows, gid0,          \
                        (const uint8_t*)w1img, b1, (const uint8_t*)img, (const uint32_t*)gt2, (const float*)sc, eps_in, cfg->seed, \
                        cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent, hT, epsT, ximg, hs_out)
-                if (ring) { LAUNCH_FWD_B2(true); } else { LAUNCH_FWD_B2(false); }
+                if (tile_ring) { LAUNCH_FWD_B2(true); } else { LAUNCH_FWD_B2(false); }
 #undef LAUNCH_FWD_B2
                 VX_CHECK_LAUNCH();
                 if (n_done == nb) return VX_OK;
@@ -652,13 +742,15 @@ int vx_mvn_enc_forward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* r
     if (nb == 0) return VX_OK;
     if (ximg && !(lik_h_shape(cfg) && aligned16(ximg))) return VX_EINVAL;     // vx_irt_lik_ximg_bytes(cfg, nb) == 0: no image
     if (hs_out && (!hT || cfg->H != 64)) return VX_EINVAL;
-    // hs and the powers of two behind it exist on the packed path only (checked BEFORE anything is launched)
-    if (hs_out && !(packed_ok(cfg) && packws && aligned16(packws) && aligned16(y) && aligned16(W1) && aligned16(b1) &&
-                    aligned16(W21) && aligned16(W22) && aligned16(h)))
-        return VX_EINVAL;
-    bool ximg_done = false, hs_done = false;
-    const float* hscale = nullptr;
-    uint32_t* ovf = ximg ? (uint32_t*)(ximg + (nb + LB_P - 1) / LB_P * (int64_t)LH_XT_BYTES) : nullptr;   // k_irt_lik_h.hip
+    const MvnPlan p = mvn_plan(cfg, nb);
+    // the packed path: the shape allows it and the buffers it reads 16 bytes at a time are aligned
+    const bool packed = p.packed && packws && aligned16(packws) && aligned16(y) && aligned16(W1) && aligned16(b1) &&
+                        aligned16(W21) && aligned16(W22) && aligned16(h);
+    // the caller will hand hs to vx_mvn_enc_backward (gd_ready bit 1), which reads it and the powers of two in packws
+    // unconditionally: they exist on the packed path only (checked BEFORE anything is launched)
+    if (hs_out && !packed) return VX_EINVAL;
+    const bool fused = packed && p.fwb;                            // the f16x2 kernels write the x image and hs themselves
+    uint32_t* ovf = ximg ? (uint32_t*)(ximg + lik_ximg_ovf_bytes(nb)) : nullptr;   // k_irt_lik_h.hip
     if (ovf && hipMemsetAsync(ovf, 0, sizeof(uint32_t), (hipStream_t)hs) != hipSuccess) return VX_EINVAL;
     // the step's row indices from the pinned host ring (vx_irt_cfg.rows_ring): inside the first launch of the fused pack, or
     // as a launch of its own in front of every other forward path
@@ -668,84 +760,90 @@ int vx_mvn_enc_forward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* r
         void* dp = nullptr;
         if (hipHostGetDevicePointer(&dp, const_cast<int64_t*>(cfg->rows_ring), 0) != hipSuccess || !dp) return VX_EINVAL;
         ring = (const int64_t*)dp;
-        if (!fwb_shape(cfg) || !(packed_ok(cfg) && packws && aligned16(packws) && aligned16(y) && aligned16(W1) && aligned16(b1) &&
-                                 aligned16(W21) && aligned16(W22) && aligned16(h))) {
+        if (!fused) {
             hipLaunchKernelGGL(k_rows_from_ring, dim3(1), dim3(256), 0, (hipStream_t)hs, ring, (int64_t)cfg->rows_ring_stride,
                                (int)cfg->rows_ring_slots, cfg->step_dev, const_cast<int64_t*>(rows), nb);
             VX_CHECK_LAUNCH();
             ring = nullptr;
         }
     }
-    const int rc = mvn_enc_forward_kernels(cfg, y, rows, nb, gid0, W1, b1, W21, b21, W22, b22, eps_in, h, x, eps, ldT, ent, hT,
-                                           epsT, packws, ximg, hs_out, hs, ximg_done, hs_done, hscale, ring);
-    if (!rc && ring) return VX_EINVAL;                                // (a ring nobody read: cannot happen -- the test above mirrors the path)
+    const int rc = mvn_enc_forward_kernels(cfg, p, packed, y, rows, nb, gid0, W1, b1, W21, b21, W22, b22, eps_in, h, x, eps, ldT,
+                                           ent, hT, epsT, packws, ximg, hs_out, hs, ring);
     if (rc) return rc;                                               // nothing is launched on buffers an error left unwritten
-    if (ximg && !ximg_done) {
+    if (ximg && !fused) {
         hipLaunchKernelGGL(k_lik_ximg_h, dim3((unsigned)((nb + LB_P - 1) / LB_P)), dim3(256), 0, (hipStream_t)hs, (int)cfg->D, nb,
                            (const float*)x, ximg, ovf);
         VX_CHECK_LAUNCH();
     }
-    if (hs_out && !hs_done) {
-        // the caller will hand hs to vx_mvn_enc_backward (gd_ready bit 1), which reads it and the powers of two in packws
-        // unconditionally: a path that wrote neither (no packed layout: unaligned weights, H != 64 ...) must not return VX_OK
-        if (!hscale) return VX_EINVAL;
-        hipLaunchKernelGGL(k_split2_f16, dim3(num_cu() * 8), dim3(256), 0, (hipStream_t)hs, (const float*)hT, nb * 64, hscale, hs_out);
+    if (hs_out && !fused) {
+        hipLaunchKernelGGL(k_split2_f16, dim3(num_cu() * 8), dim3(256), 0, (hipStream_t)hs, (const float*)hT, nb * 64,
+                           (const float*)(packws + pack_layout(cfg).hscale), hs_out);
         VX_CHECK_LAUNCH();
     }
     return VX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-static void lik_plan(const vx_irt_cfg* cfg, int64_t nb, int& kt, int& nch, int& groups, int& n_pr) {
+// person slices of the likelihood's specialised kernels: spread(), in whole XCD rounds (see their block decode)
+static int xcd_spread(int64_t n_ptiles, int64_t groups) {
+    const int n = spread(n_ptiles, groups);
+    return n >= 8 ? n & ~7 : n;
+}
+
+// The plan of vx_irt_lik_grad for (cfg, nb) and the layout of its workspace (vx_irt_lik_workspace_floats), float offsets.
+//   The register-resident (r) and the generic kernel: slabs [n_pr][slab_len] | with several item groups, gx partials
+//   [groups][nb][D] | ll partials [groups][nb]; the generic kernel then a person-major gx (gx_tmp) when only gxT is asked for.
+//   The bf16x3 / f16x2 kernels (b: a full batch whose item-major responses came): slabs [b_n_pr][slab_len] | x image of
+//   n_ptiles 64-person tiles | gx partials [b_groups][LB_DP][nbp] | ll partials [b_groups][nbp] | overflow word.
+// The workspace holds whichever of the two the call takes.
+struct LikPlan {
+    bool h;                      // the f16x2 kernel (k_irt_lik_h.hip) and its x image: 1PL / 2PL, D + 1 in (96, 112]
+    bool b;                      // the bf16x3 path (k_irt_lik_b.hip): D + 1 in (96, 112]
+    bool r;                      // the register-resident kernel (k_irt_lik_r.hip): D + 1 in (64, 128]
+    int kt, nch;                 // the generic kernel's template arguments (k_irt_lik.hip)
+    int groups, n_pr;            // item groups x person slices of the r or the generic kernel
+    int64_t slab_len, gx_part, ll_part, gx_tmp;
+    int b_groups = 0, b_n_pr = 0;
+    int64_t n_ptiles, nbp;       // the b path's 64-person tiles
+    int64_t b_ximg = -1, b_gx_part = -1, b_ll_part = -1, b_ovf = -1;
+    int64_t total;
+    int64_t ximg_bytes;          // the forward's f16x2 x image (h): tile images | overflow word (vx_irt_lik_ximg_bytes)
+};
+static LikPlan lik_plan(const vx_irt_cfg* cfg, int64_t nb) {
+    static_assert(LB_XT_BYTES % 4 == 0, "the x image's tiles fill whole floats");
+    LikPlan p;
+    p.h = lik_h_shape(cfg);
+    p.ximg_bytes = p.h ? lik_ximg_ovf_bytes(nb) + LH_FLAG_BYTES : 0;
+    p.b = !force_generic() && cfg->D >= 96 && cfg->D <= 16 * LB_NKS - 1;
+    p.r = !force_generic() && cfg->D >= 64 && cfg->D <= 127;
+    p.slab_len = (int64_t)cfg->D * cfg->J + 3 * (int64_t)cfg->J;
     const int dk = cfg->D + 1;
-    kt = dk <= 32 ? 1 : (dk <= 64 ? 2 : 4);
-    nch = cfg->J <= LIK_JC ? 1 : 2;      // 4 chunks of register-resident GA tiles spill; 2 do not
-    groups = (cfg->J + nch * LIK_JC - 1) / (nch * LIK_JC);
-    const int64_t n_ptiles = (nb + LIK_P - 1) / LIK_P;
-    int64_t want = num_cu() / groups;
-    if (want < 1) want = 1;
-    n_pr = (int)(n_ptiles < want ? n_ptiles : want);
-    if (n_pr < 1) n_pr = 1;
-}
-
-// register-resident variant (k_irt_lik_r.hip): one 128-item chunk per workgroup, D + 1 in (64, 128]
-static bool lik_r_shape(const vx_irt_cfg* cfg) {
-    return !force_generic() && cfg->D >= 64 && cfg->D <= 127;
-}
-static void lik_r_plan(const vx_irt_cfg* cfg, int64_t nb, int& groups, int& n_pr) {
-    groups = (cfg->J + LR_JC - 1) / LR_JC;
-    const int64_t n_ptiles = (nb + LR_P - 1) / LR_P;
-    int64_t want = num_cu() / groups;
-    if (want < 1) want = 1;
-    if (want > n_ptiles) want = n_ptiles;
-    if (want >= 8) want &= ~7LL;                          // whole XCD rounds (see the kernel's block decode)
-    n_pr = (int)(want < 1 ? 1 : want);
-}
-
-// bf16x3 variant (k_irt_lik_b.hip): D + 1 in (96, 112], full batch, item-major responses supplied
-static bool lik_b_shape(const vx_irt_cfg* cfg) { return !force_generic() && cfg->D >= 96 && cfg->D <= 16 * LB_NKS - 1; }
-static bool lik_b_ok(const vx_irt_cfg* cfg, const int64_t* rows, int64_t nb, const uint8_t* yT, int64_t yT_stride,
-                     const float* gxT) {
-    const int64_t nbp = (nb + LB_P - 1) / LB_P * LB_P;
-    return lik_b_shape(cfg) && !rows && yT && gxT && yT_stride % 64 == 0 && yT_stride >= nbp && aligned16(yT) && nb > 0;
-}
-static void lik_b_plan(const vx_irt_cfg* cfg, int64_t nb, int& groups, int& n_pr) {
-    groups = (cfg->J + LB_JC - 1) / LB_JC;
-    const int64_t n_ptiles = (nb + LB_P - 1) / LB_P;
-    int64_t want = num_cu() / groups;
-    if (want < 1) want = 1;
-    if (want > n_ptiles) want = n_ptiles;
-    if (want >= 8) want &= ~7LL;                          // whole XCD rounds (see the kernel's block decode)
-    n_pr = (int)(want < 1 ? 1 : want);
-}
-// workspace of the bf16x3 path, in floats: slabs | x image | gx partials | ll partials
-static int64_t lik_b_ws_floats(const vx_irt_cfg* cfg, int64_t nb) {
-    int groups, n_pr;
-    lik_b_plan(cfg, nb, groups, n_pr);
-    const int64_t n_ptiles = (nb + LB_P - 1) / LB_P, nbp = n_ptiles * LB_P;
-    const int64_t slab_len = (int64_t)cfg->D * cfg->J + 3 * (int64_t)cfg->J;
-    return (((int64_t)n_pr * slab_len + 3) & ~(int64_t)3) + n_ptiles * (LB_XT_BYTES / 4) + (int64_t)groups * LB_DP * nbp +
-           (int64_t)groups * nbp + 16;                    // + the overflow word of an x image made here
+    p.kt = dk <= 32 ? 1 : (dk <= 64 ? 2 : 4);
+    p.nch = cfg->J <= LIK_JC ? 1 : 2;      // 4 chunks of register-resident GA tiles spill; 2 do not
+    if (p.r) {                             // one 128-item chunk per workgroup
+        p.groups = (cfg->J + LR_JC - 1) / LR_JC;
+        p.n_pr = xcd_spread((nb + LR_P - 1) / LR_P, p.groups);
+    } else {
+        p.groups = (cfg->J + p.nch * LIK_JC - 1) / (p.nch * LIK_JC);
+        p.n_pr = spread((nb + LIK_P - 1) / LIK_P, p.groups);
+    }
+    p.gx_part = (int64_t)p.n_pr * p.slab_len;
+    p.ll_part = p.gx_part + (int64_t)p.groups * nb * cfg->D;
+    const int64_t used = p.gx_part + (p.groups > 1 ? (int64_t)p.groups * nb * (cfg->D + 1) : 0);
+    p.gx_tmp = p.r ? -1 : ((used + 3) & ~(int64_t)3);
+    p.total = p.r ? used : used + nb * cfg->D + 4;
+    p.n_ptiles = (nb + LB_P - 1) / LB_P;
+    p.nbp = p.n_ptiles * LB_P;
+    if (p.b) {
+        p.b_groups = (cfg->J + LB_JC - 1) / LB_JC;
+        p.b_n_pr = xcd_spread(p.n_ptiles, p.b_groups);
+        p.b_ximg = ((int64_t)p.b_n_pr * p.slab_len + 3) & ~(int64_t)3;
+        p.b_gx_part = p.b_ximg + p.n_ptiles * (LB_XT_BYTES / 4);
+        p.b_ll_part = p.b_gx_part + (int64_t)p.b_groups * LB_DP * p.nbp;
+        p.b_ovf = p.b_ll_part + (int64_t)p.b_groups * p.nbp;                   // of an x image made here
+        if (p.b_ovf + 16 > p.total) p.total = p.b_ovf + 16;
+    }
+    return p;
 }
 
 static bool lik_cfg_ok(const vx_irt_cfg* cfg) {
@@ -755,23 +853,12 @@ static bool lik_cfg_ok(const vx_irt_cfg* cfg) {
 
 int64_t vx_irt_lik_ximg_bytes(const vx_irt_cfg* cfg, int64_t nb) {
     if (!lik_cfg_ok(cfg) || nb < 0) return VX_EINVAL;
-    return lik_h_shape(cfg) ? ((nb + LB_P - 1) / LB_P) * (int64_t)LH_XT_BYTES + LH_FLAG_BYTES : 0;   // tile images | overflow word
+    return lik_plan(cfg, nb).ximg_bytes;
 }
 
 int64_t vx_irt_lik_workspace_floats(const vx_irt_cfg* cfg, int64_t nb) {
     if (!lik_cfg_ok(cfg) || nb < 0) return VX_EINVAL;
-    int kt, nch, groups, n_pr;
-    lik_plan(cfg, nb, kt, nch, groups, n_pr);
-    if (lik_r_shape(cfg)) lik_r_plan(cfg, nb, groups, n_pr);
-    const int64_t slab_len = (int64_t)cfg->D * cfg->J + 3 * (int64_t)cfg->J;
-    int64_t w = (int64_t)n_pr * slab_len;
-    if (groups > 1) w += (int64_t)groups * nb * (cfg->D + 1);
-    if (!lik_r_shape(cfg)) w += nb * cfg->D + 4;          // person-major gx when only gxT is asked for
-    if (lik_b_shape(cfg)) {                               // whichever of the two D >= 64 paths the call takes
-        const int64_t wb = lik_b_ws_floats(cfg, nb);
-        if (wb > w) w = wb;
-    }
-    return w;
+    return lik_plan(cfg, nb).total;
 }
 
 // The kernels of vx_irt_lik_grad (arguments validated by the entry point below); gd_done: the path wrote gdT itself.
@@ -780,25 +867,26 @@ static int irt_lik_grad_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const i
                                 float* ll, float* gitem, float* workspace, const uint8_t* yT, int64_t yT_stride,
                                 const uint8_t* ximg_in, const float* epsT, const float* ldT, float* gdT, uint32_t* opmax, void* hs,
                                 bool& gd_done) {
-    if (lik_b_ok(cfg, rows, nb, yT, yT_stride, gxT) && aligned16(workspace) && aligned16(gxT)) {
-        int groups, n_pr;
-        lik_b_plan(cfg, nb, groups, n_pr);
-        const int64_t n_ptiles = (nb + LB_P - 1) / LB_P, nbp = n_ptiles * LB_P;
+    const LikPlan p = lik_plan(cfg, nb);
+    const int64_t n_ptiles = p.n_ptiles, nbp = p.nbp;
+    if (p.b && !rows && yT && gxT && yT_stride % 64 == 0 && yT_stride >= nbp && aligned16(yT) && nb > 0 && aligned16(workspace) &&
+        aligned16(gxT)) {
+        const int groups = p.b_groups, n_pr = p.b_n_pr;
         LikBDims dm;
         dm.D = cfg->D; dm.J = cfg->J; dm.model = cfg->model; dm.groups = groups; dm.n_pr = n_pr; dm.gxt = 1;
         dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
-        dm.slab_len = (int64_t)cfg->D * cfg->J + 3 * (int64_t)cfg->J;
+        dm.slab_len = p.slab_len;
         float* slabs = workspace;
-        uint8_t* ximg_ws = (uint8_t*)(workspace + (((int64_t)n_pr * dm.slab_len + 3) & ~(int64_t)3));
-        float* gx_part = (float*)(ximg_ws + n_ptiles * LB_XT_BYTES);
+        uint8_t* ximg_ws = (uint8_t*)(workspace + p.b_ximg);
+        float* gx_part = workspace + p.b_gx_part;
         // 1PL / 2PL link: the f16x2 kernel and its image (the forward's, or made here); its gx stores address 16 nbp bytes
         // with 32 bits.  3PL / 4PL: the bf16x3 kernel on its own three-term image (the forward writes none for them).
-        const bool f16 = lik_h_shape(cfg) && nbp < ((int64_t)1 << 27);
+        const bool f16 = p.h && nbp < ((int64_t)1 << 27);
         const uint8_t* ximg = (f16 && ximg_in && aligned16(ximg_in)) ? ximg_in : ximg_ws;
-        float* ll_part = gx_part + (int64_t)groups * LB_DP * nbp;
+        float* ll_part = workspace + p.b_ll_part;
         // the overflow word of the f16 image: behind the forward's image, or -- an image made here -- at the end of the workspace
-        uint32_t* ovf = (ximg == ximg_ws) ? (uint32_t*)(ll_part + (int64_t)groups * nbp)
-                                          : (uint32_t*)(const_cast<uint8_t*>(ximg_in) + n_ptiles * (int64_t)LH_XT_BYTES);
+        uint32_t* ovf = (ximg == ximg_ws) ? (uint32_t*)(workspace + p.b_ovf)
+                                          : (uint32_t*)(const_cast<uint8_t*>(ximg_in) + lik_ximg_ovf_bytes(nb));
         hipStream_t st = (hipStream_t)hs;
         hipError_t he = hipMemsetAsync(slabs, 0, sizeof(float) * (size_t)n_pr * dm.slab_len, st);
         if (he != hipSuccess) return (int)he;
@@ -853,21 +941,20 @@ static int irt_lik_grad_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const i
         }
         return vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, gitem, hs);
     }
-    if (lik_r_shape(cfg)) {
-        int groups, n_pr;
-        lik_r_plan(cfg, nb, groups, n_pr);
+    const int groups = p.groups, n_pr = p.n_pr;
+    if (p.r) {
         LikRDims dm;
         dm.D = cfg->D; dm.J = cfg->J; dm.K8 = (cfg->D + 8) & ~7; dm.model = cfg->model;
         { const int nq = dm.K8 >> 3; dm.XS = 8 * (nq <= 13 ? 13 : 16) + 4; }
         dm.groups = groups; dm.n_pr = n_pr; dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
-        dm.slab_len = (int64_t)cfg->D * cfg->J + 3 * (int64_t)cfg->J;
+        dm.slab_len = p.slab_len;
         dm.fast = (cfg->D % 4 == 0 && cfg->J % 4 == 0 && cfg->J >= 8 && aligned16(x) && aligned16(y) &&
                    aligned16(gx) && aligned16(workspace)) ? 1 : 0;
         dm.gxt = gxT ? 1 : 0;                              // partials (and their sum) dimension-major
         float* slabs = workspace;
         float* gx_sum = gxT ? gxT : gx;
-        float* gx_part = groups > 1 ? workspace + (int64_t)n_pr * dm.slab_len : gx_sum;
-        float* ll_part = groups > 1 ? gx_part + (int64_t)groups * nb * cfg->D : ll;
+        float* gx_part = groups > 1 ? workspace + p.gx_part : gx_sum;
+        float* ll_part = groups > 1 ? workspace + p.ll_part : ll;
         hipStream_t st = (hipStream_t)hs;
         // several item chunks and dimension-major partials: ONE finishing launch sums the partials, makes the DIAG-row operand
         // and reduces the item slabs (k_lik_finish); otherwise the slabs are cleared and reduced as before
@@ -926,29 +1013,19 @@ static int irt_lik_grad_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const i
         }
         return vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, gitem, hs);
     }
-    float* gx_tmp = nullptr;                               // person-major result of the kernels below
-    {
-        int kt0, nch0, groups0, n_pr0;
-        lik_plan(cfg, nb, kt0, nch0, groups0, n_pr0);
-        const int64_t slab_len0 = (int64_t)cfg->D * cfg->J + 3 * (int64_t)cfg->J;
-        int64_t used = (int64_t)n_pr0 * slab_len0;
-        if (groups0 > 1) used += (int64_t)groups0 * nb * (cfg->D + 1);
-        gx_tmp = workspace + ((used + 3) & ~(int64_t)3);
-    }
     float* gxT_req = gxT;
-    if (!gx) gx = gx_tmp;
-    int kt, nch, groups, n_pr;
-    lik_plan(cfg, nb, kt, nch, groups, n_pr);
+    if (!gx) gx = workspace + p.gx_tmp;                    // person-major result of the kernels below
+    const int kt = p.kt, nch = p.nch;
     LikDims dm;
     dm.D = cfg->D; dm.J = cfg->J; dm.DS = lik_ds(cfg->D); dm.Dk2 = (cfg->D + 2) & ~1; dm.model = cfg->model;
     dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
-    dm.slab_len = (int64_t)cfg->D * cfg->J + 3 * (int64_t)cfg->J;
+    dm.slab_len = p.slab_len;
     dm.fast = (!force_generic() && cfg->D % 4 == 0 && cfg->J % 4 == 0 && aligned16(x) && aligned16(a) && aligned16(b) &&
                aligned16(y) && aligned16(gx) && (nb * cfg->D) % 4 == 0) ? 1 : 0;
     const int gen = cfg->model >= VX_IRT_3PL ? 1 : 0;
     float* slabs = workspace;
-    float* gx_part = groups > 1 ? workspace + (int64_t)n_pr * dm.slab_len : gx;
-    float* ll_part = groups > 1 ? gx_part + (int64_t)groups * nb * cfg->D : ll;
+    float* gx_part = groups > 1 ? workspace + p.gx_part : gx;
+    float* ll_part = groups > 1 ? workspace + p.ll_part : ll;
     hipStream_t st = (hipStream_t)hs;
     // slabs are only partially written when a model has no c/d segment: clear them first
     hipError_t he = hipMemsetAsync(slabs, 0, sizeof(float) * (size_t)n_pr * dm.slab_len, st);
@@ -1021,84 +1098,33 @@ int vx_irt_lik_grad(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows
 }
 
 // ------------------------------------------------------------------------------------------------
-static bool encb_fast_shape(const vx_irt_cfg* cfg) {
-    return !force_generic() && cfg->H == 64 && cfg->D % 4 == 0 &&
-           enc_bwdw_fast_lds_floats(cfg->D) * sizeof(float) <= 160 * 1024;
-}
-
-// dimension-major weight-gradient kernel (k_mvn_bwd_t.hip): packed shape, 16-byte aligned person rows
-static bool bwt_shape(const vx_irt_cfg* cfg, int64_t nb) {
-    return packed_ok(cfg) && nb % 4 == 0 && cfg->D <= 124 && bt_lds_bytes(cfg->D) <= 160 * 1024;
-}
-// the default (VX_MFMA16=0 turns it off): the weight-gradient kernel on the bf16 MFMA, operands in bf16 terms (k_mvn_bwd_b.hip)
-static bool bwb_shape(const vx_irt_cfg* cfg, int64_t nb) {
-    const bool on = (mfma16_mode() & 2) != 0;
-    return on && bwt_shape(cfg, nb) && nb % 8 == 0 && nb < ((int64_t)1 << 23) && bb_lds_bytes(cfg->D) <= 160 * 1024;
-}
-static bool bwhb_shape(const vx_irt_cfg* cfg, int64_t nb) {
-    return (mfma16_mode() & 4) && bwt_shape(cfg, nb) && nb >= 4 && cfg->D <= 16 * HB_NS && hb_lds_bytes(cfg->D) <= 160 * 1024;
-}
-static void bwt_plan(const vx_irt_cfg* cfg, int64_t nb, int& n_rowslabs, int& n_prw) {
-    n_rowslabs = (pk_rows(cfg->D) + BT_ROWS - 1) / BT_ROWS;
-    const int64_t n_ptiles = (nb + BT_P - 1) / BT_P;
-    int64_t w = num_cu() / n_rowslabs; if (w < 1) w = 1;
-    n_prw = (int)(n_ptiles < w ? n_ptiles : w); if (n_prw < 1) n_prw = 1;
-}
-
-static void encb_plan(const vx_irt_cfg* cfg, int64_t nb, int& n_rowslabs, int& n_prw, int& n_jg, int& n_prf) {
-    const int64_t RT = packed_ok(cfg) ? (int64_t)pk_rows(cfg->D) : (int64_t)tril_len(cfg->D) + cfg->D;
-    const int rows_per_wg = encb_fast_shape(cfg) ? BWF_ROWS : BW_ROWS;
-    n_rowslabs = (int)((RT + rows_per_wg - 1) / rows_per_wg);
-    n_jg = (cfg->J + FC1_JG - 1) / FC1_JG;
-    const int64_t n_ptiles = (nb + ENC_P - 1) / ENC_P;
-    int64_t w = num_cu() / n_rowslabs; if (w < 1) w = 1;
-    n_prw = (int)(n_ptiles < w ? n_ptiles : w); if (n_prw < 1) n_prw = 1;
-    int64_t f = num_cu() / n_jg; if (f < 1) f = 1;
-    n_prf = (int)(n_ptiles < f ? n_ptiles : f); if (n_prf < 1) n_prf = 1;
-}
-
 int vx_mvn_enc_bwd_layout(const vx_irt_cfg* cfg, int64_t nb) {
     if (!enc_cfg_ok(cfg) || nb < 0) return VX_EINVAL;
-    return (bwt_shape(cfg, nb) && nb >= 4 && bh_lds_bytes(cfg->D) <= 160 * 1024) ? 1 : 0;
+    return mvn_plan(cfg, nb).bwh_t ? 1 : 0;
 }
 
 // float offset, inside the workspace of vx_mvn_enc_backward, of gdT[D][nb] (the DIAG-row operand of the dimension-major
 // kernels); -1 when this (cfg, nb) does not run on them
-static int64_t encb_gd_offset(const vx_irt_cfg* cfg, int64_t nb) {
-    if (!bwt_shape(cfg, nb)) return -1;
-    int ns0, np0, nj0, nf0, ns1, np1;
-    encb_plan(cfg, nb, ns0, np0, nj0, nf0);
-    bwt_plan(cfg, nb, ns1, np1);
-    const int64_t D = cfg->D, J = cfg->J, H = cfg->H, T = tril_len(cfg->D);
-    const int64_t lenw_ref = D * H + D + T * H + T, lenf = H * J + H, Rp = pk_rows(cfg->D);
-    const int64_t lenw = Rp * (H + 1) > lenw_ref ? Rp * (H + 1) : lenw_ref;
-    const int n_prw_ws = np0 > np1 ? np0 : np1;
-    return nb * H + (int64_t)n_prw_ws * lenw + (int64_t)nf0 * lenf;
-}
-
 int64_t vx_mvn_enc_bwd_gd_offset(const vx_irt_cfg* cfg, int64_t nb) {
     if (!enc_cfg_ok(cfg) || nb < 0) return VX_EINVAL;
-    const int64_t o = encb_gd_offset(cfg, nb);
+    const int64_t o = mvn_plan(cfg, nb).gd;
     return (o >= 0 && o % 4 == 0 && (nb * cfg->D) % 4 == 0) ? o : -1;
 }
 
 int64_t vx_mvn_enc_bwd_hs_offset(const vx_irt_cfg* cfg, int64_t nb) {
     if (!enc_cfg_ok(cfg) || nb < 0) return VX_EINVAL;
-    const int64_t o = encb_gd_offset(cfg, nb);
-    return (o >= 0 && bwb_shape(cfg, nb)) ? o + nb * cfg->D + 4 : -1;
+    return mvn_plan(cfg, nb).hs;
 }
 
 int64_t vx_mvn_pack_floats(const vx_irt_cfg* cfg) {
     if (!enc_cfg_ok(cfg)) return VX_EINVAL;
-    const int64_t Rp = pk_rows(cfg->D);
-    // Wp | bp | gtab | WpT | f16x2 tile images of the heads | f16x2 k-step images of fc1 | f16x2 unit images of the hidden
-    // gradient | the operands' powers of two (and the words that collect the step's operand maxima)
-    return Rp * 64 + Rp + Rp / 8 + 8 + Rp * 64 + fb_img_floats(cfg->D) + fb_w1img_floats(cfg->J) + hb_img_floats(cfg->D) + FB_NSCALES;
+    return pack_layout(cfg).total;
 }
 
 int64_t vx_mvn_pack_opmax_offset(const vx_irt_cfg* cfg, int64_t nb) {
     if (!enc_cfg_ok(cfg) || nb < 0) return VX_EINVAL;
-    return (hb_from_forward(cfg, nb) && bwb_shape(cfg, nb)) ? vx_mvn_pack_floats(cfg) - FB_NSCALES + 11 : -1;
+    const MvnPlan p = mvn_plan(cfg, nb);
+    return (p.hb_fw && p.bwb) ? pack_layout(cfg).maxw : -1;
 }
 
 int64_t vx_mvn_enc_param_floats(const vx_irt_cfg* cfg) {
@@ -1109,20 +1135,7 @@ int64_t vx_mvn_enc_param_floats(const vx_irt_cfg* cfg) {
 
 int64_t vx_mvn_enc_bwd_workspace_floats(const vx_irt_cfg* cfg, int64_t nb) {
     if (!enc_cfg_ok(cfg) || nb < 0) return VX_EINVAL;
-    int n_rowslabs, n_prw, n_jg, n_prf;
-    encb_plan(cfg, nb, n_rowslabs, n_prw, n_jg, n_prf);
-    const int64_t D = cfg->D, J = cfg->J, H = cfg->H, T = tril_len(cfg->D);
-    int64_t lenw = D * H + D + T * H + T;
-    if (packed_ok(cfg) && (int64_t)pk_rows(cfg->D) * (H + 1) > lenw) lenw = (int64_t)pk_rows(cfg->D) * (H + 1);
-    if (bwt_shape(cfg, nb)) {                              // whichever of the two weight-gradient kernels runs
-        int ns, np;
-        bwt_plan(cfg, nb, ns, np);
-        if (np > n_prw) n_prw = np;
-    }
-    return nb * H + (int64_t)n_prw * lenw + (int64_t)n_prf * (H * J + H) + (bwt_shape(cfg, nb) ? nb * D + 4 : 0) +
-           (bwb_shape(cfg, nb) ? nb * 64 : 0) +            // two fp16 copies of hT 2^sh
-           (bwhb_shape(cfg, nb) ? hb_img_floats(cfg->D) : 0) +  // unit images of the hidden-gradient kernel
-           8;                                              // the step's operand maxima (k_pack_heads_hb)
+    return mvn_plan(cfg, nb).total;
 }
 
 // the loss of the step, summed by the call's last launch (vx_mvn_enc_backward_loss)
@@ -1135,36 +1148,28 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                         const LossTail* tail) {
     if (!enc_cfg_ok(cfg) || !y || !W21 || !W22 || !h || !eps || !ldT || (!gx && !gxT) || !genc || !workspace || nb < 0)
         return VX_EINVAL;
-    int n_rowslabs, n_prw, n_jg, n_prf;
-    encb_plan(cfg, nb, n_rowslabs, n_prw, n_jg, n_prf);
+    const MvnPlan p = mvn_plan(cfg, nb);
+    const PackLayout pk = pack_layout(cfg);
     EncDims dm = make_enc_dims(cfg, nb);
-    const int64_t D = cfg->D, J = cfg->J, H = cfg->H, T = dm.T;
-    const int64_t lenw_ref = D * H + D + T * H + T, lenf = H * J + H;
-    const int64_t Rp = pk_rows(cfg->D);
-    const bool packed = packed_ok(cfg) && packws && aligned16(packws) && aligned16(h) && aligned16(eps) &&
+    const int64_t D = cfg->D, H = cfg->H, Rp = pk.Rp, lenw = p.lenw, lenf = p.lenf;
+    const bool packed = p.packed && packws && aligned16(packws) && aligned16(h) && aligned16(eps) &&
                         aligned16(gx) && aligned16(workspace) && nb > 0;
-    if (packed_ok(cfg) && !packed && nb > 0) return VX_EINVAL;      // the plan assumed the packed row space
-    const int64_t lenw = (packed_ok(cfg) && Rp * (H + 1) > lenw_ref) ? Rp * (H + 1) : lenw_ref;
-    const bool use_t = packed && hT && epsT && gxT && bwt_shape(cfg, nb) && aligned16(hT) && aligned16(epsT) &&
+    if (p.packed && !packed && nb > 0) return VX_EINVAL;          // the plan assumed the packed row space
+    const bool use_t = packed && hT && epsT && gxT && p.bwt && aligned16(hT) && aligned16(epsT) &&
                        aligned16(gxT) && aligned16(ldT);
-    if (use_t) bwt_plan(cfg, nb, n_rowslabs, n_prw);
-    int n_prw_ws = n_prw;                                  // slab space as sized by vx_mvn_enc_bwd_workspace_floats
-    if (bwt_shape(cfg, nb)) {
-        int ns0, np0, nj0, nf0, ns1, np1;
-        encb_plan(cfg, nb, ns0, np0, nj0, nf0);
-        bwt_plan(cfg, nb, ns1, np1);
-        n_prw_ws = np0 > np1 ? np0 : np1;
-    }
+    int n_rowslabs = use_t ? p.n_rowslabs_t : p.n_rowslabs;
+    const int n_prw = use_t ? p.n_prw_t : p.n_prw, n_jg = p.n_jg, n_prf = p.n_prf;
     float* ghpre = workspace;
+    float* slabs_w = workspace + p.slabs_w;
+    float* slabs_f = workspace + p.slabs_f;
+    float* gdT = p.bwt ? workspace + p.gd : nullptr;      // the DIAG-row operand of the dimension-major kernels
+    uint16_t* hs3 = p.bwb ? (uint16_t*)(workspace + p.hs) : nullptr;   // two fp16 terms of hT 2^sh
     // written by the forward call of this step (k_enc_scales): the powers of two of the f16x2 weight images
-    const float* sc = packws ? packws + vx_mvn_pack_floats(cfg) - FB_NSCALES : nullptr;
+    const float* sc = packws ? packws + pk.sc : nullptr;
     // the step's largest |gx|, |gd|, |eps|, |ghpre| (float bits): words 11 .. 14 of the scale block when the forward call packed
     // for this backward (cleared there), the last words of the workspace otherwise
-    const bool hb_fw = packws && hb_from_forward(cfg, nb);
-    uint32_t* maxw = hb_fw ? (uint32_t*)(const_cast<float*>(sc) + 11)
-                           : (uint32_t*)(workspace + vx_mvn_enc_bwd_workspace_floats(cfg, nb) - 8);
-    float* slabs_w = ghpre + nb * H;
-    float* slabs_f = slabs_w + (int64_t)n_prw_ws * lenw;
+    const bool hb_fw = packws && p.hb_fw;
+    uint32_t* maxw = (uint32_t*)(hb_fw ? const_cast<float*>(packws) + pk.maxw : workspace + p.maxw);
     hipStream_t st = (hipStream_t)hs;
     int rc;
     bool f1t = false;                                      // fc1 gradient on the dimension-major kernel (ghpre holds ghpreT)
@@ -1196,36 +1201,28 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
     };
     if (packed) {
         const float* Wp = packws;
-        const uint32_t* gtab = (const uint32_t*)(packws + Rp * 64 + Rp);
-        if (use_t && !((gd_ready & 1) && (slabs_f + (int64_t)n_prf * lenf) == workspace + encb_gd_offset(cfg, nb))) {
-            float* gdT0 = slabs_f + (int64_t)n_prf * lenf;      // DIAG-row operand of both dimension-major kernels
+        const uint32_t* gtab = (const uint32_t*)(packws + pk.gtab);
+        if (use_t && !(gd_ready & 1)) {                    // (bit 0: the likelihood's last pass made gdT)
             hipLaunchKernelGGL(k_mvn_gd, dim3(num_cu() * 8), dim3(256), 0, st, (const float4*)gxT, (const float4*)epsT,
-                               (const float4*)ldT, cfg->scale, nb * D / 4, (float4*)gdT0);
+                               (const float4*)ldT, cfg->scale, nb * D / 4, (float4*)gdT);
             VX_CHECK_LAUNCH();
         }
         // (two full-size tile buffers: the three-buffer form of k_mvn_bwd_b.hip measured no faster -- docs/NOTEBOOK.md, round 5)
-        auto launch_bwb_on = [&](hipStream_t ws, const float* gdT, const uint16_t* hs3) -> int {
+        auto launch_bwb_on = [&](hipStream_t ws) -> int {
             const size_t lds = bb_lds_bytes(dm.D);
             int r = set_lds(k_mvn_enc_bwd_w_b<2>, lds);
             if (r) return r;
-            hipLaunchKernelGGL(k_mvn_enc_bwd_w_b<2>, dim3((unsigned)n_rowslabs, (unsigned)n_prw), dim3(BWB_THREADS), lds, ws, dm, hs3, epsT,
-                               gdT, gxT, gtab, sc, (const uint32_t*)maxw, slabs_w, Rp * (H + 1));
+            hipLaunchKernelGGL(k_mvn_enc_bwd_w_b<2>, dim3((unsigned)n_rowslabs, (unsigned)n_prw), dim3(BWB_THREADS), lds, ws, dm,
+                               (const uint16_t*)hs3, epsT, (const float*)gdT, gxT, gtab, sc, (const uint32_t*)maxw, slabs_w, Rp * (H + 1));
             VX_CHECK_LAUNCH();
             return VX_OK;
-        };
-        auto launch_bwb = [&]() -> int {
-            float* gdT = slabs_f + (int64_t)n_prf * lenf;
-            uint16_t* hs3 = (uint16_t*)(gdT + nb * D + 4);
-            // (its own bracket on ITS stream: the kernel's span while it shares the chip with the hidden gradient)
-            ProfScope ps("k_mvn_enc_bwd_w_b beside k_mvn_enc_bwd_h_b2", bwb_fork.side());
-            return launch_bwb_on(bwb_fork.side(), gdT, hs3);
         };
         // the bracket of the PAIR on the launch stream: from in front of the fork to behind the join of the head weight gradient's
         // stream = the span of {hidden gradient | head weight gradient} side by side (what bench.py prices with the sum of the two
         // kernels' flops); dropped at once when the two do not run side by side
         pair_ps.emplace("k_mvn_enc_bwd_h_b2 | k_mvn_enc_bwd_w_b side by side", st);
-        if ((gd_ready & 4) && (gd_ready & 2) && (gd_ready & 1) && hb_fw && use_t && bwb_shape(cfg, nb) && nb >= 4 &&
-            bh_lds_bytes(dm.D) <= 160 * 1024 && (mfma16_mode() & 8) && bwb_fork.fork(side_stream(1, st), st)) {
+        if ((gd_ready & 4) && (gd_ready & 2) && (gd_ready & 1) && hb_fw && use_t && p.bwb && p.bwh_t && p.side_streams &&
+            bwb_fork.fork(side_stream(1, st), st)) {
             // The head weight gradient needs nothing the hidden gradient makes once the step's operand maxima are there (bit 2:
             // vx_irt_lik_grad collected them): it starts NOW on a second stream, and the hidden gradient and then the fc1
             // gradient run beside it on the launch stream.  The two large kernels each fill the chip alone; side by side
@@ -1234,24 +1231,24 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
             // words: values that are already there, so the words do not change under the reader.)
             // (launched before or behind the hidden gradient: 9.63 against 9.62 ms -- the order does not matter)
             bwb_done = true;
-            rc = launch_bwb();
+            // (its own bracket on ITS stream: the kernel's span while it shares the chip with the hidden gradient)
+            ProfScope ps("k_mvn_enc_bwd_w_b beside k_mvn_enc_bwd_h_b2", bwb_fork.side());
+            rc = launch_bwb_on(bwb_fork.side());
             if (rc) return rc;
         } else {
             pair_ps->cancel();                                 // one kernel after the other: each has a bracket of its own
         }
-        if (use_t && nb >= 4 && bh_lds_bytes(dm.D) <= 160 * 1024) {
-            const float* WpT = (const float*)(gtab + Rp / 8 + 8);
+        if (use_t && p.bwh_t) {
+            const float* WpT = packws + pk.wpT;
             const size_t lds = bh_lds_bytes(dm.D);
             rc = set_lds(k_mvn_enc_bwd_h_t, lds);
             if (rc) return rc;
             f1t = yT && !rows && yT_stride % 16 == 0 && yT_stride >= nb && aligned16(yT) && cfg->J >= 32 &&
                   f1_lds_bytes(cfg->J) <= 160 * 1024;
-            if (bwhb_shape(cfg, nb)) {
-                float* gdT1 = slabs_f + (int64_t)n_prf * lenf;
-                uint8_t* himg = (uint8_t*)(gdT1 + nb * D + 4 + (bwb_shape(cfg, nb) ? nb * 64 : 0));
-                if (hb_fw) {                                             // made by the forward call's pack launches (k_pack_fused.hip)
-                    himg = (uint8_t*)(const_cast<float*>(sc) - hb_img_floats(dm.D));
-                } else {
+            if (p.bwhb) {
+                // the unit images: made by the forward call's pack launches (hb_fw: k_pack_fused.hip), or here
+                uint8_t* himg = (uint8_t*)(hb_fw ? const_cast<float*>(packws) + pk.himg : workspace + p.himg);
+                if (!hb_fw) {
                     hipLaunchKernelGGL(k_pack_heads_hb, dim3(hb_units(dm.D)), dim3(256), 0, st, dm.D, W21, W22, sc, himg, maxw);
                     VX_CHECK_LAUNCH();
                 }
@@ -1263,7 +1260,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                     rc = set_lds(k_mvn_enc_bwd_h_b<true>, ldsh);
                     if (rc) return rc;
                     hipLaunchKernelGGL(k_mvn_enc_bwd_h_b<true>, dim3((unsigned)((nb + 31) / 32)), dim3(HB_THREADS), ldsh, st, dm,
-                                       (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT1, f1t ? (float*)nullptr : ghpre, hT,
+                                       (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT, f1t ? (float*)nullptr : ghpre, hT,
                                        f1t ? ghpre : (float*)nullptr, maxw);
                 } else if (dm.D <= 112 && hb2_lds_bytes(dm.D) <= 160 * 1024) {
                     // large batch: 64 persons per wave, batches of four units per barrier (k_mvn_bwd_hb2.hip)
@@ -1278,13 +1275,13 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                     const int64_t n_done = (rem > 0 && 2 * rem <= round2 && nb > round2) ? nb - rem : nb;
                     // the short last round on the second stream beside the whole rounds (launched first), as in the forward
                     ForkScope tail_fork;
-                    const bool beside = n_done < nb && (mfma16_mode() & 8) && tail_fork.fork(side_stream(0, st), st);
+                    const bool beside = n_done < nb && p.side_streams && tail_fork.fork(side_stream(0, st), st);
                     const hipStream_t ts = beside ? tail_fork.side() : st;
                     auto launch_tail = [&]() -> int {
                         int r = set_lds(k_mvn_enc_bwd_h_b<false>, ldsh);
                         if (r) return r;
                         hipLaunchKernelGGL(k_mvn_enc_bwd_h_b<false>, dim3((unsigned)((nb - n_done + 32 * HB_WAVES - 1) / (32 * HB_WAVES))),
-                                           dim3(HB_THREADS), ldsh, ts, dm, (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT1,
+                                           dim3(HB_THREADS), ldsh, ts, dm, (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT,
                                            f1t ? (float*)nullptr : ghpre, hT, f1t ? ghpre : (float*)nullptr, maxw, n_done);
                         VX_CHECK_LAUNCH();
                         return VX_OK;
@@ -1294,7 +1291,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                         if (rc) return rc;                                  // (the scope joins)
                     }
                     hipLaunchKernelGGL((k_mvn_enc_bwd_h_b2<7, HNSET>), dim3((unsigned)((n_done + 255) / 256)),
-                                       dim3(64 * HB2_WAVES_OF(HNSET)), lds2, st, dm, (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT1,
+                                       dim3(64 * HB2_WAVES_OF(HNSET)), lds2, st, dm, (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT,
                                        f1t ? (float*)nullptr : ghpre, hT, f1t ? ghpre : (float*)nullptr, maxw);
                     if (beside) {
                         VX_CHECK_LAUNCH();
@@ -1309,14 +1306,14 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                     rc = set_lds(k_mvn_enc_bwd_h_b<false>, ldsh);
                     if (rc) return rc;
                     hipLaunchKernelGGL(k_mvn_enc_bwd_h_b<false>, dim3((unsigned)((nb + 32 * HB_WAVES - 1) / (32 * HB_WAVES))), dim3(HB_THREADS), ldsh, st, dm,
-                                       (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT1, f1t ? (float*)nullptr : ghpre, hT,
+                                       (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT, f1t ? (float*)nullptr : ghpre, hT,
                                        f1t ? ghpre : (float*)nullptr, maxw);
                 }
                 VX_CHECK_LAUNCH();
             } else {
             ProfScope ps("k_mvn_enc_bwd_h_t", st);
             hipLaunchKernelGGL(k_mvn_enc_bwd_h_t, dim3((unsigned)((nb + BH_P - 1) / BH_P)), dim3(BH_THREADS), lds, st, dm,
-                               cfg->scale, WpT, gtab, h, eps, ldT, gxT, slabs_f + (int64_t)n_prf * lenf, f1t ? (float*)nullptr : ghpre, hT,
+                               cfg->scale, WpT, gtab, h, eps, ldT, gxT, gdT, f1t ? (float*)nullptr : ghpre, hT,
                                f1t ? ghpre : (float*)nullptr);
             VX_CHECK_LAUNCH();
             }
@@ -1337,7 +1334,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                                dm, cfg->scale, Wp, gtab, h, eps, ldT, gx, ghpre);
             VX_CHECK_LAUNCH();
         }
-        if (nb > 0 && f1t && (mfma16_mode() & 8) && f1_fork.fork(side_stream(0, st), st)) {
+        if (nb > 0 && f1t && p.fc1_16 && p.side_streams && f1_fork.fork(side_stream(0, st), st)) {
             // the fc1 weight gradient needs ghpre only: it runs on a second stream beside the head weight gradient below
             // (0.33 ms of a 1M step that used to follow it) and is joined before this call returns (also on an error return)
             const hipStream_t fs = f1_fork.side();
@@ -1353,11 +1350,9 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
             rc = bwb_fork.join();
             if (rc) return rc;
             pair_ps.reset();                                   // the launch stream is behind both kernels here
-        } else if (use_t && bwb_shape(cfg, nb)) {
-            float* gdT = slabs_f + (int64_t)n_prf * lenf;
-            uint16_t* hs3 = (uint16_t*)(gdT + nb * D + 4);
+        } else if (use_t && p.bwb) {
             if (!(gd_ready & 2)) {                             // bit 1: the forward call already wrote the fp16 terms of hT here
-                hipLaunchKernelGGL(k_split2_f16, dim3(num_cu() * 8), dim3(256), 0, st, hT, nb * 64, sc + 3, hs3);
+                hipLaunchKernelGGL(k_split2_f16, dim3(num_cu() * 8), dim3(256), 0, st, hT, nb * 64, packws + pk.hscale, hs3);
                 VX_CHECK_LAUNCH();
             }
             if (!maxw_ready) {                                 // the operand maxima, normally collected by k_mvn_enc_bwd_h_b
@@ -1366,11 +1361,10 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                 VX_CHECK_LAUNCH();
             }
             ProfScope ps("k_mvn_enc_bwd_w_b", st);
-            rc = launch_bwb_on(st, gdT, hs3);
+            rc = launch_bwb_on(st);
             if (rc) return rc;
         } else if (use_t) {
             size_t lds = bt_lds_bytes(dm.D);
-            float* gdT = slabs_f + (int64_t)n_prf * lenf;     // DIAG-row operand, dimension-major (made above)
             const int n_jg1 = (int)((cfg->J + 127) / 128);
             if (!f1_done && !f1t && dm.Hp == 64 && (int64_t)n_jg * n_prf * 16 <= num_cu() && BT_THREADS == ENC_THREADS) {
                 // a small batch: the fc1 weight gradient (k_fc1_bwd<2, 1>) rides in the same launch (k_bwd_wt_fc1)
@@ -1378,7 +1372,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
                 if (ldsf > lds) lds = ldsf;
                 rc = set_lds(k_bwd_wt_fc1, lds);
                 if (rc) return rc;
-                const int f1fast = (!force_generic() && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(ghpre) && aligned16(y)) ? 1 : 0;
+                const int f1fast = f1fast_ok(cfg, ghpre, y);
                 ProfScope ps("k_mvn_enc_bwd_w_t + k_fc1_bwd", st);
                 hipLaunchKernelGGL(k_bwd_wt_fc1, dim3((unsigned)(n_rowslabs * n_prw + n_jg1 * n_prf)), dim3(BT_THREADS), lds, st, dm, hT,
                                    epsT, (const float*)gdT, gxT, gtab, slabs_w, Rp * (H + 1), n_rowslabs, n_prw, y, rows,
@@ -1402,7 +1396,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
             VX_CHECK_LAUNCH();
         }
     }
-    const bool fast = !packed && encb_fast_shape(cfg) && aligned16(W21) && aligned16(W22) && aligned16(h) && aligned16(eps) &&
+    const bool fast = !packed && p.encb_fast && aligned16(W21) && aligned16(W22) && aligned16(h) && aligned16(eps) &&
                       aligned16(gx) && aligned16(ghpre);
     if (nb > 0 && fast) {
         {
@@ -1451,7 +1445,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
     }
     if (f1_done || f1_launched) {
         // (joined below | launched with the head weight gradient: its slabs are summed below)
-    } else if (nb > 0 && f1t && (mfma16_mode() & 8)) {
+    } else if (nb > 0 && f1t && p.fc1_16) {
         rc = launch_fc1_c(st);
         if (rc) return rc;
     } else if (nb > 0 && f1t) {
@@ -1465,7 +1459,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
         {
             const size_t lds = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
             const dim3 grid((unsigned)n_jg, (unsigned)n_prf);
-            const int f1fast = (!force_generic() && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(ghpre) && aligned16(y)) ? 1 : 0;
+            const int f1fast = f1fast_ok(cfg, ghpre, y);
 #define LAUNCH_F1(HT)                                                                                        \
     rc = set_lds(k_fc1_bwd<HT>, lds);                                                                        \
     if (rc) return rc;                                                                                       \
@@ -1509,7 +1503,7 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
         rc = vx_reduce_slabs(slabs_f, n_prf, lenf, -1.0f, genc, hs);
         if (rc) return rc;
     }
-    rc = vx_reduce_slabs(slabs_w, n_prw, lenw_ref, -1.0f, genc + lenf, hs);
+    rc = vx_reduce_slabs(slabs_w, n_prw, p.lenw_ref, -1.0f, genc + lenf, hs);
     if (rc) return rc;
     if (tail) return vx_sum2(tail->ll, tail->ent, nb, tail->alpha, tail->loss, tail->sum_ws, const_cast<uint32_t*>(cfg->step_dev), hs);
     return VX_OK;
@@ -1681,15 +1675,14 @@ int vx_mvn_score_heads(const vx_irt_cfg* cfg, int64_t nb, const int64_t* rows, c
         !aligned16(h) || !aligned16(eps) || !aligned16(workspace))
         return VX_EINVAL;
     if (nb == 0) return VX_OK;
-    const float* sc = packws + vx_mvn_pack_floats(cfg) - FB_NSCALES;
+    const float* sc = packws + pack_layout(cfg).sc;
     hipStream_t st = (hipStream_t)hs;
     const int D = cfg->D;
     hipLaunchKernelGGL(k_pack_heads_col, dim3((unsigned)sb_tiles(D)), dim3(256), 0, st, D, W22, b22, sc, (uint8_t*)workspace);
     VX_CHECK_LAUNCH();
     // a batch that fills the chip: one workgroup of eight consumer waves and a loader wave a CU, the tiles through LDS once
     // (the L2 serves the 2 MB image to every wave of the plain form at 22 TB/s: rule 30); a smaller one: the plain form
-    static const bool no_ring = getenv("VX_SCORE_NO_RING") != nullptr;
-    const bool ring = !no_ring && nb >= 16384 && sbr_lds_bytes(D) <= 160 * 1024;
+    const bool ring = seams().score_ring && nb >= 16384 && sbr_lds_bytes(D) <= 160 * 1024;
     int rc;
     ProfScope ps("k_mvn_score_b", st, nb);
     if (ring) {
@@ -1866,7 +1859,7 @@ int64_t vx_norm_enc_param_floats(const vx_irt_cfg* cfg) {
 #define NH_PF 3
 #endif
 static bool nenc_h_shape(const vx_irt_cfg* cfg) {
-    return !force_generic() && (mfma16_mode() & 1) && cfg->H == 64 && cfg->J % 4 == 0 && cfg->J >= 256 &&
+    return !force_generic() && seams().fwd16 && cfg->H == 64 && cfg->J % 4 == 0 && cfg->J >= 256 &&
            nh_lds_bytes<NH_NP>(cfg->J) <= 160 * 1024;
 }
 int64_t vx_norm_enc_pack_floats(const vx_irt_cfg* cfg) {
@@ -1903,7 +1896,7 @@ int vx_norm_enc_forward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* 
         VX_CHECK_LAUNCH();
         return VX_OK;
     }
-    if (!force_generic() && (mfma16_mode() & 1) && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(y) && aligned16(W1) &&
+    if (!force_generic() && seams().fwd16 && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(y) && aligned16(W1) &&
         aligned16(b1) && aligned16(h) && nb_lds_bytes(cfg->J) <= 160 * 1024) {
         const size_t ldsb = nb_lds_bytes(cfg->J);                       // fc1 on the bf16 MFMA, W1 shared by the workgroup
         rc = set_lds(k_norm_enc_fwd_b, ldsb);
@@ -1973,7 +1966,7 @@ int vx_norm_enc_backward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t*
             float* ghpreT = slabs_f + (((int64_t)n_prf * lenf + 3) & ~(int64_t)3);
             hipLaunchKernelGGL(k_norm_enc_bwd_t64, dim3(nblk), dim3(256), 0, st, nb, W21, W22, h, gloc, graw, ghpreT, slabs_h);
             VX_CHECK_LAUNCH();
-            if (mfma16_mode() & 8) {
+            if (seams().fc1_16) {
                 ProfScope ps("k_fc1_bwd_c", st);                          // operands through LDS (k_fc1_bwd_c.hip), three bf16 terms
                 rc = set_lds(k_fc1_bwd_c<false>, f1c_lds_bytes());             // (tmajor: nb % 4 == 0, ghpreT 16-byte aligned)
                 if (rc) return rc;
@@ -1996,7 +1989,7 @@ int vx_norm_enc_backward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t*
         VX_CHECK_LAUNCH();
         const size_t lds = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
         const dim3 grid((unsigned)n_jg, (unsigned)n_prf);
-        const int f1fast = (!force_generic() && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(ghpre) && aligned16(y)) ? 1 : 0;
+        const int f1fast = f1fast_ok(cfg, ghpre, y);
 #define LAUNCH_F1(HT)                                                                                        \
     rc = set_lds(k_fc1_bwd<HT>, lds);                                                                        \
     if (rc) return rc;                                                                                       \
