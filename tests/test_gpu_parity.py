@@ -1157,8 +1157,8 @@ def test_captured_ccdm_step_equals_eager_step(cdm, B, vae):
     (2048, None),        # the headline's model, small-batch kernels (SPLIT forward / hidden gradient), full batch
     (33024, None),       # ... the large-batch kernels of the judged step, second-stream tails included in the capture
     (5000, 100),         # the reference's own usage: subsample_size = 100 (test.py:338), host-drawn rows staged per replay
-    (5000, 50),          # ... a subsample that is no multiple of 4: drawn two phantom rows longer (IrtEngine._pad_batch)
-])
+    (5000, 50),          # ... a subsample that is no multiple of 4: step() launches it over its own 50 rows (the person-major
+])                       # backward); the padded form of steps() is test_captured_padded_steps_equal_eager_padded_steps below
 def test_captured_amortized_step_equals_eager_step(N, B):
     """The amortized D = 100 step (VaeIRT, vi.py:673-693) replayed from its HIP graph -- Philox step and Adam's t read from
     the device counter that the loss reduction advances, a subsample's rows copied into the fixed buffer the captured
@@ -1185,6 +1185,36 @@ def test_captured_amortized_step_equals_eager_step(N, B):
         assert (st.get("graph") is not None) == graph
         if graph and B is not None:
             # the replay fetches its draw from the pinned host ring (vx_irt_cfg.rows_ring): no copy in front of it
+            assert st.get("ring") is not None and st["ring"].is_pinned() and eng.rows_ring_slots < n_steps
+        out.append((torch.stack(losses).cpu().numpy(), eng.P.cpu().numpy().copy()))
+    assert np.isfinite(out[0][0]).all() and len(set(out[0][0].tolist())) == n_steps
+    for u, v in zip(out[0], out[1]):
+        assert np.array_equal(u, v)
+
+
+def test_captured_padded_steps_equal_eager_padded_steps():
+    """steps() over subsamples of 50, the way fit() hands them over: drawn two phantom rows longer (IrtEngine._pad_batch), 52
+    rows a launch.  Replayed (single-step graph, four steps a replay, rows from the pinned ring -- 19 steps: the ring wraps)
+    against the same padded steps launched kernel by kernel: same bits in every loss and every parameter, across a scheduler
+    milestone.  (Against the oracle: tests/test_gpu_fit_path.py.)"""
+    from vipsy_amd.engine import IrtEngine, LrSpec
+    N, B, J, D, H, n_steps = 5000, 50, 500, 100, 64, 19
+    y, _, _ = _random_problem(N, J, D, H, "irt_2pl", 0.1, seed=N + 1)
+    draws = np.random.RandomState(5)
+    rows_all = [torch.from_numpy(draws.choice(N, size=B, replace=False).astype(np.int64)) for _ in range(n_steps)]
+    out = []
+    for graph in (True, False):
+        eng = IrtEngine(torch.from_numpy(y).to(_dev()), model="irt_2pl", D=D, amortized=True, H=H, seed=11)
+        eng.use_graph = graph
+        lrs = LrSpec(lambda m, p: {"lr": 1e-2 if p in ("a", "b") else 1e-3}, milestones=(4,), gamma=0.5)
+        losses = eng.steps(lrs, rows_all, b_global=B, scheduler=True)
+        torch.cuda.synchronize()
+        assert eng.t == n_steps and lrs.epoch == n_steps
+        assert eng.last["nb"] == 52 and eng.last["n_valid"] == B
+        st = getattr(eng, "_graph", None) or {}
+        assert (st.get("graph") is not None) == graph
+        if graph:
+            assert st.get("multi") is not None and eng._graphs.get(("rows", 52, B)) is st
             assert st.get("ring") is not None and st["ring"].is_pinned() and eng.rows_ring_slots < n_steps
         out.append((torch.stack(losses).cpu().numpy(), eng.P.cpu().numpy().copy()))
     assert np.isfinite(out[0][0]).all() and len(set(out[0][0].tolist())) == n_steps

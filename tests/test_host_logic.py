@@ -105,6 +105,108 @@ def test_loss_reaches_the_ring_without_an_optimiser_launch():
     assert float(eng.step_loss()) == want and float(eng.loss_ring[eng.t % LOSS_RING]) == want
 
 
+def test_pad_batch_host_side():
+    """IrtEngine._pad_batch without a device (a stub HipBackend that answers the two layout queries): a subsample that is no
+    multiple of 4 grows by indices equal to n_local -- the phantom person behind the shard's own, every response missing in the
+    extended copy -- with b_global made explicit, a list entry by entry; and everything it stands down on.  steps() tells
+    loss_and_grads how many phantoms the rows carry, and only while it runs."""
+    from vipsy_amd.engine import HipBackend, LrSpec
+
+    class _Stub(HipBackend):
+        layout, gd_offset, asked = 1, 0, None
+
+        def __init__(self):
+            pass
+
+        def mvn_enc_bwd_layout(self, cfg, nb):
+            self.asked = nb
+            return self.layout
+
+        def mvn_enc_bwd_gd_offset(self, cfg, nb):
+            return self.gd_offset
+
+    n, J = 64, 8
+    y = torch.from_numpy(np.random.RandomState(6).randint(0, 2, size=(n, J)).astype(np.uint8))
+
+    def mk(be=None, **kw):
+        kw = dict({"D": 4, "amortized": True, "H": 64}, **kw)
+        return IrtEngine(y, model="irt_2pl", backend=_Stub() if be is None else be, **kw)
+
+    for B, pad in ((50, 2), (1, 3), (2, 2), (3, 1), (61, 3)):
+        eng = mk()
+        rows = torch.randperm(n)[:B]
+        got, bg = eng._pad_batch(rows, None, None)
+        assert eng.be.asked == B + pad                          # the layout is asked for the padded count, before anything is padded
+        assert bg == B and got.dtype == rows.dtype and got.numel() == B + pad and (B + pad) % 4 == 0
+        assert torch.equal(got[:B], rows) and bool((got[B:] == n).all())
+        assert tuple(eng._y_ext.shape) == (n + 1, J) and torch.equal(eng._y_ext[:n], eng.y) and bool((eng._y_ext[n] == 255).all())
+        assert eng._y_ext_lik is eng._y_ext                     # (no phantom items here: one copy serves the likelihood too)
+        assert eng._pad_batch(rows, 1000, None)[1] == 1000      # the caller's b_global stands
+    eng = mk()
+    lst = [torch.randperm(n)[:10] for _ in range(3)]            # a list (the steps of steps()): entry by entry
+    got, bg = eng._pad_batch(lst, None, None)
+    assert bg == 10 and len(got) == 3
+    for r, g in zip(lst, got):
+        assert torch.equal(g[:10], r) and g.tolist()[10:] == [n, n]
+    eng = IrtEngine(y[:, :7].contiguous(), model="irt_2pl", D=4, amortized=True, H=64, backend=_Stub())
+    eng._pad_batch(torch.arange(10), None, None)                # phantom items: the likelihood's extended copy is its own
+    assert eng._y_ext_lik is not eng._y_ext and tuple(eng._y_ext_lik.shape) == (n + 1, eng.J) and bool((eng._y_ext_lik[n] == 255).all())
+
+    rows = torch.arange(10)
+
+    def stands_down(eng, r=rows, eps=None):
+        got, bg = eng._pad_batch(r, None, eps)
+        return got is r and bg is None and eng._y_ext is None
+    assert stands_down(mk(), torch.arange(12))                  # a multiple of 4
+    assert stands_down(mk(), None)                              # the full batch
+    assert stands_down(mk(), eps=torch.zeros(10, 4))            # the caller's draws
+    assert stands_down(mk(be=OracleBackend()))                  # not the HIP backend
+    assert stands_down(mk(estimator="score"))
+    assert stands_down(mk(amortized=False))                     # the per-person guide
+    assert stands_down(mk(D=1))
+    assert stands_down(mk(), [torch.arange(10), torch.arange(9)])       # unequal sizes
+    off = mk()
+    off.pad_batch = False                                       # the seam (VX_PAD_BATCH=0)
+    assert stands_down(off)
+    for layout, gd in ((0, 0), (1, -1)):                        # the padded count would not run the dimension-major backward
+        eng = mk()
+        eng.be.layout, eng.be.gd_offset = layout, gd
+        assert stands_down(eng)
+
+    # steps(): the phantom count is set for loss_and_grads while the steps run, and cleared behind them -- also when they raise
+    eng, seen = mk(), []
+    eng.step = lambda lrs, rows=None, b_global=None: seen.append((eng._phantom_rows, int(rows.numel()), b_global))
+    eng.use_graph = False
+    eng.steps(LrSpec(0.0), [torch.arange(10), torch.arange(10, 20)])
+    assert seen == [(2, 12, 10), (2, 12, 10)] and eng._phantom_rows == 0
+    seen.clear()
+    eng.steps(LrSpec(0.0), [torch.arange(12)], b_global=77)
+    assert seen == [(0, 12, 77)] and eng._phantom_rows == 0
+
+    def boom(lrs, rows=None, b_global=None):
+        raise KeyError("stop")
+    eng.step = boom
+    try:
+        eng.steps(LrSpec(0.0), [torch.arange(10)])
+    except KeyError:
+        pass
+    assert eng._phantom_rows == 0
+
+    # loss_and_grads refuses -- before its first launch -- rows that carry phantoms on a launch that could not take them out
+    # behind the likelihood: a count the dimension-major backward does not run, or no extended copy of the responses
+    for layout, gd, ext in ((0, 0, True), (1, -1, True), (1, 0, False)):
+        eng = mk()
+        if ext:
+            eng._pad_batch(torch.arange(10), None, None)
+        eng.be.layout, eng.be.gd_offset, eng._phantom_rows = layout, gd, 2
+        try:
+            eng.loss_and_grads(torch.cat([torch.arange(10), torch.full((2,), n)]), 10)
+        except RuntimeError as e:
+            assert "2 phantom rows" in str(e) and "12 rows" in str(e) and "D = 4" in str(e)
+        else:
+            raise AssertionError("phantom rows were launched on layout %d, gd offset %d" % (layout, gd))
+
+
 def test_graph_replay_forms_per_engine():
     """Which steps of each engine replay from a captured HIP graph (_graph_mode), and which IrtEngine steps fuse the optimiser
     into the step kernel (_fused_tail_args).  A stub HipBackend: building an engine and asking for its form call no library."""

@@ -845,7 +845,8 @@ class _EngineBase(object):
     # it): a fifth of BASELINE config 2's 42 us step, 5 % of the reference's own B = 100 step.  Nothing a step needs from the
     # host is made by the step before it -- the Philox step and Adam's t come from the device counter, a subsample's rows from
     # the pinned ring (slot = counter % slots), the loss goes into the ring -- so graph_steps consecutive steps are captured
-    # as one graph and a fit loop replays that (steps(): same kernels, same order, same bits as step() called in a loop).
+    # as one graph and a fit loop replays that (steps(): same kernels, same order, same bits as step() called in a loop --
+    # except where IrtEngine.steps pads a subsample, see there).
     graph_steps = 4
 
     def _steps_form(self, lrs, rows_seq, b_global, scheduler):
@@ -937,9 +938,13 @@ class _EngineBase(object):
     def steps(self, lrs, rows_seq, b_global=None, scheduler=False):
         """len(rows_seq) consecutive steps of a fit loop -- what step(lrs, rows=r, b_global=b_global) for r in rows_seq does,
         each followed by lrs.scheduler_step() when `scheduler` (vi.py:639-640) -- with the same results bit for bit, replayed
-        graph_steps at a time from one graph where the form allows.  rows_seq: one entry per step (None = the full batch, or
-        host / device int64 LOCAL row indices).  Returns the losses, one 0-d device tensor per step (slots of the loss ring:
-        the last LOSS_RING - 1 of them stay valid)."""
+        graph_steps at a time from one graph where the form allows (tests/test_gpu_parity.py::
+        test_steps_replayed_four_at_a_time_equal_single_steps, tests/test_gpu_fit_path.py::
+        test_unpadded_steps_vs_oracle_and_bit_equal_to_step_in_a_loop).  A subclass that launches the steps over other rows
+        than it was handed (IrtEngine.steps: a subsample that is no multiple of 4) promises the oracle's results within the
+        parity tolerance instead, not step()'s bits.  rows_seq: one entry per step (None = the full batch, or host / device
+        int64 LOCAL row indices).  Returns the losses, one 0-d device tensor per step (slots of the loss ring: the last
+        LOSS_RING - 1 of them stay valid)."""
         out, i, n = [], 0, len(rows_seq)
         while i < n:
             mode = self._steps_form(lrs, rows_seq[i:], b_global, scheduler)
@@ -1213,6 +1218,7 @@ class IrtEngine(_EngineBase):
         self.base = (torch.zeros(max(self.n_local, 1), dtype=torch.float32, device=self.dev)
                      if (estimator == "score" and baseline == "avg") else None)
         self._sp = self._y_ext = self._y_ext_lik = None      # made on first use (_sparse_lists, _pad_batch)
+        self._phantom_rows = 0                               # phantom rows at the tail of the subsamples steps() is running
 
     pad_items = os.environ.get("VX_PAD_ITEMS", "1") != "0"          # test seam: 0 = the kernels see the problem's own item count
 
@@ -1256,11 +1262,21 @@ class IrtEngine(_EngineBase):
         return super().step(lrs, rows=rows, b_global=b_global, eps=eps, num_particles=S)
 
     def steps(self, lrs, rows_seq, b_global=None, scheduler=False):
-        """_EngineBase.steps over subsamples padded to a multiple of 4 rows (_pad_batch) when all have one size."""
+        """_EngineBase.steps over subsamples padded to a multiple of 4 rows (_pad_batch) when all have one size.  Where nothing
+        is padded the results are those of step() in a loop, bit for bit.  Where rows are padded the steps run other kernels
+        over other row counts than step() does, so the bits differ: both are within the parity tolerance of the oracle, loss
+        by loss and gradient by gradient (tests/test_gpu_fit_path.py::test_padded_steps_vs_oracle_at_frozen_parameters, and
+        test_trained_trajectory_through_padded_steps_within_1e3_of_cpu_reference for the trained parameters)."""
+        phantoms = 0
         if rows_seq and all(torch.is_tensor(r) for r in rows_seq) and len({int(r.numel()) for r in rows_seq}) == 1:
+            n = int(rows_seq[0].numel())
             padded, b_global = self._pad_batch(list(rows_seq), b_global, None)   # (a list: the same rule as for particles)
-            rows_seq = padded
-        return super().steps(lrs, rows_seq, b_global=b_global, scheduler=scheduler)
+            rows_seq, phantoms = padded, int(padded[0].numel()) - n
+        self._phantom_rows = phantoms                        # loss_and_grads refuses a launch that could not take them out
+        try:
+            return super().steps(lrs, rows_seq, b_global=b_global, scheduler=scheduler)
+        finally:
+            self._phantom_rows = 0
 
     def _pad_persons(self, be, cfg, rows):
         """Persons the full-batch kernels of the amortized multivariate guide are launched over: the shard's own count, or --
@@ -1465,10 +1481,17 @@ class IrtEngine(_EngineBase):
                 eps = e_p
             n_valid, y_k, y_l = nb, self.y, (self.y_lik if self.y_lik is not None else self.y)
             keep = None
-            if rows is not None and self._y_ext is not None:
+            phantoms = self._phantom_rows if rows is not None else 0
+            ext = rows is not None and self._y_ext is not None
+            if ext:
                 # rows of a padded subsample may point at the phantom person behind the shard's own (_pad_batch)
                 y_k, y_l = self._y_ext, self._y_ext_lik
-                keep = (rows != self.n_local).to(torch.float32)
+            if phantoms and not (ext and be.mvn_enc_bwd_layout(cfg, nb) == 1 and be.mvn_enc_bwd_gd_offset(cfg, nb) >= 0):
+                # the phantoms leave the step as columns of gxT / gdT: a launch without those operands would carry their
+                # entropy and prior into the loss and their gradients into the encoder's
+                raise RuntimeError("a subsample padded with %d phantom rows cannot be launched over %d rows of %s, D = %d, "
+                                   "J = %d, H = %d: the dimension-major backward kernels do not take this shape"
+                                   % (phantoms, nb, self.model, self.D, self.J, self.H))
             if rows is None and eps is None:
                 self._n_pad = self._pad_persons(be, cfg, rows)
                 if self._n_pad != nb:                      # phantom persons up to a multiple of 8 (_pad_persons)
@@ -1504,6 +1527,10 @@ class IrtEngine(_EngineBase):
                                    step_dev=self._step_dev, rows_ring=ring)
                     self._capture_ring_used = True
                 be.mvn_enc_forward(cfg_f, y_k, rows, nb, self.gid0, enc, eps, fw)
+            if ext:
+                # behind the forward call: in a captured step `rows` holds this step's draw only once the forward's first launch
+                # has fetched it from the ring (in front of it: the draw of the step before)
+                keep = (rows != self.n_local).to(torch.float32)
             gd_off = be.mvn_enc_bwd_gd_offset(cfg, nb)     # the backward's DIAG-row operand, made in the likelihood's last pass
             gdT = encb_ws[gd_off:gd_off + nb * D] if gd_off >= 0 else None
             # the step's largest |gx|, |gd|, |eps| (the head weight gradient's power of two), collected by the likelihood's last
@@ -1524,7 +1551,9 @@ class IrtEngine(_EngineBase):
                     ll[n_valid:nb].zero_()
                     fw["ent"][n_valid:nb].zero_()
                 if keep is not None and gdT is not None and gx is None:
-                    gxT[:nb * D].view(D, nb).mul_(keep)    # (a padded subsample's phantom rows, wherever they stand)
+                    # (a padded subsample's phantom rows, wherever they stand.  Rows without phantoms on a shape that has no
+                    # gdT pass by: nothing to take out; rows WITH phantoms on such a shape were refused above)
+                    gxT[:nb * D].view(D, nb).mul_(keep)
                     gdT[:nb * D].view(D, nb).mul_(keep)
                     ll[:nb].mul_(keep)
                     fw["ent"][:nb].mul_(keep)
@@ -1558,7 +1587,7 @@ class IrtEngine(_EngineBase):
             if not fused_loss:
                 be.sum2_into(ll, fw["ent"], nb, -scale, lossslot, self.sum_ws, **sdc)
             self._zero_phantom_head_grads()
-            self.last = {"fw": fw, "gx": gx, "gxT": gxT, "ll": ll, "nb": nb, "n_valid": n_valid}
+            self.last = {"fw": fw, "gx": gx, "gxT": gxT, "ll": ll, "nb": nb, "n_valid": n_valid - phantoms}
         else:
             # D = 1: the flat item layout [a: J | b: J | c: J | d: J] IS the kernels' gradient layout -> written in place
             g1d, i1d_ws = gitem, self._buf("i1d_ws", be.irt1d_workspace(cfg, nb))

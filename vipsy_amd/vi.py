@@ -162,7 +162,9 @@ class BasePsy(object):
         K = getattr(self.engine, "graph_steps", 1) if S == 1 and hasattr(self.engine, "steps") else 1
         if K > 1:
             # one particle: the iterations go to the engine K at a time (IrtEngine.steps: several steps of the loop replayed from
-            # one graph where the step's form allows; the draws are made in the same order, the results are the same bits)
+            # one graph where the step's form allows; the draws are made in the same order.  The results are the bits of step()
+            # in a loop, except for a subsample_size that is no multiple of 4 on the shapes IrtEngine.steps pads: there both
+            # are within the parity tolerance of the oracle, tests/test_gpu_fit_path.py)
             i = 0
             while i < max_iter:
                 n = min(K, max_iter - i)
