@@ -50,6 +50,38 @@ def test_observed_cell_lists_encode_the_responses():
         for w0 in range(0, len(pidx), 4096):
             c = np.array([cnt[i] if i >= 0 else -1 for i in pidx[w0:w0 + 4096]])
             assert (np.diff(c) <= 0).all()
+    # structured designs (tests/response_designs.py): booklets of very different length in file order and shuffled, 64 empty
+    # persons in a row, a complete case at J = 1024, the degenerate ends -- where the lists of a group do NOT end together
+    from tests import design_cases as dc
+    for name in ("sorted9000", "shuffled3000", "j1024_complete", "empty_block_small", "all_missing", "single_cell", "hetero_shards"):
+        y, facts = dc.design(name)
+        n, J = y.shape
+        eng = IrtEngine(torch.from_numpy(y), model="irt_2pl", D=1, backend=OracleBackend(), observed_lists=True)
+        sp = eng._sparse_lists(None)
+        assert sp is not None and sp["n_groups"] == (n + 63) // 64 and sp["missing"] == facts["missing"], name
+        assert np.array_equal(_decode_lists(sp, n, J), y), name
+        cnt = (y != 255).sum(1)
+        pidx, glen = sp["pidx"].cpu().numpy(), sp["glen"].cpu().numpy()
+        c = np.where(pidx >= 0, cnt[np.maximum(pidx, 0)], -1)
+        for w0 in range(0, len(pidx), 4096):
+            assert (np.diff(c[w0:w0 + 4096]) <= 0).all(), name
+            assert sorted(pidx[w0:w0 + 4096][pidx[w0:w0 + 4096] >= 0].tolist()) == list(range(w0, min(n, w0 + 4096))), name
+        longest = np.maximum(c, 0).reshape(-1, 64).max(1)
+        assert np.array_equal(glen, (longest + 3) // 4), name         # the quads of the longest list of each group
+        assert np.array_equal(glen == 0, longest == 0), name          # ... none exactly for a group without an observed cell
+        assert sp["Lq"] == max(1, (int(cnt.max()) + 3) // 4), name
+        if "empty_block" in facts:
+            assert int((glen == 0).sum()) >= 1, name                  # the 64 empty persons fill a whole group (with the lone one)
+        if name == "j1024_complete":
+            assert sp["Lq"] == 256 and glen[0] == 256 and int(np.median(glen)) <= 32      # one complete case sets Lq for all
+        if name == "all_missing":
+            assert sp["Lq"] == 1 and (glen == 0).all()
+        if name == "single_cell":
+            assert sp["Lq"] == 1 and glen.tolist() == [1] + [0] * (len(glen) - 1)
+        if name in ("shuffled3000", "sorted9000"):
+            # lists of one group do not end together: the group at a booklet boundary holds lists of two lengths
+            spread = np.array([c[g * 64:(g + 1) * 64].max() - max(0, c[g * 64:(g + 1) * 64].min()) for g in range(len(glen))])
+            assert spread.max() >= 30, name
     # mostly observed responses, or a minibatch: no lists
     y = rng.randint(0, 2, size=(100, 10)).astype(np.uint8)
     eng = IrtEngine(torch.from_numpy(y), model="irt_2pl", D=1, backend=OracleBackend(), observed_lists=True)
