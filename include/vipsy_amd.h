@@ -36,7 +36,7 @@ extern "C" {
 #define VX_OK 0
 #define VX_EINVAL (-1)       /* bad argument / unsupported shape */
 #define VX_EUNIMPL (-2)
-#define VX_ABI_VERSION 5
+#define VX_ABI_VERSION 6
 
 enum vx_model { VX_IRT_1PL = 1, VX_IRT_2PL = 2, VX_IRT_3PL = 3, VX_IRT_4PL = 4 }; /* vi.py:538-543 */
 
@@ -412,6 +412,37 @@ int64_t vx_sm_enc_bwd_workspace_floats(const vx_hodina_cfg* cfg, int64_t nb);
 int vx_sm_enc_backward(const vx_hodina_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* W2,
                        const float* h, const float* z, const float* off, const float* T, float* gla, float* genc,
                        float* workspace, void* hip_stream);
+
+/* ---- Person scores by quadrature over a fixed grid of latent nodes (no reference counterpart: the reference stops at fit()).
+ * For a response row y_i and G nodes with normalised log-weights logw[G] and coordinates coord[G][D]:
+ *     ll[i][g]  = sum_j log P(y_ij | node g)                      (missing cells: the reference's constant, as in the step)
+ *     loglik[i] = log sum_g exp(logw[g] + ll[i][g])               the marginal log-likelihood of the row
+ *     mean[i][D], sd[i][D]                                        posterior mean (EAP) and standard deviation (PSD) of coord
+ *     argmax[i]                                                   the node that maximises logw + ll (ties: the lowest index)
+ * Exact and deterministic -- no guide, no random numbers: the item parameters are all it takes, so respondents that were
+ * not in the training data are scored like those that were.  Two steps:
+ *   1. vx_grid_table_irt / vx_grid_table_cdm fill `img` (vx_grid_image_bytes(J, G) bytes, 16-byte aligned) with the tables
+ *      T1[j][g] = log P(y_j = 1 | g), T0[j][g] = log P(y_j = 0 | g) as the fp16-pair operand image of the main kernel.
+ *        IRT: nodes theta[G][D]; item parameters as the step kernels take them (a [D][J] -- unused for 1PL, which needs D = 1 --,
+ *             b, unconstrained c_un / d_un for 3PL / 4PL); z = Dc (theta_g . a_j + b_j) through the cell of the step kernels.
+ *             cfg: model, D, J, Dc.
+ *        DINA / DINO: the nodes are the G = 2^K patterns in the order of all_attrs (bit k of g = attribute k; their coordinates
+ *             are the attribute bits, D = K); q, g_un, s_un as vx_ccdm_grad takes them; dino: 0 / 1.  cfg: K, J.
+ *   2. vx_grid_posterior: rows (or NULL) picks the persons, y is [n_local][J] (254 = a cell outside the problem: adds nothing).
+ *      The log-likelihoods are a GEMM of 0/1 indicators with the tables on v_mfma_f32_32x32x16_f16; node tiles are combined by
+ *      an online log-sum-exp with the moments taken about the running MAP node, nothing of size [nb][G] touches memory, and
+ *      every sum runs in a fixed order: the same call gives the same bits, and a person gives the same bits through `rows`.
+ * Limits: 1 <= J <= 1024, 1 <= G <= 1024, 1 <= D (K) <= 10, nb >= 1; VX_EINVAL beyond them. */
+int64_t vx_grid_image_bytes(int32_t J, int32_t G);
+int vx_grid_table_irt(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int32_t G, const float* a /*[D][J] or NULL (1PL)*/,
+                      const float* b /*[J]*/, const float* c_un /*[J] or NULL*/, const float* d_un /*[J] or NULL*/,
+                      void* img, void* hip_stream);
+int vx_grid_table_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const float* g_un, const float* s_un,
+                      void* img, void* hip_stream);
+int vx_grid_posterior(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G,
+                      int32_t D, const void* img, const float* logw /*[G]*/, const float* coord /*[G][D]*/,
+                      float* loglik /*[nb]*/, float* mean /*[nb][D]*/, float* sd /*[nb][D]*/, int32_t* argmax /*[nb]*/,
+                      void* hip_stream);
 
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,

@@ -30,6 +30,7 @@
 #include "k_cdm_sf.hip"
 #include "k_synth.hip"
 #include "k_vaeccdm.hip"
+#include "k_grid_post.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2124,6 +2125,65 @@ int vx_ccdm_grad(const vx_hodina_cfg* cfg, int32_t dino, const uint8_t* y, const
     return VX_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Person scores on a grid of latent nodes (k_grid_post.hip): two table builders and one kernel
+int64_t vx_grid_image_bytes(int32_t J, int32_t G) {
+    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG) return VX_EINVAL;
+    return gp_image_bytes(J, G);
+}
+
+int vx_grid_table_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* a, const float* b, const float* c_un,
+                      const float* d_un, void* img, void* hs) {
+    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GP_MAXD || cfg->J < 1 || cfg->J > GP_MAXJ ||
+        G < 1 || G > GP_MAXG || !theta || !b || !img || !aligned16(img))
+        return VX_EINVAL;
+    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
+        return VX_EINVAL;
+    const int64_t cells = (int64_t)gp_nt(G) * 32 * gp_kc(cfg->J) * 16;
+    const int blocks = grid_1d(cells, 256);
+    hipStream_t st = (hipStream_t)hs;
+#define LAUNCH_GT(M)                                                                                                  \
+    hipLaunchKernelGGL((k_grid_table_irt<M>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, \
+                       a, b, c_un, d_un, (uint16_t*)img)
+    if (cfg->model == 1) { LAUNCH_GT(1); } else if (cfg->model == 2) { LAUNCH_GT(2); } else if (cfg->model == 3) { LAUNCH_GT(3); }
+    else { LAUNCH_GT(4); }
+#undef LAUNCH_GT
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_table_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* g_un, const float* s_un, void* img,
+                      void* hs) {
+    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || cfg->J > GP_MAXJ || (dino != 0 && dino != 1) || !q || !g_un || !s_un || !img ||
+        !aligned16(img))
+        return VX_EINVAL;
+    const int64_t cells = (int64_t)gp_nt(1 << cfg->K) * 32 * gp_kc(cfg->J) * 16;
+    hipLaunchKernelGGL(k_grid_table_cdm, dim3(grid_1d(cells, 256)), dim3(256), 0, (hipStream_t)hs, (int)cfg->K, (int)cfg->J,
+                       (int)dino, q, g_un, s_un, (uint16_t*)img);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_posterior(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, int32_t D, const void* img,
+                      const float* logw, const float* coord, float* loglik, float* mean, float* sd, int32_t* argmax, void* hs) {
+    if (!y || !img || !aligned16(img) || !logw || !coord || !loglik || !mean || !sd || !argmax) return VX_EINVAL;
+    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || D < 1 || D > GP_MAXD || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    const int64_t units = (nb + 32 * GP_MT - 1) / (32 * GP_MT);
+    int64_t blocks = (units + GP_WAVES - 1) / GP_WAVES;
+    const int64_t cap = (int64_t)num_cu() * 2;                 // two waves a SIMD; a block's first act is to fill its LDS
+    if (blocks > cap) blocks = cap;
+    hipStream_t st = (hipStream_t)hs;
+    const uint4* im = (const uint4*)img;
+#define LAUNCH_GP(DPV)                                                                                                \
+    hipLaunchKernelGGL((k_grid_post<DPV>), dim3((int)blocks), dim3(GP_THREADS), (size_t)gp_nt(G) * 32 * (DPV + 1) * sizeof(float), \
+                       st, y, rows, nb, (int)J, (int)G, (int)D, im, logw, coord, loglik, mean, sd, argmax)
+    if (D == 1) { LAUNCH_GP(1); } else if (D == 2) { LAUNCH_GP(2); } else if (D == 3) { LAUNCH_GP(3); }
+    else if (D == 4) { LAUNCH_GP(4); } else if (D <= 6) { LAUNCH_GP(6); } else if (D <= 8) { LAUNCH_GP(8); } else { LAUNCH_GP(10); }
+#undef LAUNCH_GP
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Bernoulli-guide DINA / DINO with the score-function estimator (VCDM / VaeCDM, vi.py:726-816): k_cdm_sf.hip

@@ -227,6 +227,24 @@ class HipBackend(object):
                                  _hip.ptr(s_), _hip.ptr(elbo), _hip.ptr(gitem), _hip.ptr(ws), _hip.stream_ptr())
         _hip.check(rc, "vx_ccdm_grad")
 
+    def grid_image_bytes(self, J, G):
+        return self._size("vx_grid_image_bytes", J, G)
+
+    def grid_table_irt(self, cfg, theta, G, a, b, c_un, d_un, img):
+        rc = self.L.vx_grid_table_irt(ctypes.byref(cfg), _hip.ptr(theta), G, _hip.ptr(a), _hip.ptr(b), _hip.ptr(c_un),
+                                      _hip.ptr(d_un), _hip.ptr(img), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_table_irt")
+
+    def grid_table_cdm(self, cfg, dino, q, g, s_, img):
+        rc = self.L.vx_grid_table_cdm(ctypes.byref(cfg), int(dino), _hip.ptr(q), _hip.ptr(g), _hip.ptr(s_), _hip.ptr(img),
+                                      _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_table_cdm")
+
+    def grid_posterior(self, y, rows, nb, J, G, D, img, logw, coord, loglik, mean, sd, argmax):
+        rc = self.L.vx_grid_posterior(_hip.ptr(y), _hip.ptr(rows), nb, J, G, D, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord),
+                                      _hip.ptr(loglik), _hip.ptr(mean), _hip.ptr(sd), _hip.ptr(argmax), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_posterior")
+
     def cdm_sf_workspace(self, cfg, nb):
         return self._size("vx_cdm_sf_workspace_floats", ctypes.byref(cfg), nb)
 
@@ -347,6 +365,48 @@ class HipBackend(object):
         rc = self.L.vx_philox_normals(_hip.ptr(out), _hip.ptr(gids), gid0, n, D, seed, step, stream,
                                       _hip.stream_ptr())
         _hip.check(rc, "vx_philox_normals")
+
+
+SCORE_MAX_NODES = 1024           # GP_MAXG (vipsy_amd/csrc/k_grid_post.hip)
+SCORE_MAX_DIMS = 3               # IRT: the tensor-product grid stops being a method beyond three dimensions
+
+
+def score_grid(D, nodes=61, span=6.0):
+    """The quadrature grid of IrtEngine.score: `nodes` equally spaced points on [-span, span] in each of the D dimensions
+    (tensor product, dimension 0 slowest: node g = (i_0 * nodes + i_1) * nodes + i_2 sits at (p[i_0], p[i_1], p[i_2])), weights
+    proportional to exp(-|theta|^2 / 2) -- the N(0, I) prior of the model (vi.py:590) -- normalised to sum 1.
+    Returns (theta float32 [G, D], logw float32 [G]); `nodes` may also be an explicit pair (theta [G, D], logw [G])."""
+    D = int(D)
+    if not 1 <= D <= SCORE_MAX_DIMS:
+        raise ValueError("grid scores need 1 <= x_feature <= %d (got %d): a tensor-product grid of n nodes a dimension has "
+                         "n**D points, and the kernel takes at most %d" % (SCORE_MAX_DIMS, D, SCORE_MAX_NODES))
+    if isinstance(nodes, (tuple, list)):
+        if len(nodes) != 2:
+            raise ValueError("explicit nodes are a pair (theta [G, D], logw [G])")
+        theta = np.asarray(nodes[0], dtype=np.float64)
+        logw = np.asarray(nodes[1], dtype=np.float64).reshape(-1)
+        if theta.ndim == 1 and D == 1:
+            theta = theta[:, None]
+        if theta.ndim != 2 or theta.shape[1] != D or theta.shape[0] != logw.shape[0]:
+            raise ValueError("explicit nodes: theta must be [G, %d] and logw [G]" % D)
+        if not 1 <= theta.shape[0] <= SCORE_MAX_NODES:
+            raise ValueError("explicit nodes: 1 <= G <= %d" % SCORE_MAX_NODES)
+        if not (np.isfinite(theta).all() and np.isfinite(logw).all()):
+            raise ValueError("explicit nodes: theta and logw must be finite")
+        return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(logw, dtype=np.float32)
+    if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or nodes < 2:
+        raise ValueError("nodes must be an integer >= 2 (points per dimension) or a pair (theta, logw)")
+    if not (isinstance(span, (int, float, np.floating, np.integer)) and np.isfinite(span) and span > 0):
+        raise ValueError("span must be a positive finite number")
+    n = int(nodes)
+    if n ** D > SCORE_MAX_NODES:
+        raise ValueError("%d nodes in each of %d dimensions are %d grid points; the kernel takes at most %d" %
+                         (n, D, n ** D, SCORE_MAX_NODES))
+    p = np.linspace(-float(span), float(span), n)
+    theta = np.stack([m.reshape(-1) for m in np.meshgrid(*([p] * D), indexing="ij")], axis=1)
+    lw = -0.5 * (theta ** 2).sum(axis=1)
+    lw = lw - (lw.max() + np.log(np.exp(lw - lw.max()).sum()))
+    return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
 
 
 _ADAM_NOOP = {"weight_decay": 0, "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
@@ -539,6 +599,57 @@ class _EngineBase(object):
 
     def _phase(self, name):
         return _Phase(self.events, name)
+
+    # -- person scores on a grid of latent nodes (vx_grid_*; no reference counterpart) -------------
+    def score(self, y_u8=None, rows=None, **kw):
+        raise NotImplementedError("%s has no grid scores: its pattern prior depends on a continuous latent, on the other "
+                                  "persons of the batch, or it has no enumerated likelihood (IrtEngine with x_feature <= 3 and "
+                                  "CcdmEngine have them)" % type(self).__name__)
+
+    def _score_inputs(self, y_u8, rows, J):
+        """The responses a score call reads ([n][J] u8 on the device, the training responses by default) and its rows."""
+        if y_u8 is None:
+            y = self.y if self.y.shape[1] == J else self.y[:, :J].contiguous()      # (without the phantom items)
+        else:
+            y = torch.as_tensor(y_u8)
+            if y.dtype != torch.uint8 or y.dim() != 2:
+                raise ValueError("responses must be a uint8 matrix (0 / 1 / 255 = missing)")
+            if y.shape[1] != J:
+                raise ValueError("responses have %d items, the model has %d" % (y.shape[1], J))
+            y = y.to(self.dev).contiguous()
+        if y.shape[0] < 1:
+            raise ValueError("no persons to score")
+        if rows is not None:
+            rows = torch.as_tensor(rows).to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
+            if rows.numel() < 1:
+                raise ValueError("no persons to score")
+            if int(rows.min()) < 0 or int(rows.max()) >= y.shape[0]:
+                raise IndexError("rows must index the %d response rows" % y.shape[0])
+        return y, rows
+
+    def _grid_posterior(self, y, rows, J, theta, logw, fill_tables):
+        """Tables (fill_tables(img)) and the posterior kernel, in buffers of their own: nothing a step reads is touched."""
+        be = self.be
+        G, D = int(theta.shape[0]), int(theta.shape[1])
+        n = int(y.shape[0]) if rows is None else int(rows.numel())
+        img = torch.empty(be.grid_image_bytes(J, G), dtype=torch.uint8, device=self.dev)
+        fill_tables(img)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = {"loglik": torch.empty(n, **f32), "mean": torch.empty(n, D, **f32), "sd": torch.empty(n, D, **f32),
+               "node": torch.empty(n, dtype=torch.int32, device=self.dev)}
+        be.grid_posterior(y, rows, n, J, G, D, img, logw, theta, out["loglik"], out["mean"], out["sd"], out["node"])
+        return out
+
+    def marginal_loglik(self, y_u8=None, rows=None, **kw):
+        """sum_i log p(y_i) under the item parameters as they stand, summed on the device in a fixed order."""
+        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
+            raise NotImplementedError("marginal_loglik over a process group: score() gives the local shard's rows; the "
+                                      "cross-rank sum is not built")
+        ll = self.score(y_u8, rows, **kw)["loglik"]
+        out = torch.empty(1, dtype=torch.float32, device=self.dev)
+        ws = torch.empty(1024, dtype=torch.float32, device=self.dev)            # vx_sum_workspace_floats(); not the step's
+        self.be.sum_into(ll, int(ll.numel()), 1.0, out, ws)
+        return float(out.item())
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1425,6 +1536,29 @@ class IrtEngine(_EngineBase):
             return torch.tril(u, -1) + torch.diag_embed(torch.exp(diag))
         return u.clone()
 
+    def score(self, y_u8=None, rows=None, nodes=61, span=6.0):
+        """Person scores by quadrature over a grid (score_grid): for each scored row the posterior mean `eap` (n, D) and
+        standard deviation `psd` (n, D) of the latent under the N(0, I) prior and the item parameters as they stand, the
+        marginal log-likelihood `loglik` (n,) and the MAP grid node `node` (n,).  y_u8: responses to score ([n, item_size]
+        uint8, 255 = missing), by default the training responses; rows: indices into them.  Exact and deterministic, needs
+        no guide: new respondents are scored like training ones.  The model's own items and dimensions only -- phantom
+        items / dimensions of a padded engine are not in the tables.  x_feature <= 3 and nodes ** x_feature <= 1024."""
+        if self.D_model > SCORE_MAX_DIMS:
+            raise NotImplementedError("grid scores need x_feature <= %d (this model has %d): a tensor-product grid of n nodes "
+                                      "a dimension has n**D points" % (SCORE_MAX_DIMS, self.D_model))
+        theta_np, logw_np = score_grid(self.D_model, nodes, span)
+        J, Dm = self.J_items, self.D_model
+        y, rows = self._score_inputs(y_u8, rows, J)
+        theta, logw = torch.from_numpy(theta_np).to(self.dev), torch.from_numpy(logw_np).to(self.dev)
+        flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()          # noqa: E731  (the problem's own items)
+        a = self.unconstrained("a").contiguous() if self.model != "irt_1pl" else None
+        c = flat("c") if self.model in ("irt_3pl", "irt_4pl") else None
+        d = flat("d") if self.model == "irt_4pl" else None
+        cfg = self.be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
+        out = self._grid_posterior(y, rows, J, theta, logw,
+                                   lambda img: self.be.grid_table_irt(cfg, theta, int(theta.shape[0]), a, flat("b"), c, d, img))
+        return {"eap": out["mean"], "psd": out["sd"], "loglik": out["loglik"], "node": out["node"]}
+
     # -- one ELBO-gradient step ------------------------------------------------------------------
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, guide_grads=True):
         """Fills self.G (flat grads + loss slot) and per-person grads for ONE particle.
@@ -1805,6 +1939,22 @@ class CcdmEngine(_EngineBase):
 
     def param(self, name):
         return torch.sigmoid(self.unconstrained(name))
+
+    def score(self, y_u8=None, rows=None):
+        """Classification of each scored row under the uniform pattern prior (the clamped Categorical of the step) and the
+        item parameters as they stand: `attr_prob` (n, K) posterior mastery probabilities, `pattern` (n,) the most probable
+        pattern (bit k = attribute k), `loglik` (n,) the marginal log-likelihood.  y_u8 / rows as IrtEngine.score."""
+        K, J, C = self.K, self.J, 1 << self.K
+        y, rows = self._score_inputs(y_u8, rows, J)
+        bits = ((torch.arange(C, device=self.dev)[:, None] >> torch.arange(K, device=self.dev)[None, :]) & 1)
+        coord = bits.to(torch.float32).contiguous()
+        eps32 = float(np.finfo(np.float32).eps)
+        logw = torch.full((C,), 1.0 / C, dtype=torch.float32, device=self.dev).clamp(eps32, 1.0 - eps32).log()
+        cfg = self.be.hodina_cfg(K, J, 0, 1.0, 0, 0, 0)
+        out = self._grid_posterior(y, rows, J, coord, logw,
+                                   lambda img: self.be.grid_table_cdm(cfg, self.cdm == "dino", self.q, self.view("g"),
+                                                                      self.view("s"), img))
+        return {"attr_prob": out["mean"], "pattern": out["node"], "loglik": out["loglik"]}
 
     def _replayable(self, full):
         # VCCDM (vi.py:819-865; test.py:560,585,624: 100-1500 rows a step): no guide, no random numbers -- the pattern

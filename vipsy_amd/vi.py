@@ -194,6 +194,29 @@ class BasePsy(object):
     def _postfix(self):
         return {}
 
+    # -- after the fit: person scores and the marginal log-likelihood (no reference counterpart) -------------------------
+    def _score_data(self, data):
+        """`data` under the reference's contract (float with NaN = missing, or uint8), with the model's item count."""
+        if data is None:
+            return None
+        y = to_u8(data, self.device)
+        if y.dim() != 2 or int(y.shape[1]) != self.item_size:
+            raise ValueError("data must be [persons, %d items], got %s" % (self.item_size, tuple(y.shape)))
+        return y
+
+    def score(self, data=None, **kw):
+        """Exact grid posteriors of the persons in `data` (None: the training data; with a `group` this rank's shard) under
+        the item parameters as they stand -- VIRT / VaeIRT with x_feature <= 3: eap, psd, loglik, node (IrtEngine.score);
+        VCCDM: attr_prob, pattern, loglik (CcdmEngine.score).  The other classes refuse."""
+        return self.engine.score(self._score_data(data), **kw)
+
+    def marginal_loglik(self, data=None, **kw):
+        """The marginal log-likelihood of `data` (None: the training data), a Python float.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("marginal_loglik with a group of %d ranks: score() gives the local shard's rows; the "
+                                      "cross-rank sum is not built" % self.world)
+        return self.engine.marginal_loglik(self._score_data(data), **kw)
+
 
 class BaseIRT(BasePsy):
     """vi.py:536-656 (constructor kwargs identical: model, x_feature, share_cov, D, a_free, a0, b0)."""
