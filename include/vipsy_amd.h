@@ -444,6 +444,21 @@ int vx_grid_posterior(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[
                       float* loglik /*[nb]*/, float* mean /*[nb][D]*/, float* sd /*[nb][D]*/, int32_t* argmax /*[nb]*/,
                       void* hip_stream);
 
+/* ---- Expected counts from the grid posteriors (the Bock-Aitkin E-step; the per-item half of what vx_grid_posterior gives per
+ * person).  With p_i(g) = exp(logw[g] + ll[i][g] - loglik[i]), loglik being vx_grid_posterior's output for the same y, rows, nb,
+ * img and logw:
+ *     n1[j][g] = sum_i p_i(g) [y_ij == 1]      n0[j][g] = sum_i p_i(g) [y_ij == 0]      mass[g] = sum_i p_i(g)
+ * They are the gradient of sum_i loglik[i] with respect to the tables T1 / T0, the data of the empirical item characteristic
+ * curve and of the RMSD / MD item-fit statistics, and (mass) the estimated latent distribution.  A 255 cell adds the missing
+ * constant to ll and enters neither table, a 254 cell adds nothing anywhere; a person with no response adds their prior to mass.
+ * Two chained products on v_mfma_f32_32x32x16_f16 (p as an fp16 pair), nothing of size [nb][G] touches memory; the persons go
+ * to chunks whose slabs (workspace: vx_grid_counts_workspace_floats(nb, J, G) floats) are added in a fixed order, no atomics:
+ * the same call gives the same bits.  Limits as vx_grid_posterior: 1 <= J <= 1024, 1 <= G <= 1024, nb >= 1; VX_EINVAL beyond. */
+int64_t vx_grid_counts_workspace_floats(int64_t nb, int32_t J, int32_t G);
+int vx_grid_counts(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G,
+                   const void* img, const float* logw /*[G]*/, const float* loglik /*[nb]*/, float* n1 /*[J][G]*/,
+                   float* n0 /*[J][G]*/, float* mass /*[G]*/, float* workspace, void* hip_stream);
+
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,
                     void* hip_stream);

@@ -31,6 +31,7 @@
 #include "k_synth.hip"
 #include "k_vaeccdm.hip"
 #include "k_grid_post.hip"
+#include "k_grid_counts.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2182,6 +2183,42 @@ int vx_grid_posterior(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t
     else if (D == 4) { LAUNCH_GP(4); } else if (D <= 6) { LAUNCH_GP(6); } else if (D <= 8) { LAUNCH_GP(8); } else { LAUNCH_GP(10); }
 #undef LAUNCH_GP
     VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+// Expected counts from the grid posteriors (k_grid_counts.hip): one kernel over (node groups x person chunks), then the chunks'
+// slabs added in ascending order
+int64_t vx_grid_counts_workspace_floats(int64_t nb, int32_t J, int32_t G) {
+    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    const GcPlan p = gc_plan(nb, J, G);
+    return p.n_chunks * p.slab_len;
+}
+
+int vx_grid_counts(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, const void* img, const float* logw,
+                   const float* loglik, float* n1, float* n0, float* mass, float* workspace, void* hs) {
+    if (!y || !img || !aligned16(img) || !logw || !loglik || !n1 || !n0 || !mass || !workspace) return VX_EINVAL;
+    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    const GcPlan p = gc_plan(nb, J, G);
+    hipStream_t st = (hipStream_t)hs;
+    const uint4* im = (const uint4*)img;
+    const dim3 grid((unsigned)(p.n_groups * p.n_chunks));
+    int rc;
+#define LAUNCH_GC(ITV, NTGV)                                                                                          \
+    rc = set_lds(k_grid_counts<ITV, NTGV>, gc_lds_bytes<NTGV>());                                                     \
+    if (rc) return rc;                                                                                                \
+    hipLaunchKernelGGL((k_grid_counts<ITV, NTGV>), grid, dim3(GC_THREADS), gc_lds_bytes<NTGV>(), st, y, rows, nb, (int)J, (int)G, \
+                       im, logw, loglik, p.n_groups, p.rounds_per_chunk, workspace, p.slab_len)
+    if (p.it == 1) { LAUNCH_GC(1, 2); } else if (p.it == 2) { LAUNCH_GC(2, 2); } else { LAUNCH_GC(4, 1); }
+#undef LAUNCH_GC
+    VX_CHECK_LAUNCH();
+    const int64_t JG = (int64_t)J * G;
+    float* const outs[3] = {n1, n0, mass};
+    const int64_t offs[3] = {0, JG, 2 * JG}, lens[3] = {JG, JG, (int64_t)G};
+    for (int k = 0; k < 3; ++k) {
+        hipLaunchKernelGGL(k_reduce_slabs, dim3(grid_1d(lens[k], 64)), dim3(256), 0, st, workspace + offs[k], p.n_chunks,
+                           p.slab_len, lens[k], 1.0f, outs[k]);
+        VX_CHECK_LAUNCH();
+    }
     return VX_OK;
 }
 

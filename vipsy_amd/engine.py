@@ -240,6 +240,14 @@ class HipBackend(object):
                                       _hip.stream_ptr())
         _hip.check(rc, "vx_grid_table_cdm")
 
+    def grid_counts_workspace(self, nb, J, G):
+        return self._size("vx_grid_counts_workspace_floats", nb, J, G)
+
+    def grid_counts(self, y, rows, nb, J, G, img, logw, loglik, n1, n0, mass, ws):
+        rc = self.L.vx_grid_counts(_hip.ptr(y), _hip.ptr(rows), nb, J, G, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(loglik),
+                                   _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(mass), _hip.ptr(ws), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_counts")
+
     def grid_posterior(self, y, rows, nb, J, G, D, img, logw, coord, loglik, mean, sd, argmax):
         rc = self.L.vx_grid_posterior(_hip.ptr(y), _hip.ptr(rows), nb, J, G, D, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord),
                                       _hip.ptr(loglik), _hip.ptr(mean), _hip.ptr(sd), _hip.ptr(argmax), _hip.stream_ptr())
@@ -407,6 +415,34 @@ def score_grid(D, nodes=61, span=6.0):
     lw = -0.5 * (theta ** 2).sum(axis=1)
     lw = lw - (lw.max() + np.log(np.exp(lw - lw.max()).sum()))
     return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
+
+
+def grid_image_prob(img, J, G):
+    """P(y_j = 1 | node g), float32 [J][G], read back from the operand image of vx_grid_table_* (k_grid_post.hip: [node tile][item
+    chunk][T1 head, T1 low, T0 head, T0 low][64 lanes][8 fp16], lane = node % 32 + 32 * (item % 16 // 8), values T * 2^10): the
+    exponential of the very T1 the kernels multiply with, not a second evaluation of the response function."""
+    KC, NT = (J + 15) // 16, (G + 31) // 32
+    t = img.view(torch.float16).view(NT, KC, 4, 2, 32, 8)[:, :, 0:2].to(torch.float64)
+    t1 = (t[:, :, 0] + t[:, :, 1]) / 1024.0                                   # [node tile][item chunk][item half][node][item]
+    t1 = t1.permute(1, 2, 4, 0, 3).reshape(KC * 16, NT * 32)[:J, :G]
+    return torch.exp(t1).to(torch.float32).contiguous()
+
+
+def item_fit_stats(n1, n0, prob):
+    """Per-item fit from the expected counts, in float64 on the tables' device.  With n = n1 + n0, N_j = sum_g n[j][g] and every
+    sum over the nodes with n[j][g] > 0: n_obs = N_j (the persons who answered j), md = sum (n1 - n prob) / N_j, rmsd =
+    sqrt(sum (n1 - n prob)^2 / n / N_j), observed = n1 / n (NaN where n = 0).  An item nobody answered: NaN, NaN, n_obs 0."""
+    n1, n0, prob = n1.to(torch.float64), n0.to(torch.float64), prob.to(torch.float64)
+    n = n1 + n0
+    pos = n > 0
+    zero = torch.zeros_like(n)
+    n_obs = torch.where(pos, n, zero).sum(1)
+    safe = torch.where(pos, n, torch.ones_like(n))
+    resid = torch.where(pos, n1 - n * prob, zero)
+    md = resid.sum(1) / n_obs                                                 # 0 / 0 = NaN: nobody answered
+    rmsd = torch.sqrt((resid * resid / safe).sum(1) / n_obs)
+    observed = torch.where(pos, n1 / safe, torch.full_like(n, float("nan")))
+    return {"n_obs": n_obs, "md": md, "rmsd": rmsd, "observed": observed}
 
 
 _ADAM_NOOP = {"weight_decay": 0, "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
@@ -601,10 +637,27 @@ class _EngineBase(object):
         return _Phase(self.events, name)
 
     # -- person scores on a grid of latent nodes (vx_grid_*; no reference counterpart) -------------
-    def score(self, y_u8=None, rows=None, **kw):
+    def _no_grid(self):
         raise NotImplementedError("%s has no grid scores: its pattern prior depends on a continuous latent, on the other "
                                   "persons of the batch, or it has no enumerated likelihood (IrtEngine with x_feature <= 3 and "
                                   "CcdmEngine have them)" % type(self).__name__)
+
+    def score(self, y_u8=None, rows=None, **kw):
+        self._no_grid()
+
+    def expected_counts(self, y_u8=None, rows=None, **kw):
+        self._no_grid()
+
+    def item_fit(self, y_u8=None, rows=None, **kw):
+        """Per-item fit statistics of the scored rows (item_fit_stats over expected_counts): `n_obs`, `md`, `rmsd` [J] and
+        `observed` [J][G] as float64 device tensors, beside the `prob` [J][G] they are measured against.  One rank only."""
+        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
+            raise NotImplementedError("item_fit over a process group: expected_counts() gives the local shard's sums; the "
+                                      "cross-rank sum is not built")
+        c = self.expected_counts(y_u8, rows, **kw)
+        out = item_fit_stats(c["n1"], c["n0"], c["prob"])
+        out["prob"] = c["prob"]
+        return out
 
     def _score_inputs(self, y_u8, rows, J):
         """The responses a score call reads ([n][J] u8 on the device, the training responses by default) and its rows."""
@@ -638,6 +691,21 @@ class _EngineBase(object):
         out = {"loglik": torch.empty(n, **f32), "mean": torch.empty(n, D, **f32), "sd": torch.empty(n, D, **f32),
                "node": torch.empty(n, dtype=torch.int32, device=self.dev)}
         be.grid_posterior(y, rows, n, J, G, D, img, logw, theta, out["loglik"], out["mean"], out["sd"], out["node"])
+        out["img"] = img
+        return out
+
+    def _grid_counts(self, y, rows, J, theta, logw, fill_tables):
+        """The posterior kernel for loglik, then the counts kernel over the same image, in per-call buffers: n1, n0 [J][G],
+        mass [G] and prob [J][G] = P(y_j = 1 | node g) out of the image."""
+        be = self.be
+        post = self._grid_posterior(y, rows, J, theta, logw, fill_tables)
+        G = int(theta.shape[0])
+        n = int(post["loglik"].numel())
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = {"n1": torch.empty(J, G, **f32), "n0": torch.empty(J, G, **f32), "mass": torch.empty(G, **f32)}
+        ws = torch.empty(be.grid_counts_workspace(n, J, G), **f32)
+        be.grid_counts(y, rows, n, J, G, post["img"], logw, post["loglik"], out["n1"], out["n0"], out["mass"], ws)
+        out["prob"] = grid_image_prob(post["img"], J, G)
         return out
 
     def marginal_loglik(self, y_u8=None, rows=None, **kw):
@@ -1543,6 +1611,11 @@ class IrtEngine(_EngineBase):
         uint8, 255 = missing), by default the training responses; rows: indices into them.  Exact and deterministic, needs
         no guide: new respondents are scored like training ones.  The model's own items and dimensions only -- phantom
         items / dimensions of a padded engine are not in the tables.  x_feature <= 3 and nodes ** x_feature <= 1024."""
+        out = self._grid_posterior(*self._grid_call(y_u8, rows, nodes, span))
+        return {"eap": out["mean"], "psd": out["sd"], "loglik": out["loglik"], "node": out["node"]}
+
+    def _grid_call(self, y_u8, rows, nodes, span):
+        """What score() and expected_counts() hand to the grid kernels: (y, rows, J, theta, logw, fill_tables)."""
         if self.D_model > SCORE_MAX_DIMS:
             raise NotImplementedError("grid scores need x_feature <= %d (this model has %d): a tensor-product grid of n nodes "
                                       "a dimension has n**D points" % (SCORE_MAX_DIMS, self.D_model))
@@ -1555,9 +1628,18 @@ class IrtEngine(_EngineBase):
         c = flat("c") if self.model in ("irt_3pl", "irt_4pl") else None
         d = flat("d") if self.model == "irt_4pl" else None
         cfg = self.be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
-        out = self._grid_posterior(y, rows, J, theta, logw,
-                                   lambda img: self.be.grid_table_irt(cfg, theta, int(theta.shape[0]), a, flat("b"), c, d, img))
-        return {"eap": out["mean"], "psd": out["sd"], "loglik": out["loglik"], "node": out["node"]}
+        return (y, rows, J, theta, logw,
+                lambda img: self.be.grid_table_irt(cfg, theta, int(theta.shape[0]), a, flat("b"), c, d, img))
+
+    def expected_counts(self, y_u8=None, rows=None, nodes=61, span=6.0):
+        """The expected-count tables of the scored rows over the grid of score() (the Bock-Aitkin E-step): `n1`, `n0` [J][G] =
+        the posterior mass at node g of the persons who answered item j correctly / wrongly, `mass` [G] = the posterior mass
+        of all scored persons, `prob` [J][G] = P(y_j = 1 | node g) as the tables hold it, `theta` [G][D] and `logw` [G].
+        Inputs and refusals as score(); the model's own items only.  Deterministic: the same call gives the same bits."""
+        call = self._grid_call(y_u8, rows, nodes, span)
+        out = self._grid_counts(*call)
+        out["theta"], out["logw"] = call[3], call[4]
+        return out
 
     # -- one ELBO-gradient step ------------------------------------------------------------------
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, guide_grads=True):
@@ -1944,6 +2026,11 @@ class CcdmEngine(_EngineBase):
         """Classification of each scored row under the uniform pattern prior (the clamped Categorical of the step) and the
         item parameters as they stand: `attr_prob` (n, K) posterior mastery probabilities, `pattern` (n,) the most probable
         pattern (bit k = attribute k), `loglik` (n,) the marginal log-likelihood.  y_u8 / rows as IrtEngine.score."""
+        out = self._grid_posterior(*self._grid_call(y_u8, rows))
+        return {"attr_prob": out["mean"], "pattern": out["node"], "loglik": out["loglik"]}
+
+    def _grid_call(self, y_u8, rows):
+        """What score() and expected_counts() hand to the grid kernels: (y, rows, J, patterns, logw, fill_tables)."""
         K, J, C = self.K, self.J, 1 << self.K
         y, rows = self._score_inputs(y_u8, rows, J)
         bits = ((torch.arange(C, device=self.dev)[:, None] >> torch.arange(K, device=self.dev)[None, :]) & 1)
@@ -1951,10 +2038,16 @@ class CcdmEngine(_EngineBase):
         eps32 = float(np.finfo(np.float32).eps)
         logw = torch.full((C,), 1.0 / C, dtype=torch.float32, device=self.dev).clamp(eps32, 1.0 - eps32).log()
         cfg = self.be.hodina_cfg(K, J, 0, 1.0, 0, 0, 0)
-        out = self._grid_posterior(y, rows, J, coord, logw,
-                                   lambda img: self.be.grid_table_cdm(cfg, self.cdm == "dino", self.q, self.view("g"),
-                                                                      self.view("s"), img))
-        return {"attr_prob": out["mean"], "pattern": out["node"], "loglik": out["loglik"]}
+        return (y, rows, J, coord, logw,
+                lambda img: self.be.grid_table_cdm(cfg, self.cdm == "dino", self.q, self.view("g"), self.view("s"), img))
+
+    def expected_counts(self, y_u8=None, rows=None):
+        """The expected-count tables of the scored rows over the 2^K patterns (IrtEngine.expected_counts): `n1`, `n0` [J][2^K],
+        `mass` [2^K], `prob` [J][2^K] = P(y_j = 1 | pattern) and `patterns` [2^K][K], the attribute bits of every node."""
+        call = self._grid_call(y_u8, rows)
+        out = self._grid_counts(*call)
+        out["patterns"] = call[3]
+        return out
 
     def _replayable(self, full):
         # VCCDM (vi.py:819-865; test.py:560,585,624: 100-1500 rows a step): no guide, no random numbers -- the pattern

@@ -210,6 +210,22 @@ class BasePsy(object):
         VCCDM: attr_prob, pattern, loglik (CcdmEngine.score).  The other classes refuse."""
         return self.engine.score(self._score_data(data), **kw)
 
+    def expected_counts(self, data=None, **kw):
+        """The expected-count tables of the persons in `data` (None: the training data) over the grid of score(): device
+        tensors n1, n0 [items][nodes], mass [nodes], prob [items][nodes], and theta / logw (IRT) or patterns (VCCDM); see
+        IrtEngine.expected_counts / CcdmEngine.expected_counts.  With a `group` of more than one rank these are the sums over
+        THIS rank's shard only: add them across ranks yourself.  The classes without score() refuse."""
+        return self.engine.expected_counts(self._score_data(data), **kw)
+
+    def item_fit(self, data=None, **kw):
+        """Per-item fit of `data` (None: the training data) against the model as it stands, ready to print: a dict of numpy
+        arrays n_obs, md, rmsd [items] (the mean and root-mean-square deviation of the observed from the fitted item
+        characteristic curve, weighted by the posterior population), observed, prob [items][nodes].  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("item_fit with a group of %d ranks: expected_counts() gives the local shard's sums; the "
+                                      "cross-rank sum is not built" % self.world)
+        return {k: v.detach().cpu().numpy() for k, v in self.engine.item_fit(self._score_data(data), **kw).items()}
+
     def marginal_loglik(self, data=None, **kw):
         """The marginal log-likelihood of `data` (None: the training data), a Python float.  One rank only."""
         if self.world > 1:
