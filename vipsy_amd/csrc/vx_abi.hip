@@ -41,6 +41,7 @@
 #include <utility>
 #include <optional>
 #include <cstdio>
+#include <type_traits>
 
 namespace {
 
@@ -71,6 +72,15 @@ inline int set_lds_ptr(const void* kernel, size_t bytes) {
 }
 template <typename K>
 int set_lds(K kernel, size_t bytes) { return set_lds_ptr(reinterpret_cast<const void*>(kernel), bytes); }
+// one launch with dynamic LDS: the attribute, the launch, its status (a kernel's defaulted arguments are passed explicitly)
+template <typename K, typename... Args>
+int launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    const int rc = set_lds(kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
 
 inline int grid_1d(int64_t n, int block) {
     int64_t g = (n + block - 1) / block;
@@ -260,6 +270,31 @@ struct ForkScope {
     ~ForkScope() { (void)join(); }
 };
 
+// dm.Hp (32 / 64 / 96 / 128) as the compile-time hidden width HT = Hp / 32 of the shape-generic encoder kernels:
+// f(std::integral_constant<int, HT>) launches the instance and returns the call's status
+template <typename F>
+int with_hidden_width(int Hp, F&& f) {
+    switch (Hp) {
+        case 32: return f(std::integral_constant<int, 1>());
+        case 64: return f(std::integral_constant<int, 2>());
+        case 96: return f(std::integral_constant<int, 3>());
+        default: return f(std::integral_constant<int, 4>());
+    }
+}
+
+// A short last chip round BESIDE the whole rounds (the guide forward and the hidden gradient): with a side stream whose fork
+// succeeds, tail(side stream) is launched first -- its workgroups take their CUs at once, the whole rounds fill the rest, and
+// they cost their share of the chip's time instead of a round of their own -- then whole() on the launch stream, then the
+// join; otherwise whole(), then tail(launch stream).  The launch stream is joined on every error return too (the scope).
+template <typename Tail, typename Whole>
+int with_last_round(SideStream* side, hipStream_t st, Tail&& tail, Whole&& whole) {
+    ForkScope fork;
+    const bool beside = side && fork.fork(*side, st);
+    int rc = beside ? tail(fork.side()) : whole();
+    if (rc) return rc;
+    rc = beside ? whole() : tail(st);
+    return rc ? rc : fork.join();
+}
 }  // namespace
 
 extern "C" {
@@ -393,26 +428,8 @@ static int reduce_step_slabs(const float* slabs, int64_t n_slabs, int J, float* 
 
 int64_t vx_sum_workspace_floats(void) { return 1024; }
 
-int vx_sum(const float* v, int64_t n, float alpha, float* out, float* workspace, uint32_t* step_dev, void* hs) {
-    if (!v || !out || !workspace || n < 0) return VX_EINVAL;
-    int nblk = (int)((n + 4095) / 4096);
-    if (nblk < 1) nblk = 1;
-    if (nblk > 1024) nblk = 1024;
-    if (nblk == 1) {                                       // a small batch: one launch (k_sum_stage1's final form)
-        hipLaunchKernelGGL(k_sum_stage1, dim3(1), dim3(256), 0, (hipStream_t)hs, v, n, workspace, (const float*)nullptr, alpha, out,
-                           step_dev);
-        VX_CHECK_LAUNCH();
-        return VX_OK;
-    }
-    hipLaunchKernelGGL(k_sum_stage1, dim3(nblk), dim3(256), 0, (hipStream_t)hs, v, n, workspace, (const float*)nullptr);
-    VX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, (hipStream_t)hs, workspace, nblk, alpha, out, step_dev);
-    VX_CHECK_LAUNCH();
-    return VX_OK;
-}
-
-int vx_sum2(const float* v1, const float* v2, int64_t n, float alpha, float* out, float* workspace, uint32_t* step_dev, void* hs) {
-    if (!v1 || !v2 || !out || !workspace || n < 0) return VX_EINVAL;
+// the sum of v1 (+ v2, when given) in one launch (a small batch: k_sum_stage1's final form) or two
+static int sum_impl(const float* v1, const float* v2, int64_t n, float alpha, float* out, float* workspace, uint32_t* step_dev, void* hs) {
     int nblk = (int)((n + 4095) / 4096);
     if (nblk < 1) nblk = 1;
     if (nblk > 1024) nblk = 1024;
@@ -426,6 +443,16 @@ int vx_sum2(const float* v1, const float* v2, int64_t n, float alpha, float* out
     hipLaunchKernelGGL(k_sum_stage2, dim3(1), dim3(256), 0, (hipStream_t)hs, workspace, nblk, alpha, out, step_dev);
     VX_CHECK_LAUNCH();
     return VX_OK;
+}
+
+int vx_sum(const float* v, int64_t n, float alpha, float* out, float* workspace, uint32_t* step_dev, void* hs) {
+    if (!v || !out || !workspace || n < 0) return VX_EINVAL;
+    return sum_impl(v, nullptr, n, alpha, out, workspace, step_dev, hs);
+}
+
+int vx_sum2(const float* v1, const float* v2, int64_t n, float alpha, float* out, float* workspace, uint32_t* step_dev, void* hs) {
+    if (!v1 || !v2 || !out || !workspace || n < 0) return VX_EINVAL;
+    return sum_impl(v1, v2, n, alpha, out, workspace, step_dev, hs);
 }
 
 int vx_adam_step(float* p, const float* g, float* m, float* v, const float* free_mask, int64_t n,
@@ -513,8 +540,8 @@ static PackLayout pack_layout(const vx_irt_cfg* cfg) {
 
 // The plan of the guide's forward and backward calls for (cfg, nb): the kernels the shape allows, the grids and the layout of
 // the backward's workspace (vx_mvn_enc_bwd_workspace_floats).  Which kernels a call launches also depends on its pointers
-// (alignment, the optional buffers it passes, the gd_ready bits); the layout depends on (cfg, nb) and the seams alone, as the
-// size and offset queries do.  Workspace, float offsets:
+// (alignment, the optional buffers it passes, the gd_ready bits): bwd_route() resolves that into a BwdRoute before the first
+// launch; the layout depends on (cfg, nb) and the seams alone, as the size and offset queries do.  Workspace, float offsets:
 //   ghpre [nb][H] | weight-gradient slabs [n_prw_ws][lenw] | fc1 slabs [n_prf][lenf] | gdT [D][nb] + 4 | hs: two fp16 copies of
 //   hT [nb][64] | unit images of the hidden gradient | the step's operand maxima [8]
 // gdT exists with the dimension-major kernels (bwt), hs with the bf16 head weight gradient (bwb), the unit images with the
@@ -578,160 +605,175 @@ static int f1fast_ok(const vx_irt_cfg* cfg, const float* ghpre, const uint8_t* y
     return (!force_generic() && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(ghpre) && aligned16(y)) ? 1 : 0;
 }
 
-// The kernels of the forward (packed: the entry point below found the packed path usable).  The packed path on the f16x2
-// kernels (p.fwb) writes the likelihood's x image and the fp16 terms of hT itself; the entry point makes them behind the
-// other paths.  ring: the step's row indices, left in the pinned host ring for that path only.
-static int mvn_enc_forward_kernels(const vx_irt_cfg* cfg, const MvnPlan& p, bool packed, const uint8_t* y, const int64_t* rows,
-                                   int64_t nb, int64_t gid0, const float* W1, const float* b1, const float* W21, const float* b21,
-                                   const float* W22, const float* b22, const float* eps_in, float* h, float* x, float* eps,
-                                   float* ldT, float* ent, float* hT, float* epsT, float* packws, uint8_t* ximg, uint16_t* hs_out,
-                                   void* hs, const int64_t* ring) {
-    EncDims dm = make_enc_dims(cfg, nb);
-    const dim3 grid((unsigned)((nb + ENC_P - 1) / ENC_P));
-    int rc;
-    if (packed) {
+// fc1's weight gradient from person-major operands (k_fc1_bwd): slabs_f[n_prf][lenf].  A small batch (the reference's
+// B = 100: two person tiles) takes 128 items a workgroup instead of 512 -- four times the workgroups, a quarter of the MFMA
+// chain, the response words and the slab piece each
+static bool fc1_small_batch(int Hp, int n_jg, int n_prf) { return Hp == 64 && (int64_t)n_jg * n_prf * 16 <= num_cu(); }
+static int fc1_bwd_person_major(const EncDims& dm, bool small, int n_jg, int n_prf, const uint8_t* y, const int64_t* rows,
+                                const float* ghpre, float* slabs_f, int64_t lenf, int f1fast, hipStream_t st) {
+    const size_t lds = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
+    if (small)
+        return launch_lds(k_fc1_bwd<2, 1>, dim3((unsigned)((dm.J + 127) / 128), (unsigned)n_prf), dim3(ENC_THREADS), lds, st, dm, y, rows,
+                          ghpre, slabs_f, lenf, f1fast);
+    return with_hidden_width(dm.Hp, [&](auto ht) -> int {
+        return launch_lds(k_fc1_bwd<decltype(ht)::value>, dim3((unsigned)n_jg, (unsigned)n_prf), dim3(ENC_THREADS), lds, st, dm, y, rows,
+                          ghpre, slabs_f, lenf, f1fast);
+    });
+}
+
+// One call of the guide's forward: the entry point's arguments, the plan and what the entry point derived from them
+// (packed: the packed path is usable; ring: the step's row indices, left in the pinned host ring for the fused pack only).
+extern "C++" struct FwdCall {                               // (C++ linkage: it has a member template)
+    const vx_irt_cfg* cfg; MvnPlan p; EncDims dm; bool packed;
+    const uint8_t* y; const int64_t* rows; int64_t nb, gid0;
+    const float *W1, *b1, *W21, *b21, *W22, *b22, *eps_in;
+    float *h, *x, *eps, *ldT, *ent, *hT, *epsT, *packws;
+    uint8_t* ximg; uint16_t* hs_out; hipStream_t st; const int64_t* ring;
+    // one launch of an f16x2 forward kernel (k_mvn_fwd_b*.hip) on the images of fwd_pack_fused; more: the first person of a
+    // launch that is not the whole batch
+    template <typename K, typename... More>
+    int launch_b(K kernel, unsigned grid, unsigned threads, size_t lds, hipStream_t s, More... more) const {
         const PackLayout pk = pack_layout(cfg);
-        float* Wp = packws;
-        float* bp = packws + pk.bp;
-        uint32_t* gtab = (uint32_t*)(packws + pk.gtab);
-        float* WpT = packws + pk.wpT;
-        // the powers of two of the f16x2 operands (the backward kernels read them too: pack_scales below)
-        float* sc = packws + pk.sc;
-        if (!p.fwb) {
-            hipLaunchKernelGGL(k_pack_heads, dim3((unsigned)pk.Rp), dim3(64), 0, (hipStream_t)hs, (int)cfg->D, 64, W21, b21, W22, b22,
-                               Wp, bp, gtab, WpT);
-            VX_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(64), 0, (hipStream_t)hs, (uint32_t*)(packws + pk.maxw), 4);
-            hipLaunchKernelGGL(k_enc_scales_max, dim3(FB_SC_BLOCKS), dim3(256), 0, (hipStream_t)hs, (int)dm.D, (int)dm.J, W1, b1, W21,
-                               b21, W22, b22, sc);
-            hipLaunchKernelGGL(k_enc_scales, dim3(1), dim3(64), 0, (hipStream_t)hs, sc);
-            VX_CHECK_LAUNCH();
-        }
-        if (p.fwb) {
-            uint8_t* img = (uint8_t*)(packws + pk.img);
-            const int n_tiles = fb_tiles(dm.D);
-            uint32_t* gt2 = (uint32_t*)(packws + pk.gt2);
-            uint8_t* w1img = (uint8_t*)(packws + pk.w1img);
-            // every weight image of the step in two launches (k_pack_fused.hip).  The unit images of the hidden gradient are
-            // made here too when that kernel will run (p.hb_fw: the backward call then reads them from packws), and
-            // WpT only when a kernel of this step reads it (the fp32 hidden-gradient kernel)
-            const bool hb = p.hb_fw;
-            uint8_t* himg = hb ? (uint8_t*)(packws + pk.himg) : nullptr;
-            // with the f16x2 hidden gradient (hb) no kernel of the step reads the packed copy Wp / bp / WpT: stage 1 is the maxima
-            // alone and stage 2 takes the tile images from the parameters themselves (and writes gtab, which the head weight
-            // gradient reads)
-            const bool direct = hb;
-            const int n_row_blocks = direct ? 0 : (int)((pk.Rp + 3) / 4), n_w1 = (dm.J + 15) / 16;
-            hipLaunchKernelGGL(k_pack_stage1, dim3(n_row_blocks + FB_SC_BLOCKS + (ring ? 1 : 0)), dim3(256), 0, (hipStream_t)hs,
-                               (int)dm.D, (int)dm.J, W1, b1, W21, b21, W22, b22, Wp, bp, gtab, hb ? (float*)nullptr : WpT, sc, ring,
-                               (int64_t)cfg->rows_ring_stride, (int)cfg->rows_ring_slots, cfg->step_dev, const_cast<int64_t*>(rows),
-                               nb, n_row_blocks);
-            VX_CHECK_LAUNCH();
-            hipLaunchKernelGGL(k_pack_stage2, dim3(n_w1 + n_tiles + (hb ? hb_units(dm.D) : 0)), dim3(256), 0, (hipStream_t)hs,
-                               (int)dm.D, (int)dm.J, n_tiles, pk_off_total(dm.D) / 8, W1, W21, W22, (const float*)Wp, (const float*)bp,
-                               (const uint32_t*)gtab, sc, w1img, img, gt2, himg, direct ? b21 : (const float*)nullptr,
-                               direct ? b22 : (const float*)nullptr, direct ? gtab : (uint32_t*)nullptr);
-            VX_CHECK_LAUNCH();
-            const size_t ldsb = fb_lds_bytes(dm.D, dm.J);
-            if (nb <= FB_SPLIT_MAX) {
-                // small batch: one 32-person tile per workgroup, its four waves share the head tiles
-                ProfScope ps("k_mvn_enc_fwd_b", (hipStream_t)hs);
-                rc = set_lds(k_mvn_enc_fwd_b<true>, ldsb);
-                if (rc) return rc;
-                // (with an x image: whole 64-person tiles, the absent half gets its zero rows)
-                const unsigned gs = ximg ? (unsigned)(((nb + 63) / 64) * 2) : (unsigned)((nb + FB_WP - 1) / FB_WP);
-                hipLaunchKernelGGL(k_mvn_enc_fwd_b<true>, dim3(gs), dim3(FB_THREADS), ldsb,
-                                   (hipStream_t)hs, dm, y, rows, gid0, (const uint8_t*)w1img, b1, (const uint8_t*)img,
-                                   (const uint32_t*)gt2, (const float*)sc, eps_in, cfg->seed, cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent, hT, epsT, ximg, hs_out);
-                VX_CHECK_LAUNCH();
-                return VX_OK;
-            }
-            int64_t n_done = 0;                                     // persons taken by k_mvn_enc_fwd_b2
-            // large batch: k_mvn_fwd_b2.hip with ONE person set per wave -- 128-person workgroups, two of them on a CU (two
-            // waves per SIMD, out of step): 2.74 against 2.86-2.97 ms for the 64-persons-per-wave form on the same box
-            // (tools/fwd2_bench.hip).  A chip round is 65 536 persons either way: a last round that fills less than half the
-            // chip goes to the 128-person kernel of k_mvn_fwd_b.hip (1M persons: 15 full rounds + 16 960 persons)
-            constexpr int FNS = 1;
-            if (fb2_lds_bytes(dm.D, dm.J, FNS) <= 80 * 1024) {
-                const int64_t round2 = (int64_t)FB2_WAVES * 64 * num_cu();
-                const int64_t rem = nb % round2;
-                n_done = (rem > 0 && 2 * rem <= round2) ? nb - rem : nb;
-                n_done -= n_done % (FB2_WAVES * 64);            // whole 64-person tiles of the x image, whole workgroups
-            }
-            // the short last round runs on a second stream BESIDE the whole rounds (launched first: its workgroups take their
-            // CUs at once, the whole rounds fill the rest), not after them: its 133 workgroups then cost their share of the
-            // chip's time instead of a round of their own
-            ForkScope tail_fork;
-            auto launch_tail = [&](hipStream_t ts) -> int {
-                int r = set_lds(k_mvn_enc_fwd_b<false>, ldsb);
-                if (r) return r;
-                // (timed only when it runs alone: beside the whole rounds its bracket spans theirs)
-                ProfScope ps("k_mvn_enc_fwd_b", ts, nb - n_done, ts == (hipStream_t)hs);
-                const dim3 gridb((unsigned)((nb - n_done + FB_WAVES * FB_WP - 1) / (FB_WAVES * FB_WP)));
-                hipLaunchKernelGGL(k_mvn_enc_fwd_b<false>, gridb, dim3(FB_THREADS), ldsb, ts, dm, y, rows, gid0,
-                                   (const uint8_t*)w1img, b1, (const uint8_t*)img, (const uint32_t*)gt2, (const float*)sc, eps_in, cfg->seed,
-                                   cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent, hT, epsT, ximg, hs_out, n_done);
-                VX_CHECK_LAUNCH();
-                return VX_OK;
-            };
-            if (n_done > 0 && n_done < nb && p.side_streams && tail_fork.fork(side_stream(0, (hipStream_t)hs), (hipStream_t)hs)) {
-                rc = launch_tail(tail_fork.side());
-                if (rc) return rc;                                  // (the scope joins)
-            }
-            if (n_done > 0) {
-                // the head tiles through the workgroup's LDS ring where the shape allows it: a quarter of the L2 -> CU bytes
-                const bool tile_ring = seams().fwd_ring && fb2s_shape_ok((int)dm.D, (int)dm.J);
-                const size_t lds2 = tile_ring ? fb2s_lds_bytes((int)dm.D) : fb2_lds_bytes(dm.D, dm.J, FNS);
-                rc = tile_ring ? set_lds(k_mvn_enc_fwd_b2<FNS, true>, lds2) : set_lds(k_mvn_enc_fwd_b2<FNS, false>, lds2);
-                if (rc) return rc;
-                ProfScope ps("k_mvn_enc_fwd_b2", (hipStream_t)hs, n_done);
-                const int wg = FB2_WAVES * 32 * FNS;
-                const dim3 grid2((unsigned)((n_done + wg - 1) / wg));                                             // the grid stops at n_done
-#define LAUNCH_FWD_B2(SH)                                                                                                          \
-    hipLaunchKernelGGL((k_mvn_enc_fwd_b2<FNS, SH>), grid2, dim3(FB2_THREADS), lds2, (hipStream_t)hs, dm, y, rows, gid0,          \
-                       (const uint8_t*)w1img, b1, (const uint8_t*)img, (const uint32_t*)gt2, (const float*)sc, eps_in, cfg->seed, \
-                       cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent, hT, epsT, ximg, hs_out)
-                if (tile_ring) { LAUNCH_FWD_B2(true); } else { LAUNCH_FWD_B2(false); }
-#undef LAUNCH_FWD_B2
-                VX_CHECK_LAUNCH();
-                if (n_done == nb) return VX_OK;
-            }
-            if (tail_fork.active()) return tail_fork.join();
-            return launch_tail((hipStream_t)hs);
-        }
-        const size_t ldsp = enc_p_lds_floats(dm.D, dm.J) * sizeof(float);
-        rc = set_lds(k_mvn_enc_fwd_p, ldsp);
-        if (rc) return rc;
-        const dim3 gridp((unsigned)((nb + EP_WAVES * EP_WP - 1) / (EP_WAVES * EP_WP)));
-        ProfScope ps("k_mvn_enc_fwd_p", (hipStream_t)hs);
-        hipLaunchKernelGGL(k_mvn_enc_fwd_p, gridp, dim3(EP_THREADS), ldsp, (hipStream_t)hs, dm, y, rows, gid0, W1, b1, Wp,
-                           bp, gtab, eps_in, cfg->seed, cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent, hT, epsT);
-        VX_CHECK_LAUNCH();
-        return VX_OK;
+        return launch_lds(kernel, dim3(grid), dim3(threads), lds, s, dm, y, rows, gid0, (const uint8_t*)(packws + pk.w1img), b1,
+                          (const uint8_t*)(packws + pk.img), (const uint32_t*)(packws + pk.gt2), (const float*)(packws + pk.sc), eps_in,
+                          cfg->seed, cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent, hT, epsT, ximg, hs_out, more...);
     }
-    if (!force_generic() && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(y) && aligned16(W1) && aligned16(b1) &&
-        aligned16(W21) && aligned16(W22) && aligned16(h)) {
-        const size_t ldsr = enc_r_lds_floats(dm.D, dm.J) * sizeof(float);
-        if (ldsr <= 160 * 1024) {
-            rc = set_lds(k_mvn_enc_fwd_r, ldsr);
-            if (rc) return rc;
-            const dim3 gridr((unsigned)((nb + ER_WAVES * ER_WP - 1) / (ER_WAVES * ER_WP)));
-            hipLaunchKernelGGL(k_mvn_enc_fwd_r, gridr, dim3(ER_THREADS), ldsr, (hipStream_t)hs, dm, y, rows, gid0, W1, b1,
-                               W21, b21, W22, b22, eps_in, cfg->seed, cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent);
-            VX_CHECK_LAUNCH();
-            return VX_OK;
-        }
-    }
-    const size_t lds = enc_fwd_lds_floats(dm.D, dm.Hp) * sizeof(float);
-#define LAUNCH_FWD(HT)                                                                                       \
-    rc = set_lds(k_mvn_enc_fwd<HT>, lds);                                                                    \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_mvn_enc_fwd<HT>, grid, dim3(ENC_THREADS), lds, (hipStream_t)hs, dm, y, rows, gid0, W1, \
-                       b1, W21, b21, W22, b22, eps_in, cfg->seed, cfg->step, cfg->step_dev, cfg->stream, h, x, eps, ldT, ent)
-    if (dm.Hp == 32) { LAUNCH_FWD(1); } else if (dm.Hp == 64) { LAUNCH_FWD(2); } else if (dm.Hp == 96) { LAUNCH_FWD(3); } else { LAUNCH_FWD(4); }
-#undef LAUNCH_FWD
+};
+
+// the packed copy of the heads and the powers of two of the f16x2 operands (the backward kernels read them too), for the
+// packed fp32 forward
+static int fwd_pack_heads(const FwdCall& c) {
+    const PackLayout pk = pack_layout(c.cfg);
+    float* sc = c.packws + pk.sc;
+    hipLaunchKernelGGL(k_pack_heads, dim3((unsigned)pk.Rp), dim3(64), 0, c.st, (int)c.cfg->D, 64, c.W21, c.b21, c.W22, c.b22,
+                       c.packws, c.packws + pk.bp, (uint32_t*)(c.packws + pk.gtab), c.packws + pk.wpT);
+    VX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(64), 0, c.st, (uint32_t*)(c.packws + pk.maxw), 4);
+    hipLaunchKernelGGL(k_enc_scales_max, dim3(FB_SC_BLOCKS), dim3(256), 0, c.st, (int)c.dm.D, (int)c.dm.J, c.W1, c.b1, c.W21,
+                       c.b21, c.W22, c.b22, sc);
+    hipLaunchKernelGGL(k_enc_scales, dim3(1), dim3(64), 0, c.st, sc);
     VX_CHECK_LAUNCH();
     return VX_OK;
+}
+
+// every weight image of the step in two launches (k_pack_fused.hip), for the f16x2 forward.  The unit images of the hidden
+// gradient are made here too when that kernel will run (p.hb_fw: the backward call then reads them from packws), and WpT
+// only when a kernel of this step reads it (the fp32 hidden-gradient kernel)
+static int fwd_pack_fused(const FwdCall& c) {
+    const PackLayout pk = pack_layout(c.cfg);
+    const EncDims& dm = c.dm;
+    float *Wp = c.packws, *bp = c.packws + pk.bp, *sc = c.packws + pk.sc;
+    uint32_t* gtab = (uint32_t*)(c.packws + pk.gtab);
+    const int n_tiles = fb_tiles(dm.D);
+    // with the f16x2 hidden gradient (hb) no kernel of the step reads the packed copy Wp / bp / WpT: stage 1 is the maxima
+    // alone and stage 2 takes the tile images from the parameters themselves (direct; and writes gtab, which the head weight
+    // gradient reads)
+    const bool hb = c.p.hb_fw, direct = hb;
+    uint8_t* himg = hb ? (uint8_t*)(c.packws + pk.himg) : nullptr;
+    const int n_row_blocks = direct ? 0 : (int)((pk.Rp + 3) / 4), n_w1 = (dm.J + 15) / 16;
+    hipLaunchKernelGGL(k_pack_stage1, dim3(n_row_blocks + FB_SC_BLOCKS + (c.ring ? 1 : 0)), dim3(256), 0, c.st,
+                       (int)dm.D, (int)dm.J, c.W1, c.b1, c.W21, c.b21, c.W22, c.b22, Wp, bp, gtab, hb ? (float*)nullptr : c.packws + pk.wpT,
+                       sc, c.ring, (int64_t)c.cfg->rows_ring_stride, (int)c.cfg->rows_ring_slots, c.cfg->step_dev,
+                       const_cast<int64_t*>(c.rows), c.nb, n_row_blocks);
+    VX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_pack_stage2, dim3(n_w1 + n_tiles + (hb ? hb_units(dm.D) : 0)), dim3(256), 0, c.st,
+                       (int)dm.D, (int)dm.J, n_tiles, pk_off_total(dm.D) / 8, c.W1, c.W21, c.W22, (const float*)Wp, (const float*)bp,
+                       (const uint32_t*)gtab, sc, (uint8_t*)(c.packws + pk.w1img), (uint8_t*)(c.packws + pk.img),
+                       (uint32_t*)(c.packws + pk.gt2), himg, direct ? c.b21 : (const float*)nullptr,
+                       direct ? c.b22 : (const float*)nullptr, direct ? gtab : (uint32_t*)nullptr);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+// packed f16x2, small batch: one 32-person tile per workgroup, its four waves share the head tiles
+static int fwd_b_small(const FwdCall& c) {
+    ProfScope ps("k_mvn_enc_fwd_b", c.st);
+    // (with an x image: whole 64-person tiles, the absent half gets its zero rows)
+    const unsigned gs = c.ximg ? (unsigned)(((c.nb + 63) / 64) * 2) : (unsigned)((c.nb + FB_WP - 1) / FB_WP);
+    return c.launch_b(k_mvn_enc_fwd_b<true>, gs, FB_THREADS, fb_lds_bytes(c.dm.D, c.dm.J), c.st, (int64_t)0);
+}
+
+// packed f16x2, large batch: k_mvn_fwd_b2.hip with ONE person set per wave -- 128-person workgroups, two of them on a CU (two
+// waves per SIMD, out of step): 2.74 against 2.86-2.97 ms for the 64-persons-per-wave form on the same box
+// (tools/fwd2_bench.hip).  A chip round is 65 536 persons either way: a last round that fills less than half the chip goes
+// to the 128-person kernel of k_mvn_fwd_b.hip (1M persons: 15 full rounds + 16 960 persons), beside the whole rounds
+static int fwd_b_large(const FwdCall& c) {
+    const EncDims& dm = c.dm;
+    const int64_t nb = c.nb;
+    const size_t ldsb = fb_lds_bytes(dm.D, dm.J);
+    constexpr int FNS = 1;
+    int64_t n_done = 0;                                     // persons taken by k_mvn_enc_fwd_b2
+    if (fb2_lds_bytes(dm.D, dm.J, FNS) <= 80 * 1024) {
+        const int64_t round2 = (int64_t)FB2_WAVES * 64 * num_cu();
+        const int64_t rem = nb % round2;
+        n_done = (rem > 0 && 2 * rem <= round2) ? nb - rem : nb;
+        n_done -= n_done % (FB2_WAVES * 64);            // whole 64-person tiles of the x image, whole workgroups
+    }
+    auto last_round = [&](hipStream_t ts) -> int {
+        // (timed only when it runs alone: beside the whole rounds its bracket spans theirs)
+        ProfScope ps("k_mvn_enc_fwd_b", ts, nb - n_done, ts == c.st);
+        return c.launch_b(k_mvn_enc_fwd_b<false>, (unsigned)((nb - n_done + FB_WAVES * FB_WP - 1) / (FB_WAVES * FB_WP)), FB_THREADS,
+                          ldsb, ts, n_done);
+    };
+    auto whole_rounds = [&]() -> int {
+        // the head tiles through the workgroup's LDS ring where the shape allows it: a quarter of the L2 -> CU bytes
+        const bool tile_ring = seams().fwd_ring && fb2s_shape_ok((int)dm.D, (int)dm.J);
+        const size_t lds2 = tile_ring ? fb2s_lds_bytes((int)dm.D) : fb2_lds_bytes(dm.D, dm.J, FNS);
+        ProfScope ps("k_mvn_enc_fwd_b2", c.st, n_done);
+        const int wg = FB2_WAVES * 32 * FNS;
+        const unsigned grid2 = (unsigned)((n_done + wg - 1) / wg);                                          // the grid stops at n_done
+        return tile_ring ? c.launch_b(k_mvn_enc_fwd_b2<FNS, true>, grid2, FB2_THREADS, lds2, c.st)
+                         : c.launch_b(k_mvn_enc_fwd_b2<FNS, false>, grid2, FB2_THREADS, lds2, c.st);
+    };
+    if (n_done == 0) return last_round(c.st);
+    if (n_done == nb) return whole_rounds();
+    return with_last_round(c.p.side_streams ? &side_stream(0, c.st) : nullptr, c.st, last_round, whole_rounds);
+}
+
+// packed fp32 (k_mvn_packed.hip)
+static int fwd_p(const FwdCall& c) {
+    const PackLayout pk = pack_layout(c.cfg);
+    ProfScope ps("k_mvn_enc_fwd_p", c.st);
+    return launch_lds(k_mvn_enc_fwd_p, dim3((unsigned)((c.nb + EP_WAVES * EP_WP - 1) / (EP_WAVES * EP_WP))), dim3(EP_THREADS),
+                      enc_p_lds_floats(c.dm.D, c.dm.J) * sizeof(float), c.st, c.dm, c.y, c.rows, c.gid0, c.W1, c.b1, c.packws,
+                      c.packws + pk.bp, (uint32_t*)(c.packws + pk.gtab), c.eps_in, c.cfg->seed, c.cfg->step, c.cfg->step_dev,
+                      c.cfg->stream, c.h, c.x, c.eps, c.ldT, c.ent, c.hT, c.epsT);
+}
+
+// unpacked, register-resident (k_mvn_enc_r.hip): H = 64, 16-byte loads
+static bool fwd_r_ok(const FwdCall& c) {
+    return !force_generic() && c.cfg->H == 64 && c.cfg->J % 4 == 0 && aligned16(c.y) && aligned16(c.W1) && aligned16(c.b1) &&
+           aligned16(c.W21) && aligned16(c.W22) && aligned16(c.h) && enc_r_lds_floats(c.dm.D, c.dm.J) * sizeof(float) <= 160 * 1024;
+}
+static int fwd_r(const FwdCall& c) {
+    return launch_lds(k_mvn_enc_fwd_r, dim3((unsigned)((c.nb + ER_WAVES * ER_WP - 1) / (ER_WAVES * ER_WP))), dim3(ER_THREADS),
+                      enc_r_lds_floats(c.dm.D, c.dm.J) * sizeof(float), c.st, c.dm, c.y, c.rows, c.gid0, c.W1, c.b1, c.W21, c.b21,
+                      c.W22, c.b22, c.eps_in, c.cfg->seed, c.cfg->step, c.cfg->step_dev, c.cfg->stream, c.h, c.x, c.eps, c.ldT, c.ent);
+}
+
+// shape-generic (k_mvn_enc.hip)
+static int fwd_generic(const FwdCall& c) {
+    return with_hidden_width(c.dm.Hp, [&](auto ht) -> int {
+        return launch_lds(k_mvn_enc_fwd<decltype(ht)::value>, dim3((unsigned)((c.nb + ENC_P - 1) / ENC_P)), dim3(ENC_THREADS),
+                          enc_fwd_lds_floats(c.dm.D, c.dm.Hp) * sizeof(float), c.st, c.dm, c.y, c.rows, c.gid0, c.W1, c.b1, c.W21,
+                          c.b21, c.W22, c.b22, c.eps_in, c.cfg->seed, c.cfg->step, c.cfg->step_dev, c.cfg->stream, c.h, c.x, c.eps,
+                          c.ldT, c.ent);
+    });
+}
+
+// The kernels of the forward, chosen once.  The packed path on the f16x2 kernels (p.fwb) writes the likelihood's x image and
+// the fp16 terms of hT itself; the entry point makes them behind the other paths.
+static int mvn_enc_forward_kernels(const FwdCall& c) {
+    if (c.packed && c.p.fwb) {
+        const int rc = fwd_pack_fused(c);
+        if (rc) return rc;
+        return c.nb <= FB_SPLIT_MAX ? fwd_b_small(c) : fwd_b_large(c);
+    }
+    if (c.packed) {
+        const int rc = fwd_pack_heads(c);
+        return rc ? rc : fwd_p(c);
+    }
+    return fwd_r_ok(c) ? fwd_r(c) : fwd_generic(c);
 }
 
 int vx_mvn_enc_forward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, int64_t gid0,
@@ -769,8 +811,9 @@ int vx_mvn_enc_forward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* r
             ring = nullptr;
         }
     }
-    const int rc = mvn_enc_forward_kernels(cfg, p, packed, y, rows, nb, gid0, W1, b1, W21, b21, W22, b22, eps_in, h, x, eps, ldT,
-                                           ent, hT, epsT, packws, ximg, hs_out, hs, ring);
+    const FwdCall c{cfg, p, make_enc_dims(cfg, nb), packed, y, rows, nb, gid0, W1, b1, W21, b21, W22, b22, eps_in, h, x, eps, ldT,
+                    ent, hT, epsT, packws, ximg, hs_out, (hipStream_t)hs, ring};
+    const int rc = mvn_enc_forward_kernels(c);
     if (rc) return rc;                                               // nothing is launched on buffers an error left unwritten
     if (ximg && !fused) {
         hipLaunchKernelGGL(k_lik_ximg_h, dim3((unsigned)((nb + LB_P - 1) / LB_P)), dim3(256), 0, (hipStream_t)hs, (int)cfg->D, nb,
@@ -863,113 +906,123 @@ int64_t vx_irt_lik_workspace_floats(const vx_irt_cfg* cfg, int64_t nb) {
     return lik_plan(cfg, nb).total;
 }
 
-// The kernels of vx_irt_lik_grad (arguments validated by the entry point below); gd_done: the path wrote gdT itself.
-static int irt_lik_grad_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* x,
-                                const float* a, const float* b, const float* c_un, const float* d_un, float* gx, float* gxT,
-                                float* ll, float* gitem, float* workspace, const uint8_t* yT, int64_t yT_stride,
-                                const uint8_t* ximg_in, const float* epsT, const float* ldT, float* gdT, uint32_t* opmax, void* hs,
-                                bool& gd_done) {
-    const LikPlan p = lik_plan(cfg, nb);
-    const int64_t n_ptiles = p.n_ptiles, nbp = p.nbp;
-    if (p.b && !rows && yT && gxT && yT_stride % 64 == 0 && yT_stride >= nbp && aligned16(yT) && nb > 0 && aligned16(workspace) &&
-        aligned16(gxT)) {
-        const int groups = p.b_groups, n_pr = p.b_n_pr;
-        LikBDims dm;
-        dm.D = cfg->D; dm.J = cfg->J; dm.model = cfg->model; dm.groups = groups; dm.n_pr = n_pr; dm.gxt = 1;
-        dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
-        dm.slab_len = p.slab_len;
-        float* slabs = workspace;
-        uint8_t* ximg_ws = (uint8_t*)(workspace + p.b_ximg);
-        float* gx_part = workspace + p.b_gx_part;
-        // 1PL / 2PL link: the f16x2 kernel and its image (the forward's, or made here); its gx stores address 16 nbp bytes
-        // with 32 bits.  3PL / 4PL: the bf16x3 kernel on its own three-term image (the forward writes none for them).
-        const bool f16 = p.h && nbp < ((int64_t)1 << 27);
-        const uint8_t* ximg = (f16 && ximg_in && aligned16(ximg_in)) ? ximg_in : ximg_ws;
-        float* ll_part = workspace + p.b_ll_part;
-        // the overflow word of the f16 image: behind the forward's image, or -- an image made here -- at the end of the workspace
-        uint32_t* ovf = (ximg == ximg_ws) ? (uint32_t*)(workspace + p.b_ovf)
-                                          : (uint32_t*)(const_cast<uint8_t*>(ximg_in) + lik_ximg_ovf_bytes(nb));
-        hipStream_t st = (hipStream_t)hs;
+// One call of vx_irt_lik_grad (arguments validated by the entry point below) and its plan
+struct LikCall {
+    const vx_irt_cfg* cfg; LikPlan p;
+    const uint8_t* y; const int64_t* rows; int64_t nb;
+    const float *x, *a, *b, *c_un, *d_un;
+    float *gx, *gxT, *ll, *gitem, *workspace;
+    const uint8_t* yT; int64_t yT_stride; const uint8_t* ximg_in;
+    const float *epsT, *ldT; float* gdT; uint32_t* opmax; hipStream_t st;
+};
+// what a path returns: the call's status, and whether the path wrote gdT (and the operand maxima) itself
+struct LikDone { int rc; bool gd_done; LikDone(int r, bool gd = false) : rc(r), gd_done(gd) {} };
+
+// the bf16x3 / f16x2 kernels (k_irt_lik_b.hip, k_irt_lik_h.hip): a full batch whose item-major responses came
+static bool lik_b_ok(const LikCall& c) {
+    return c.p.b && !c.rows && c.yT && c.gxT && c.yT_stride % 64 == 0 && c.yT_stride >= c.p.nbp && aligned16(c.yT) && c.nb > 0 &&
+           aligned16(c.workspace) && aligned16(c.gxT);
+}
+static LikDone lik_grad_b(const LikCall& c) {
+    const vx_irt_cfg* cfg = c.cfg; const LikPlan& p = c.p;
+    const int64_t nb = c.nb, n_ptiles = p.n_ptiles, nbp = p.nbp;
+    const int groups = p.b_groups, n_pr = p.b_n_pr;
+    LikBDims dm;
+    dm.D = cfg->D; dm.J = cfg->J; dm.model = cfg->model; dm.groups = groups; dm.n_pr = n_pr; dm.gxt = 1;
+    dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
+    dm.slab_len = p.slab_len;
+    float* slabs = c.workspace;
+    uint8_t* ximg_ws = (uint8_t*)(c.workspace + p.b_ximg);
+    float* gx_part = c.workspace + p.b_gx_part;
+    // 1PL / 2PL link: the f16x2 kernel and its image (the forward's, or made here); its gx stores address 16 nbp bytes
+    // with 32 bits.  3PL / 4PL: the bf16x3 kernel on its own three-term image (the forward writes none for them).
+    const bool f16 = p.h && nbp < ((int64_t)1 << 27);
+    const uint8_t* ximg = (f16 && c.ximg_in && aligned16(c.ximg_in)) ? c.ximg_in : ximg_ws;
+    float* ll_part = c.workspace + p.b_ll_part;
+    // the overflow word of the f16 image: behind the forward's image, or -- an image made here -- at the end of the workspace
+    uint32_t* ovf = (ximg == ximg_ws) ? (uint32_t*)(c.workspace + p.b_ovf)
+                                      : (uint32_t*)(const_cast<uint8_t*>(c.ximg_in) + lik_ximg_ovf_bytes(nb));
+    hipStream_t st = c.st;
+    hipError_t he = hipMemsetAsync(slabs, 0, sizeof(float) * (size_t)n_pr * dm.slab_len, st);
+    if (he != hipSuccess) return (int)he;
+    if (ximg == ximg_ws) {
+        if (f16) {
+            if (hipMemsetAsync(ovf, 0, sizeof(uint32_t), st) != hipSuccess) return VX_EINVAL;
+            hipLaunchKernelGGL(k_lik_ximg_h, dim3((unsigned)n_ptiles), dim3(256), 0, st, (int)cfg->D, nb, c.x, ximg_ws, ovf);
+        } else {
+            hipLaunchKernelGGL(k_lik_ximg, dim3((unsigned)n_ptiles), dim3(256), 0, st, (int)cfg->D, nb, c.x, ximg_ws, (const uint32_t*)nullptr);
+        }
+        VX_CHECK_LAUNCH();
+    }
+    int rc;
+    const dim3 grid((unsigned)(groups * n_pr));
+    if (f16) {
+        rc = set_lds(k_irt_lik_h<0>, LH_LDS_BYTES);
+        if (rc) return rc;
+        ProfScope ps("k_irt_lik_h", st);
+        hipLaunchKernelGGL((k_irt_lik_h<0>), grid, dim3(LH_THREADS), LH_LDS_BYTES, st, dm, c.yT, c.yT_stride, ximg, c.a, c.b,
+                           gx_part, ll_part, slabs, (const uint32_t*)ovf);
+        VX_CHECK_LAUNCH();
+        // the stand-by for a latent outside the f16 image's range (|x| >= 511.75): the bf16x3 kernel on its own image, both
+        // returning at once unless the overflow word is set -- two empty launches a step otherwise.  Its image takes the
+        // workspace's image region (an f16 image made here is dead by then; the overflow word is not in that region).
+        rc = set_lds(k_irt_lik_b<0>, LB_LDS_BYTES);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_lik_ximg, dim3((unsigned)(n_ptiles < 4 * num_cu() ? n_ptiles : 4 * num_cu())), dim3(256), 0, st, (int)cfg->D,
+                           nb, c.x, ximg_ws, (const uint32_t*)ovf);
+        hipLaunchKernelGGL((k_irt_lik_b<0>), grid, dim3(LB_THREADS), LB_LDS_BYTES, st, dm, c.yT, c.yT_stride, (const uint8_t*)ximg_ws,
+                           c.a, c.b, c.c_un, c.d_un, gx_part, ll_part, slabs, (long long*)nullptr, (const uint32_t*)ovf);
+    } else {
+        const auto kernel = cfg->model >= VX_IRT_3PL ? k_irt_lik_b<1> : k_irt_lik_b<0>;
+        rc = set_lds(kernel, LB_LDS_BYTES);
+        if (rc) return rc;
+        ProfScope ps("k_irt_lik_b", st);
+        hipLaunchKernelGGL(kernel, grid, dim3(LB_THREADS), LB_LDS_BYTES, st, dm, c.yT, c.yT_stride, ximg, c.a, c.b, c.c_un, c.d_un,
+                           gx_part, ll_part, slabs, (long long*)nullptr, (const uint32_t*)nullptr);
+    }
+    VX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lik_reduce_parts, dim3((unsigned)n_ptiles), dim3(256), (size_t)64 * (cfg->D | 1) * sizeof(float), st, (const float*)gx_part, (const float*)ll_part,
+                       c.x, groups, (int)cfg->D, nb, nbp, cfg->scale, c.gxT, c.ll, c.epsT, c.ldT, c.gdT, c.opmax);
+    VX_CHECK_LAUNCH();
+    if (c.gx) {                                        // both orders requested: gx[nb][D] = transpose(gxT[D][nb])
+        hipLaunchKernelGGL(k_transpose, dim3(num_cu() * 8), dim3(256), 0, st, c.gxT, c.gx, (int64_t)cfg->D, nb);
+        VX_CHECK_LAUNCH();
+    }
+    return LikDone(vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, c.gitem, (void*)st), true);
+}
+
+// the register-resident kernel (k_irt_lik_r.hip)
+static LikDone lik_grad_r(const LikCall& c) {
+    const vx_irt_cfg* cfg = c.cfg; const LikPlan& p = c.p;
+    const int64_t nb = c.nb;
+    const int groups = p.groups, n_pr = p.n_pr;
+    const uint8_t* y = c.y; const int64_t* rows = c.rows; const float *x = c.x, *a = c.a, *b = c.b, *c_un = c.c_un, *d_un = c.d_un;
+    float *gx = c.gx, *gxT = c.gxT;
+    LikRDims dm;
+    dm.D = cfg->D; dm.J = cfg->J; dm.K8 = (cfg->D + 8) & ~7; dm.model = cfg->model;
+    { const int nq = dm.K8 >> 3; dm.XS = 8 * (nq <= 13 ? 13 : 16) + 4; }
+    dm.groups = groups; dm.n_pr = n_pr; dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
+    dm.slab_len = p.slab_len;
+    dm.fast = (cfg->D % 4 == 0 && cfg->J % 4 == 0 && cfg->J >= 8 && aligned16(x) && aligned16(y) &&
+               aligned16(gx) && aligned16(c.workspace)) ? 1 : 0;
+    dm.gxt = gxT ? 1 : 0;                              // partials (and their sum) dimension-major
+    float* slabs = c.workspace;
+    float* gx_sum = gxT ? gxT : gx;
+    float* gx_part = groups > 1 ? c.workspace + p.gx_part : gx_sum;
+    float* ll_part = groups > 1 ? c.workspace + p.ll_part : c.ll;
+    hipStream_t st = c.st;
+    // several item chunks and dimension-major partials: ONE finishing launch sums the partials, makes the DIAG-row operand
+    // and reduces the item slabs (k_lik_finish); otherwise the slabs are cleared and reduced as before
+    const bool finish1 = nb > 0 && groups > 1 && !(gxT && gx);
+    if (!finish1) {
         hipError_t he = hipMemsetAsync(slabs, 0, sizeof(float) * (size_t)n_pr * dm.slab_len, st);
         if (he != hipSuccess) return (int)he;
-        if (ximg == ximg_ws) {
-            if (f16) {
-                if (hipMemsetAsync(ovf, 0, sizeof(uint32_t), st) != hipSuccess) return VX_EINVAL;
-                hipLaunchKernelGGL(k_lik_ximg_h, dim3((unsigned)n_ptiles), dim3(256), 0, st, (int)cfg->D, nb, x, ximg_ws, ovf);
-            } else {
-                hipLaunchKernelGGL(k_lik_ximg, dim3((unsigned)n_ptiles), dim3(256), 0, st, (int)cfg->D, nb, x, ximg_ws, (const uint32_t*)nullptr);
-            }
-            VX_CHECK_LAUNCH();
-        }
-        int rc;
-        const dim3 grid((unsigned)(groups * n_pr));
-        if (f16) {
-            rc = set_lds(k_irt_lik_h<0>, LH_LDS_BYTES);
-            if (rc) return rc;
-            ProfScope ps("k_irt_lik_h", st);
-            hipLaunchKernelGGL((k_irt_lik_h<0>), grid, dim3(LH_THREADS), LH_LDS_BYTES, st, dm, yT, yT_stride, ximg, a, b,
-                               gx_part, ll_part, slabs, (const uint32_t*)ovf);
-            VX_CHECK_LAUNCH();
-            // the stand-by for a latent outside the f16 image's range (|x| >= 511.75): the bf16x3 kernel on its own image, both
-            // returning at once unless the overflow word is set -- two empty launches a step otherwise.  Its image takes the
-            // workspace's image region (an f16 image made here is dead by then; the overflow word is not in that region).
-            rc = set_lds(k_irt_lik_b<0>, LB_LDS_BYTES);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_lik_ximg, dim3((unsigned)(n_ptiles < 4 * num_cu() ? n_ptiles : 4 * num_cu())), dim3(256), 0, st, (int)cfg->D,
-                               nb, x, ximg_ws, (const uint32_t*)ovf);
-            hipLaunchKernelGGL((k_irt_lik_b<0>), grid, dim3(LB_THREADS), LB_LDS_BYTES, st, dm, yT, yT_stride, (const uint8_t*)ximg_ws,
-                               a, b, c_un, d_un, gx_part, ll_part, slabs, (long long*)nullptr, (const uint32_t*)ovf);
-        } else if (cfg->model >= VX_IRT_3PL) {
-            rc = set_lds(k_irt_lik_b<1>, LB_LDS_BYTES);
-            if (rc) return rc;
-            ProfScope ps("k_irt_lik_b", st);
-            hipLaunchKernelGGL((k_irt_lik_b<1>), grid, dim3(LB_THREADS), LB_LDS_BYTES, st, dm, yT, yT_stride, ximg,
-                               a, b, c_un, d_un, gx_part, ll_part, slabs, (long long*)nullptr);
-        } else {
-            rc = set_lds(k_irt_lik_b<0>, LB_LDS_BYTES);
-            if (rc) return rc;
-            ProfScope ps("k_irt_lik_b", st);
-            hipLaunchKernelGGL((k_irt_lik_b<0>), grid, dim3(LB_THREADS), LB_LDS_BYTES, st, dm, yT, yT_stride, ximg,
-                               a, b, c_un, d_un, gx_part, ll_part, slabs, (long long*)nullptr);
-        }
-        VX_CHECK_LAUNCH();
-        gd_done = true;
-        hipLaunchKernelGGL(k_lik_reduce_parts, dim3((unsigned)n_ptiles), dim3(256), (size_t)64 * (cfg->D | 1) * sizeof(float), st, (const float*)gx_part, (const float*)ll_part,
-                           x, groups, (int)cfg->D, nb, nbp, cfg->scale, gxT, ll, epsT, ldT, gdT, opmax);
-        VX_CHECK_LAUNCH();
-        if (gx) {                                          // both orders requested: gx[nb][D] = transpose(gxT[D][nb])
-            hipLaunchKernelGGL(k_transpose, dim3(num_cu() * 8), dim3(256), 0, st, gxT, gx, (int64_t)cfg->D, nb);
-            VX_CHECK_LAUNCH();
-        }
-        return vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, gitem, hs);
     }
-    const int groups = p.groups, n_pr = p.n_pr;
-    if (p.r) {
-        LikRDims dm;
-        dm.D = cfg->D; dm.J = cfg->J; dm.K8 = (cfg->D + 8) & ~7; dm.model = cfg->model;
-        { const int nq = dm.K8 >> 3; dm.XS = 8 * (nq <= 13 ? 13 : 16) + 4; }
-        dm.groups = groups; dm.n_pr = n_pr; dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
-        dm.slab_len = p.slab_len;
-        dm.fast = (cfg->D % 4 == 0 && cfg->J % 4 == 0 && cfg->J >= 8 && aligned16(x) && aligned16(y) &&
-                   aligned16(gx) && aligned16(workspace)) ? 1 : 0;
-        dm.gxt = gxT ? 1 : 0;                              // partials (and their sum) dimension-major
-        float* slabs = workspace;
-        float* gx_sum = gxT ? gxT : gx;
-        float* gx_part = groups > 1 ? workspace + p.gx_part : gx_sum;
-        float* ll_part = groups > 1 ? workspace + p.ll_part : ll;
-        hipStream_t st = (hipStream_t)hs;
-        // several item chunks and dimension-major partials: ONE finishing launch sums the partials, makes the DIAG-row operand
-        // and reduces the item slabs (k_lik_finish); otherwise the slabs are cleared and reduced as before
-        const bool finish1 = nb > 0 && groups > 1 && !(gxT && gx);
-        if (!finish1) {
-            hipError_t he = hipMemsetAsync(slabs, 0, sizeof(float) * (size_t)n_pr * dm.slab_len, st);
-            if (he != hipSuccess) return (int)he;
-        }
-        if (nb > 0) {
-            const size_t lds = likr_lds_bytes(dm.XS);
-            const dim3 grid((unsigned)(groups * n_pr));
-            int rc = VX_EINVAL;
-            const int nq = dm.K8 >> 3;                     // 9..16; instantiated: 13, 16 (extra rows are zeros)
+    if (nb > 0) {
+        const size_t lds = likr_lds_bytes(dm.XS);
+        const dim3 grid((unsigned)(groups * n_pr));
+        int rc = VX_EINVAL;
+        const int nq = dm.K8 >> 3;                     // 9..16; instantiated: 13, 16 (extra rows are zeros)
 #define LAUNCH_LIKR(GEN, NQ, FAST)                                                                              \
     rc = set_lds(k_irt_lik_r<GEN, NQ, FAST>, lds);                                                              \
     if (rc) return rc;                                                                                          \
@@ -979,45 +1032,49 @@ static int irt_lik_grad_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const i
 #define DISPATCH_LIKR(GEN, FAST)                            \
     if (nq <= 13) { LAUNCH_LIKR(GEN, 13, FAST); }           \
     else { LAUNCH_LIKR(GEN, 16, FAST); }
-            const int fastv = dm.fast ? (rows ? 2 : 1) : 0;
-            if (cfg->model >= VX_IRT_3PL) {
-                if (fastv == 2) { DISPATCH_LIKR(1, 2) } else if (fastv == 1) { DISPATCH_LIKR(1, 1) } else { DISPATCH_LIKR(1, 0) }
-            } else {
-                if (fastv == 2) { DISPATCH_LIKR(0, 2) } else if (fastv == 1) { DISPATCH_LIKR(0, 1) } else { DISPATCH_LIKR(0, 0) }
-            }
+        const int fastv = dm.fast ? (rows ? 2 : 1) : 0;
+        if (cfg->model >= VX_IRT_3PL) {
+            if (fastv == 2) { DISPATCH_LIKR(1, 2) } else if (fastv == 1) { DISPATCH_LIKR(1, 1) } else { DISPATCH_LIKR(1, 0) }
+        } else {
+            if (fastv == 2) { DISPATCH_LIKR(0, 2) } else if (fastv == 1) { DISPATCH_LIKR(0, 1) } else { DISPATCH_LIKR(0, 0) }
+        }
 #undef DISPATCH_LIKR
 #undef LAUNCH_LIKR
+        VX_CHECK_LAUNCH();
+        if (finish1) {
+            const int64_t n_gx = nb * cfg->D;
+            const bool with_gd = c.gdT && gxT && !c.opmax;   // (the maxima, when asked for, come from k_absmax3 behind k_mvn_gd)
+            const int nblk_gx = grid_1d(n_gx, 256), nblk_ll = grid_1d(nb, 256), nblk_s = grid_1d(dm.slab_len, 64);
+            // (the kernel writes the a and b columns of every item, and the c / d columns only for the 3PL / 4PL links)
+            const int64_t len_w = cfg->model >= VX_IRT_3PL ? dm.slab_len : (int64_t)(cfg->D + 1) * cfg->J;
+            hipLaunchKernelGGL(k_lik_finish, dim3((unsigned)(nblk_gx + nblk_ll + nblk_s)), dim3(256), 0, st, (const float*)gx_part,
+                               groups, n_gx, gx_sum, with_gd ? c.epsT : (const float*)nullptr, c.ldT, with_gd ? c.gdT : (float*)nullptr,
+                               cfg->scale, (const float*)ll_part, nb, c.ll, (const float*)slabs, (int64_t)n_pr, dm.slab_len, len_w,
+                               c.gitem, nblk_gx, nblk_ll);
             VX_CHECK_LAUNCH();
-            if (finish1) {
-                const int64_t n_gx = nb * cfg->D;
-                const bool with_gd = gdT && gxT && !opmax;       // (the maxima, when asked for, come from k_absmax3 behind k_mvn_gd)
-                const int nblk_gx = grid_1d(n_gx, 256), nblk_ll = grid_1d(nb, 256), nblk_s = grid_1d(dm.slab_len, 64);
-                // (the kernel writes the a and b columns of every item, and the c / d columns only for the 3PL / 4PL links)
-                const int64_t len_w = cfg->model >= VX_IRT_3PL ? dm.slab_len : (int64_t)(cfg->D + 1) * cfg->J;
-                hipLaunchKernelGGL(k_lik_finish, dim3((unsigned)(nblk_gx + nblk_ll + nblk_s)), dim3(256), 0, st, (const float*)gx_part,
-                                   groups, n_gx, gx_sum, with_gd ? epsT : (const float*)nullptr, ldT, with_gd ? gdT : (float*)nullptr,
-                                   cfg->scale, (const float*)ll_part, nb, ll, (const float*)slabs, (int64_t)n_pr, dm.slab_len, len_w,
-                                   gitem, nblk_gx, nblk_ll);
-                VX_CHECK_LAUNCH();
-                if (with_gd) gd_done = true;
-                return VX_OK;
-            }
-            if (groups > 1) {
-                int r2 = vx_reduce_slabs(gx_part, groups, nb * cfg->D, 1.0f, gx_sum, hs);
-                if (r2) return r2;
-                r2 = vx_reduce_slabs(ll_part, groups, nb, 1.0f, ll, hs);
-                if (r2) return r2;
-            }
-            if (gxT && gx) {                               // both orders requested: gx[nb][D] = transpose(gxT[D][nb])
-                hipLaunchKernelGGL(k_transpose, dim3(num_cu() * 8), dim3(256), 0, st, gxT, gx, (int64_t)cfg->D, nb);
-                VX_CHECK_LAUNCH();
-            }
+            return LikDone(VX_OK, with_gd);
         }
-        return vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, gitem, hs);
+        if (groups > 1) {
+            int r2 = vx_reduce_slabs(gx_part, groups, nb * cfg->D, 1.0f, gx_sum, (void*)st);
+            if (r2) return r2;
+            r2 = vx_reduce_slabs(ll_part, groups, nb, 1.0f, c.ll, (void*)st);
+            if (r2) return r2;
+        }
+        if (gxT && gx) {                               // both orders requested: gx[nb][D] = transpose(gxT[D][nb])
+            hipLaunchKernelGGL(k_transpose, dim3(num_cu() * 8), dim3(256), 0, st, gxT, gx, (int64_t)cfg->D, nb);
+            VX_CHECK_LAUNCH();
+        }
     }
-    float* gxT_req = gxT;
-    if (!gx) gx = workspace + p.gx_tmp;                    // person-major result of the kernels below
-    const int kt = p.kt, nch = p.nch;
+    return vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, c.gitem, (void*)st);
+}
+
+// the shape-generic kernel (k_irt_lik.hip)
+static LikDone lik_grad_generic(const LikCall& c) {
+    const vx_irt_cfg* cfg = c.cfg; const LikPlan& p = c.p;
+    const int64_t nb = c.nb;
+    const int groups = p.groups, n_pr = p.n_pr, kt = p.kt, nch = p.nch;
+    const uint8_t* y = c.y; const int64_t* rows = c.rows; const float *x = c.x, *a = c.a, *b = c.b, *c_un = c.c_un, *d_un = c.d_un;
+    float* gx = c.gx ? c.gx : c.workspace + p.gx_tmp;  // person-major result of the kernels below
     LikDims dm;
     dm.D = cfg->D; dm.J = cfg->J; dm.DS = lik_ds(cfg->D); dm.Dk2 = (cfg->D + 2) & ~1; dm.model = cfg->model;
     dm.Dc = cfg->Dc; dm.scale = cfg->scale; dm.nb = nb;
@@ -1025,10 +1082,10 @@ static int irt_lik_grad_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const i
     dm.fast = (!force_generic() && cfg->D % 4 == 0 && cfg->J % 4 == 0 && aligned16(x) && aligned16(a) && aligned16(b) &&
                aligned16(y) && aligned16(gx) && (nb * cfg->D) % 4 == 0) ? 1 : 0;
     const int gen = cfg->model >= VX_IRT_3PL ? 1 : 0;
-    float* slabs = workspace;
-    float* gx_part = groups > 1 ? workspace + p.gx_part : gx;
-    float* ll_part = groups > 1 ? workspace + p.ll_part : ll;
-    hipStream_t st = (hipStream_t)hs;
+    float* slabs = c.workspace;
+    float* gx_part = groups > 1 ? c.workspace + p.gx_part : gx;
+    float* ll_part = groups > 1 ? c.workspace + p.ll_part : c.ll;
+    hipStream_t st = c.st;
     // slabs are only partially written when a model has no c/d segment: clear them first
     hipError_t he = hipMemsetAsync(slabs, 0, sizeof(float) * (size_t)n_pr * dm.slab_len, st);
     if (he != hipSuccess) return (int)he;
@@ -1054,19 +1111,18 @@ static int irt_lik_grad_kernels(const vx_irt_cfg* cfg, const uint8_t* y, const i
 #undef LAUNCH_LIK
         VX_CHECK_LAUNCH();
         if (groups > 1) {
-            int r2 = vx_reduce_slabs(gx_part, groups, nb * cfg->D, 1.0f, gx, hs);
+            int r2 = vx_reduce_slabs(gx_part, groups, nb * cfg->D, 1.0f, gx, (void*)st);
             if (r2) return r2;
-            r2 = vx_reduce_slabs(ll_part, groups, nb, 1.0f, ll, hs);
+            r2 = vx_reduce_slabs(ll_part, groups, nb, 1.0f, c.ll, (void*)st);
             if (r2) return r2;
         }
     }
-    if (gxT_req && nb > 0) {
-        hipLaunchKernelGGL(k_transpose, dim3(num_cu() * 8), dim3(256), 0, (hipStream_t)hs, gx, gxT_req, nb,
-                           (int64_t)cfg->D);
+    if (c.gxT && nb > 0) {
+        hipLaunchKernelGGL(k_transpose, dim3(num_cu() * 8), dim3(256), 0, st, gx, c.gxT, nb, (int64_t)cfg->D);
         VX_CHECK_LAUNCH();
     }
     // loss gradients = -(d ELBO / d .)
-    return vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, gitem, hs);
+    return vx_reduce_slabs(slabs, n_pr, dm.slab_len, -1.0f, c.gitem, (void*)st);
 }
 
 int vx_irt_lik_grad(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* x,
@@ -1081,10 +1137,11 @@ int vx_irt_lik_grad(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows
         return VX_EINVAL;
     if (cfg->model >= VX_IRT_3PL && !c_un) return VX_EINVAL;
     if (cfg->model == VX_IRT_4PL && !d_un) return VX_EINVAL;
-    bool gd_done = false;
-    const int rc = irt_lik_grad_kernels(cfg, y, rows, nb, x, a, b, c_un, d_un, gx, gxT, ll, gitem, workspace, yT, yT_stride, ximg_in,
-                                        epsT, ldT, gdT, opmax, hs, gd_done);
-    if (rc) return rc;
+    const LikCall c{cfg, lik_plan(cfg, nb), y, rows, nb, x, a, b, c_un, d_un, gx, gxT, ll, gitem, workspace, yT, yT_stride, ximg_in,
+                    epsT, ldT, gdT, opmax, (hipStream_t)hs};
+    const LikDone done = lik_b_ok(c) ? lik_grad_b(c) : (c.p.r ? lik_grad_r(c) : lik_grad_generic(c));
+    if (done.rc) return done.rc;
+    const bool gd_done = done.gd_done;
     // the fused DIAG-row operand of the guide backward, for the paths that do not make it themselves
     if (gdT && !gd_done && nb > 0) {
         hipLaunchKernelGGL(k_mvn_gd, dim3(num_cu() * 8), dim3(256), 0, (hipStream_t)hs, (const float4*)gxT, (const float4*)epsT,
@@ -1143,88 +1200,331 @@ int64_t vx_mvn_enc_bwd_workspace_floats(const vx_irt_cfg* cfg, int64_t nb) {
 // the loss of the step, summed by the call's last launch (vx_mvn_enc_backward_loss)
 struct LossTail { const float* ll; const float* ent; float alpha; float* loss; float* sum_ws; };
 
-static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb,
-                        const float* W21, const float* W22, const float* h, const float* eps, const float* ldT,
-                        const float* gx, const float* hT, const float* epsT, const float* gxT, const uint8_t* yT,
-                        int64_t yT_stride, float* genc, float* workspace, const float* packws, int32_t gd_ready, void* hs,
-                        const LossTail* tail) {
-    if (!enc_cfg_ok(cfg) || !y || !W21 || !W22 || !h || !eps || !ldT || (!gx && !gxT) || !genc || !workspace || nb < 0)
-        return VX_EINVAL;
-    const MvnPlan p = mvn_plan(cfg, nb);
-    const PackLayout pk = pack_layout(cfg);
-    EncDims dm = make_enc_dims(cfg, nb);
-    const int64_t D = cfg->D, H = cfg->H, Rp = pk.Rp, lenw = p.lenw, lenf = p.lenf;
-    const bool packed = p.packed && packws && aligned16(packws) && aligned16(h) && aligned16(eps) &&
-                        aligned16(gx) && aligned16(workspace) && nb > 0;
-    if (p.packed && !packed && nb > 0) return VX_EINVAL;          // the plan assumed the packed row space
-    const bool use_t = packed && hT && epsT && gxT && p.bwt && aligned16(hT) && aligned16(epsT) &&
-                       aligned16(gxT) && aligned16(ldT);
-    int n_rowslabs = use_t ? p.n_rowslabs_t : p.n_rowslabs;
-    const int n_prw = use_t ? p.n_prw_t : p.n_prw, n_jg = p.n_jg, n_prf = p.n_prf;
-    float* ghpre = workspace;
-    float* slabs_w = workspace + p.slabs_w;
-    float* slabs_f = workspace + p.slabs_f;
-    float* gdT = p.bwt ? workspace + p.gd : nullptr;      // the DIAG-row operand of the dimension-major kernels
-    uint16_t* hs3 = p.bwb ? (uint16_t*)(workspace + p.hs) : nullptr;   // two fp16 terms of hT 2^sh
-    // written by the forward call of this step (k_enc_scales): the powers of two of the f16x2 weight images
-    const float* sc = packws ? packws + pk.sc : nullptr;
-    // the step's largest |gx|, |gd|, |eps|, |ghpre| (float bits): words 11 .. 14 of the scale block when the forward call packed
-    // for this backward (cleared there), the last words of the workspace otherwise
-    const bool hb_fw = packws && p.hb_fw;
-    uint32_t* maxw = (uint32_t*)(hb_fw ? const_cast<float*>(packws) + pk.maxw : workspace + p.maxw);
-    hipStream_t st = (hipStream_t)hs;
-    int rc;
-    bool f1t = false;                                      // fc1 gradient on the dimension-major kernel (ghpre holds ghpreT)
-    bool maxw_ready = false;                               // k_mvn_enc_bwd_h_b ran: the operand maxima of the step are collected
-    bool f1_done = false;                                  // the fc1 gradient (and its slab sum) went out on the side stream
-    bool f1_launched = false;                              // ... rode in the head weight gradient's launch (k_bwd_wt_fc1)
-    ForkScope f1_fork;                                     // ... joined below, or by the scope on an error return
-    ForkScope bwb_fork;
-    bool bwb_done = false;
-    std::optional<ProfScope> pair_ps;
-    // the fc1 weight gradient from dimension-major operands (k_fc1_bwd_c.hip; ghpre holds ghpreT): two fp16 terms of ghpre when
-    // the hidden-gradient kernel collected the step's largest |ghpre| (maxw[3]), three bf16 terms otherwise
-    auto launch_fc1_c = [&](hipStream_t fs) -> int {
-        ProfScope ps("k_fc1_bwd_c", fs);
-        const dim3 grid((unsigned)((cfg->J + 1 + 511) / 512), (unsigned)n_prf);
-        if (maxw_ready) {
-            int r = set_lds(k_fc1_bwd_c<true>, f1c_lds_bytes());
-            if (r) return r;
-            hipLaunchKernelGGL(k_fc1_bwd_c<true>, grid, dim3(F1C_THREADS), f1c_lds_bytes(), fs, dm, yT, yT_stride, ghpre, slabs_f, lenf,
-                               (const uint32_t*)maxw);
-        } else {
-            int r = set_lds(k_fc1_bwd_c<false>, f1c_lds_bytes());
-            if (r) return r;
-            hipLaunchKernelGGL(k_fc1_bwd_c<false>, grid, dim3(F1C_THREADS), f1c_lds_bytes(), fs, dm, yT, yT_stride, ghpre, slabs_f, lenf,
-                               (const uint32_t*)nullptr);
+// The arguments of one vx_mvn_enc_backward(_loss) call
+struct BwdArgs {
+    const uint8_t* y; const int64_t* rows; int64_t nb;
+    const float *W21, *W22, *h, *eps, *ldT, *gx, *hT, *epsT, *gxT;
+    const uint8_t* yT; int64_t yT_stride;
+    float *genc, *workspace; const float* packws; int32_t gd_ready; const LossTail* tail;
+};
+
+// The route of one backward call: every choice that (plan, pointer presence and alignment, nb, rows, yT_stride, gd_ready
+// bits) decide, resolved by bwd_route() before the first launch.  What a fork's success decides at run time is not in here.
+enum class BwdLayout { Empty, DimMajor, PackedPersonMajor, Fast, Generic };    // Empty: nb == 0; DimMajor: hT / epsT / gxT / gdT
+enum class HidKernel { None, B_small, B2, B_large, T, P, Fast, Generic };      // h_b<true> | h_b2 (+ h_b<false>) | h_b<false> | h_t | h_p | ..
+enum class WgtKernel { None, B, T, T_fc1, FastPacked, Fast, Generic };         // w_b | w_t | k_bwd_wt_fc1 | w_fast<true> | w_fast<false> | w<HT>
+enum class Fc1Kernel { None, C, T, Rode, Small, Wide };                        // fc1_bwd_c | fc1_bwd_t | in k_bwd_wt_fc1 | fc1_bwd<2, 1> | fc1_bwd<HT>
+struct BwdRoute {
+    bool refused;                // VX_EINVAL: the plan assumed the packed row space, or the person-major kernel has no gx
+    BwdLayout layout;
+    bool packed;                 // DimMajor or PackedPersonMajor: the packed head layout, the one-launch tail (k_enc_bwd_tail)
+    HidKernel hid;
+    int64_t hid_n_done;          // B2: the persons of its whole chip rounds; the rest is a last round of h_b<false> ...
+    bool hid_last_side;          // ... which wants the side stream (0)
+    bool pack_hb, pack_heads;    // k_pack_heads_hb / k_pack_heads in front of the hidden gradient
+    bool f1t;                    // the hidden gradient leaves ghpreT (dimension-major) for the fc1 gradient
+    WgtKernel wgt;
+    int n_rowslabs, n_prw;       // its grid
+    bool gd_first;               // k_mvn_gd in front of everything (gd_ready bit 0 not set)
+    bool split_hs, absmax;       // B: k_split2_f16 (bit 1 not set) / k_clear_words + k_absmax3 (maxima not collected) in front of it
+    bool pair;                   // B wants stream 1, beside the hidden gradient (all three gd_ready bits, images from the forward)
+    Fc1Kernel fc1;
+    bool fc1_side;               // C wants stream 0, beside the head weight gradient
+    bool maxw_in_pack;           // the operand maxima and the unit images live in packws (the forward packed for this backward) ...
+    bool maxw_ready;             // ... and the maxima are collected when the weight and fc1 gradients start (an h_b kernel ran)
+};
+static BwdRoute bwd_route(const vx_irt_cfg* cfg, const MvnPlan& p, const BwdArgs& a) {
+    const int64_t nb = a.nb;
+    const bool f1_small = fc1_small_batch((cfg->H + 31) / 32 * 32, p.n_jg, p.n_prf);
+    BwdRoute r = {};
+    r.packed = p.packed && a.packws && aligned16(a.packws) && aligned16(a.h) && aligned16(a.eps) && aligned16(a.gx) &&
+               aligned16(a.workspace) && nb > 0;
+    const bool use_t = r.packed && a.hT && a.epsT && a.gxT && p.bwt && aligned16(a.hT) && aligned16(a.epsT) && aligned16(a.gxT) &&
+                       aligned16(a.ldT);
+    const bool fast = !r.packed && p.encb_fast && aligned16(a.W21) && aligned16(a.W22) && aligned16(a.h) && aligned16(a.eps) &&
+                      aligned16(a.gx) && aligned16(a.workspace);
+    r.layout = nb == 0 ? BwdLayout::Empty : use_t ? BwdLayout::DimMajor : r.packed ? BwdLayout::PackedPersonMajor
+               : fast ? BwdLayout::Fast : BwdLayout::Generic;
+    r.maxw_in_pack = a.packws && p.hb_fw;
+    r.n_rowslabs = use_t ? p.n_rowslabs_t : p.n_rowslabs;
+    r.n_prw = use_t ? p.n_prw_t : p.n_prw;
+    r.gd_first = use_t && !(a.gd_ready & 1);
+    // the hidden gradient
+    if (use_t && p.bwh_t) {
+        r.f1t = a.yT && !a.rows && a.yT_stride % 16 == 0 && a.yT_stride >= nb && aligned16(a.yT) && cfg->J >= 32 &&
+                f1_lds_bytes(cfg->J) <= 160 * 1024;
+        r.hid = HidKernel::T;
+        if (p.bwhb) {
+            r.pack_hb = !r.maxw_in_pack;
+            r.maxw_ready = true;
+            // small batch: the eight waves of a workgroup share the units; large batch: 64 persons per wave, batches of four
+            // units per barrier (k_mvn_bwd_hb2.hip)
+            r.hid = nb <= HB_SPLIT_MAX ? HidKernel::B_small
+                    : (cfg->D <= 112 && hb2_lds_bytes(cfg->D) <= 160 * 1024) ? HidKernel::B2 : HidKernel::B_large;
+            // B2's workgroups take 256 persons: a last round that fills less than half the chip goes to the 32-persons-
+            // per-wave kernel instead (1M persons: 15 full rounds + 16 960 persons), as in the forward
+            const int64_t round2 = (int64_t)256 * num_cu(), rem = nb % round2;
+            r.hid_n_done = (rem > 0 && 2 * rem <= round2 && nb > round2) ? nb - rem : nb;
+            r.hid_last_side = r.hid == HidKernel::B2 && r.hid_n_done < nb && p.side_streams;
         }
+    } else if (r.packed) {
+        r.hid = HidKernel::P;
+        // the forward call packed for the f16x2 hidden gradient and made no packed copy of the heads (k_pack_fused.hip,
+        // direct): this kernel reads one
+        r.pack_heads = r.maxw_in_pack;
+    } else if (nb > 0) {
+        r.hid = fast ? HidKernel::Fast : HidKernel::Generic;
+    }
+    r.refused = (p.packed && !r.packed && nb > 0) || (r.hid == HidKernel::P && !a.gx);
+    // the head weight gradient.  T_fc1: a small batch, the fc1 weight gradient (k_fc1_bwd<2, 1>) rides in the same launch
+    const bool rides = !r.f1t && f1_small && BT_THREADS == ENC_THREADS;
+    if (use_t) r.wgt = p.bwb ? WgtKernel::B : rides ? WgtKernel::T_fc1 : WgtKernel::T;
+    else if (nb > 0) r.wgt = r.packed ? WgtKernel::FastPacked : fast ? WgtKernel::Fast : WgtKernel::Generic;
+    r.split_hs = r.wgt == WgtKernel::B && !(a.gd_ready & 2);
+    r.absmax = r.wgt == WgtKernel::B && !r.maxw_ready;
+    r.pair = r.wgt == WgtKernel::B && (a.gd_ready & 7) == 7 && r.maxw_in_pack && p.bwh_t && p.side_streams;
+    // (the plan sized its row slabs for the fast kernel where the shape allows that one)
+    if (r.wgt == WgtKernel::Generic) r.n_rowslabs = (int)(((int64_t)tril_len(cfg->D) + cfg->D + BW_ROWS - 1) / BW_ROWS);
+    // the fc1 gradient
+    if (r.f1t) r.fc1 = p.fc1_16 ? Fc1Kernel::C : Fc1Kernel::T;
+    else if (nb > 0) r.fc1 = r.wgt == WgtKernel::T_fc1 ? Fc1Kernel::Rode : f1_small ? Fc1Kernel::Small : Fc1Kernel::Wide;
+    r.fc1_side = r.fc1 == Fc1Kernel::C && p.side_streams;
+    return r;
+}
+
+// What the stages of one backward call read: the call, its plans and route, the regions of its buffers
+extern "C++" struct BwdCtx {                                // (C++ linkage: it has a member template)
+    const vx_irt_cfg* cfg; BwdArgs a; MvnPlan p; PackLayout pk; BwdRoute rt; EncDims dm; hipStream_t st;
+    float *ghpre, *slabs_w, *slabs_f;
+    float* gdT;                  // the DIAG-row operand of the dimension-major kernels
+    uint16_t* hs3;               // two fp16 terms of hT 2^sh
+    const float* sc;             // written by the forward call of this step (k_enc_scales): the powers of two of the f16x2 weight images
+    uint32_t* maxw;              // the step's largest |gx|, |gd|, |eps|, |ghpre| (float bits): words 11 .. 14 of the scale block when the
+                                 // forward call packed for this backward (cleared there), the last words of the workspace otherwise
+    uint8_t* himg;               // the unit images: made by the forward call's pack launches (k_pack_fused.hip), or here
+    const uint32_t* gtab;
+    // one launch of an f16x2 hidden-gradient kernel (k_mvn_bwd_hb*.hip); more: the first person of a launch that is not the whole batch
+    template <typename K, typename... More>
+    int launch_hid_b(K kernel, int64_t n, int per_wg, unsigned threads, size_t lds, hipStream_t s, More... more) const {
+        return launch_lds(kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(threads), lds, s, dm, (const uint8_t*)himg, sc, a.h,
+                          a.eps, a.gxT, (const float*)gdT, rt.f1t ? (float*)nullptr : ghpre, a.hT, rt.f1t ? ghpre : (float*)nullptr,
+                          maxw, more...);
+    }
+};
+static BwdCtx bwd_ctx(const vx_irt_cfg* cfg, const BwdArgs& a, const MvnPlan& p, const BwdRoute& rt, hipStream_t st) {
+    BwdCtx c{cfg, a, p, pack_layout(cfg), rt, make_enc_dims(cfg, a.nb), st};
+    float* pw = const_cast<float*>(a.packws);
+    c.ghpre = a.workspace; c.slabs_w = a.workspace + p.slabs_w; c.slabs_f = a.workspace + p.slabs_f;
+    c.gdT = p.bwt ? a.workspace + p.gd : nullptr; c.hs3 = p.bwb ? (uint16_t*)(a.workspace + p.hs) : nullptr;
+    c.sc = pw ? pw + c.pk.sc : nullptr;
+    c.maxw = (uint32_t*)(rt.maxw_in_pack ? pw + c.pk.maxw : a.workspace + p.maxw);
+    c.himg = !p.bwhb ? nullptr : (uint8_t*)(rt.maxw_in_pack ? pw + c.pk.himg : a.workspace + p.himg);
+    c.gtab = pw ? (const uint32_t*)(pw + c.pk.gtab) : nullptr;
+    return c;
+}
+
+// Stage 1, the hidden gradient: ghpre (or ghpreT: rt.f1t) from the heads' gradients.  beside_w: the head weight gradient
+// already runs on its stream.
+static int bwd_hidden(const BwdCtx& c, bool beside_w) {
+    const BwdArgs& a = c.a; const BwdRoute& rt = c.rt; const EncDims& dm = c.dm;
+    const int64_t nb = a.nb;
+    hipStream_t st = c.st;
+    const dim3 grid_p((unsigned)((nb + ENC_P - 1) / ENC_P));
+    if (rt.pack_hb) {
+        hipLaunchKernelGGL(k_pack_heads_hb, dim3(hb_units(dm.D)), dim3(256), 0, st, dm.D, a.W21, a.W22, c.sc, c.himg, c.maxw);
         VX_CHECK_LAUNCH();
-        return VX_OK;
-    };
-    if (packed) {
-        const float* Wp = packws;
-        const uint32_t* gtab = (const uint32_t*)(packws + pk.gtab);
-        if (use_t && !(gd_ready & 1)) {                    // (bit 0: the likelihood's last pass made gdT)
-            hipLaunchKernelGGL(k_mvn_gd, dim3(num_cu() * 8), dim3(256), 0, st, (const float4*)gxT, (const float4*)epsT,
-                               (const float4*)ldT, cfg->scale, nb * D / 4, (float4*)gdT);
+    }
+    if (rt.pack_heads) {
+        hipLaunchKernelGGL(k_pack_heads, dim3((unsigned)c.pk.Rp), dim3(64), 0, st, (int)dm.D, 64, a.W21, (const float*)nullptr, a.W22,
+                           (const float*)nullptr, const_cast<float*>(a.packws), (float*)nullptr, const_cast<uint32_t*>(c.gtab),
+                           (float*)nullptr);
+        VX_CHECK_LAUNCH();
+    }
+    switch (rt.hid) {
+    case HidKernel::B_small: case HidKernel::B2: case HidKernel::B_large: {
+        const size_t ldsh = hb_lds_bytes(dm.D);
+        // (beside the head weight gradient the bracket spans both kernels: filed under a name of its own, not priced)
+        ProfScope ps(beside_w ? "k_mvn_enc_bwd_h_b2 beside k_mvn_enc_bwd_w_b" : "k_mvn_enc_bwd_h_b", st);
+        if (rt.hid == HidKernel::B_small) return c.launch_hid_b(k_mvn_enc_bwd_h_b<true>, nb, 32, HB_THREADS, ldsh, st, (int64_t)0);
+        if (rt.hid == HidKernel::B_large) return c.launch_hid_b(k_mvn_enc_bwd_h_b<false>, nb, 32 * HB_WAVES, HB_THREADS, ldsh, st, (int64_t)0);
+        constexpr int HNSET = 1;                              // eight waves of 32 persons (k_mvn_bwd_hb2.hip)
+        const int64_t n_done = rt.hid_n_done;
+        auto whole_rounds = [&]() -> int {
+            return c.launch_hid_b(k_mvn_enc_bwd_h_b2<7, HNSET>, n_done, 256, 64 * HB2_WAVES_OF(HNSET), hb2_lds_bytes(dm.D), st);
+        };
+        if (n_done == nb) return whole_rounds();
+        // the short last round on the second stream beside the whole rounds (launched first), as in the forward
+        return with_last_round(rt.hid_last_side ? &side_stream(0, st) : nullptr, st, [&](hipStream_t ts) -> int {
+            return c.launch_hid_b(k_mvn_enc_bwd_h_b<false>, nb - n_done, 32 * HB_WAVES, HB_THREADS, ldsh, ts, n_done);
+        }, whole_rounds);
+    }
+    case HidKernel::T: {
+        ProfScope ps("k_mvn_enc_bwd_h_t", st);
+        return launch_lds(k_mvn_enc_bwd_h_t, dim3((unsigned)((nb + BH_P - 1) / BH_P)), dim3(BH_THREADS), bh_lds_bytes(dm.D), st, dm,
+                          c.cfg->scale, a.packws + c.pk.wpT, c.gtab, a.h, a.eps, a.ldT, a.gxT, c.gdT,
+                          rt.f1t ? (float*)nullptr : c.ghpre, a.hT, rt.f1t ? c.ghpre : (float*)nullptr);
+    }
+    case HidKernel::P:
+        return launch_lds(k_mvn_enc_bwd_h_p, grid_p, dim3(ENC_THREADS), enc_bwdh_p_lds_floats(dm.D) * sizeof(float), st, dm,
+                          c.cfg->scale, a.packws, c.gtab, a.h, a.eps, a.ldT, a.gx, c.ghpre);
+    case HidKernel::Fast:
+        return launch_lds(k_mvn_enc_bwd_h_fast, grid_p, dim3(ENC_THREADS), enc_bwdh_fast_lds_floats(dm.D) * sizeof(float), st, dm,
+                          c.cfg->scale, a.W21, a.W22, a.h, a.eps, a.ldT, a.gx, c.ghpre);
+    case HidKernel::Generic:
+        return with_hidden_width(dm.Hp, [&](auto ht) -> int {
+            return launch_lds(k_mvn_enc_bwd_h<decltype(ht)::value>, grid_p, dim3(ENC_THREADS),
+                              enc_bwdh_lds_floats(dm.D, dm.Hp) * sizeof(float), st, dm, c.cfg->scale, a.W21, a.W22, a.h, a.eps, a.ldT,
+                              a.gx, c.ghpre);
+        });
+    case HidKernel::None: break;
+    }
+    return VX_OK;
+}
+
+// Stage 2, the head weight gradient on stream ws (the launch stream, or for WgtKernel::B of a pair the side stream):
+// slabs_w[n_prw][.] over a grid of n_rowslabs x n_prw, with what has to precede it on that stream
+static int bwd_weights(const BwdCtx& c, hipStream_t ws) {
+    const BwdArgs& a = c.a; const BwdRoute& rt = c.rt; const EncDims& dm = c.dm;
+    const int64_t nb = a.nb, Rp = c.pk.Rp, H = c.cfg->H;
+    const dim3 grid((unsigned)rt.n_rowslabs, (unsigned)rt.n_prw);
+    switch (rt.wgt) {
+    case WgtKernel::B: {
+        if (rt.split_hs) {                       // bit 1: the forward call already wrote the fp16 terms of hT here
+            hipLaunchKernelGGL(k_split2_f16, dim3(num_cu() * 8), dim3(256), 0, ws, a.hT, nb * 64, a.packws + c.pk.hscale, c.hs3);
             VX_CHECK_LAUNCH();
         }
-        // (two full-size tile buffers: the three-buffer form of k_mvn_bwd_b.hip measured no faster -- docs/NOTEBOOK.md, round 5)
-        auto launch_bwb_on = [&](hipStream_t ws) -> int {
-            const size_t lds = bb_lds_bytes(dm.D);
-            int r = set_lds(k_mvn_enc_bwd_w_b<2>, lds);
-            if (r) return r;
-            hipLaunchKernelGGL(k_mvn_enc_bwd_w_b<2>, dim3((unsigned)n_rowslabs, (unsigned)n_prw), dim3(BWB_THREADS), lds, ws, dm,
-                               (const uint16_t*)hs3, epsT, (const float*)gdT, gxT, gtab, sc, (const uint32_t*)maxw, slabs_w, Rp * (H + 1));
+        if (rt.absmax) {                         // the operand maxima, normally collected by k_mvn_enc_bwd_h_b
+            hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(64), 0, ws, c.maxw, 4);
+            hipLaunchKernelGGL(k_absmax3, dim3(grid_1d(nb * dm.D, 1024)), dim3(256), 0, ws, a.gxT, (const float*)c.gdT, a.epsT,
+                               nb * dm.D, c.maxw);
             VX_CHECK_LAUNCH();
-            return VX_OK;
-        };
+        }
+        // (its own bracket on ITS stream beside the hidden gradient: the kernel's span while it shares the chip with it)
+        ProfScope ps(ws == c.st ? "k_mvn_enc_bwd_w_b" : "k_mvn_enc_bwd_w_b beside k_mvn_enc_bwd_h_b2", ws);
+        // (two full-size tile buffers: the three-buffer form of k_mvn_bwd_b.hip measured no faster -- docs/NOTEBOOK.md, round 5)
+        return launch_lds(k_mvn_enc_bwd_w_b<2>, grid, dim3(BWB_THREADS), bb_lds_bytes(dm.D), ws, dm, (const uint16_t*)c.hs3, a.epsT,
+                          (const float*)c.gdT, a.gxT, c.gtab, c.sc, (const uint32_t*)c.maxw, c.slabs_w, Rp * (H + 1));
+    }
+    case WgtKernel::T_fc1: {
+        const int n_jg1 = (int)((dm.J + 127) / 128), n_prf = c.p.n_prf;
+        size_t lds = bt_lds_bytes(dm.D);
+        const size_t ldsf = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
+        if (ldsf > lds) lds = ldsf;
+        ProfScope ps("k_mvn_enc_bwd_w_t + k_fc1_bwd", ws);
+        return launch_lds(k_bwd_wt_fc1, dim3((unsigned)(rt.n_rowslabs * rt.n_prw + n_jg1 * n_prf)), dim3(BT_THREADS), lds, ws, dm, a.hT,
+                          a.epsT, (const float*)c.gdT, a.gxT, c.gtab, c.slabs_w, Rp * (H + 1), rt.n_rowslabs, rt.n_prw, a.y, a.rows,
+                          (const float*)c.ghpre, c.slabs_f, c.p.lenf, f1fast_ok(c.cfg, c.ghpre, a.y), n_jg1, n_prf);
+    }
+    case WgtKernel::T: {
+        ProfScope ps("k_mvn_enc_bwd_w_t", ws);
+        return launch_lds(k_mvn_enc_bwd_w_t, grid, dim3(BT_THREADS), bt_lds_bytes(dm.D), ws, dm, a.hT, a.epsT, c.gdT, a.gxT, c.gtab,
+                          c.slabs_w, Rp * (H + 1));
+    }
+    case WgtKernel::FastPacked: case WgtKernel::Fast: {
+        const bool pk = rt.wgt == WgtKernel::FastPacked;       // packed rows through gtab | the reference row order
+        return launch_lds(pk ? k_mvn_enc_bwd_w_fast<true> : k_mvn_enc_bwd_w_fast<false>, grid, dim3(ENC_THREADS),
+                          enc_bwdw_fast_lds_floats(dm.D) * sizeof(float), ws, dm, c.cfg->scale, a.h, a.eps, a.ldT, a.gx,
+                          pk ? c.gtab : (const uint32_t*)nullptr, c.slabs_w, pk ? Rp * (H + 1) : c.p.lenw);
+    }
+    case WgtKernel::Generic:
+        return with_hidden_width(dm.Hp, [&](auto ht) -> int {
+            return launch_lds(k_mvn_enc_bwd_w<decltype(ht)::value>, grid, dim3(ENC_THREADS), enc_bwdw_lds_floats(dm.D, dm.Hp) * sizeof(float),
+                              ws, dm, c.cfg->scale, a.h, a.eps, a.ldT, a.gx, c.slabs_w, c.p.lenw);
+        });
+    case WgtKernel::None: break;
+    }
+    return VX_OK;
+}
+
+// Stage 3, the fc1 weight gradient on stream fs: slabs_f[n_prf][lenf] from ghpre (or ghpreT) and the responses
+static int bwd_fc1(const BwdCtx& c, hipStream_t fs) {
+    const BwdArgs& a = c.a; const EncDims& dm = c.dm;
+    const int n_prf = c.p.n_prf;
+    const int64_t lenf = c.p.lenf;
+    switch (c.rt.fc1) {
+    case Fc1Kernel::C: {
+        // from dimension-major operands through LDS (k_fc1_bwd_c.hip; ghpre holds ghpreT): two fp16 terms of ghpre when the
+        // hidden-gradient kernel collected the step's largest |ghpre| (maxw[3]), three bf16 terms otherwise
+        ProfScope ps("k_fc1_bwd_c", fs);
+        return launch_lds(c.rt.maxw_ready ? k_fc1_bwd_c<true> : k_fc1_bwd_c<false>, dim3((unsigned)((dm.J + 1 + 511) / 512), (unsigned)n_prf),
+                          dim3(F1C_THREADS), f1c_lds_bytes(), fs, dm, a.yT, a.yT_stride, c.ghpre, c.slabs_f, lenf,
+                          c.rt.maxw_ready ? (const uint32_t*)c.maxw : (const uint32_t*)nullptr);
+    }
+    case Fc1Kernel::T:
+        return launch_lds(k_fc1_bwd_t, dim3((unsigned)((dm.J + 511) / 512), (unsigned)n_prf), dim3(F1_THREADS), f1_lds_bytes(dm.J), fs, dm,
+                          a.yT, a.yT_stride, c.ghpre, c.slabs_f, lenf);
+    case Fc1Kernel::Small: case Fc1Kernel::Wide:
+        return fc1_bwd_person_major(dm, c.rt.fc1 == Fc1Kernel::Small, c.p.n_jg, n_prf, a.y, a.rows, c.ghpre, c.slabs_f, lenf,
+                                    f1fast_ok(c.cfg, c.ghpre, a.y), fs);
+    case Fc1Kernel::Rode: break;                           // launched with the head weight gradient: its slabs are summed by the tail
+    case Fc1Kernel::None:                                  // nb == 0: no kernel wrote a slab
+        if (hipError_t he = hipMemsetAsync(c.slabs_w, 0, sizeof(float) * (size_t)(c.rt.n_prw * c.p.lenw + n_prf * lenf), fs)) return (int)he;
+    }
+    return VX_OK;
+}
+
+// Stage 4, the tail: the slabs summed into genc, the loss.  Flat encoder-gradient layout = nn.Linear order:
+// [W1 | b1 | W21 | b21 | W22 | b22]; loss grads = -dELBO.  f1_done: the side stream already summed the fc1 slabs into genc
+static int bwd_tail(const BwdCtx& c, bool f1_done) {
+    const BwdArgs& a = c.a;
+    const LossTail* tail = a.tail;
+    const int64_t nb = a.nb, Rp = c.pk.Rp, H = c.cfg->H, lenf = c.p.lenf;
+    const int n_prf = c.p.n_prf;
+    void* hs = (void*)c.st;
+    uint32_t* step_dev = const_cast<uint32_t*>(c.cfg->step_dev);
+    int rc;
+    if (c.rt.packed) {
+        // ONE launch ends the call (k_enc_bwd_tail): the head gradients back in the reference layout, the fc1 slabs summed
+        // (unless the side stream did), the loss of a small batch -- three launches of ~5 us until round 5
+        const int n_unpack = (int)((Rp + 3) / 4);
+        const int n_f1 = f1_done ? 0 : grid_1d(lenf, 64);
+        const bool loss_here = tail && nb <= 4096;
+        hipLaunchKernelGGL(k_enc_bwd_tail, dim3((unsigned)(n_unpack + n_f1 + (loss_here ? 1 : 0))), dim3(256), 0, c.st, (int)c.cfg->D, (int)H,
+                           c.slabs_w, c.rt.n_prw, Rp * (H + 1), -1.0f, a.genc + lenf, n_unpack, (const float*)c.slabs_f, (int64_t)n_prf, lenf,
+                           a.genc, n_f1, loss_here ? tail->ll : nullptr, loss_here ? tail->ent : nullptr, nb,
+                           loss_here ? tail->alpha : 0.f, loss_here ? tail->loss : nullptr, loss_here ? tail->sum_ws : nullptr,
+                           loss_here ? step_dev : nullptr);
+        VX_CHECK_LAUNCH();
+        if (tail && !loss_here) return vx_sum2(tail->ll, tail->ent, nb, tail->alpha, tail->loss, tail->sum_ws, step_dev, hs);
+        return VX_OK;
+    }
+    if (!f1_done) {
+        rc = vx_reduce_slabs(c.slabs_f, n_prf, lenf, -1.0f, a.genc, hs);
+        if (rc) return rc;
+    }
+    rc = vx_reduce_slabs(c.slabs_w, c.rt.n_prw, c.p.lenw_ref, -1.0f, a.genc + lenf, hs);
+    if (rc) return rc;
+    if (tail) return vx_sum2(tail->ll, tail->ent, nb, tail->alpha, tail->loss, tail->sum_ws, step_dev, hs);
+    return VX_OK;
+}
+
+// vx_mvn_enc_backward(_loss): check the arguments, resolve the route, refuse, then the four stages in order.  The only state
+// carried across stages is what a fork's success decides at run time: w_done (the head weight gradient already runs on
+// stream 1) and f1_done (the fc1 gradient ran and was summed on stream 0).
+static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const BwdArgs& a, void* hs) {
+    if (!enc_cfg_ok(cfg) || !a.y || !a.W21 || !a.W22 || !a.h || !a.eps || !a.ldT || (!a.gx && !a.gxT) || !a.genc || !a.workspace ||
+        a.nb < 0)
+        return VX_EINVAL;
+    const MvnPlan p = mvn_plan(cfg, a.nb);
+    const BwdRoute rt = bwd_route(cfg, p, a);
+    if (rt.refused) return VX_EINVAL;
+    hipStream_t st = (hipStream_t)hs;
+    const BwdCtx c = bwd_ctx(cfg, a, p, rt, st);
+    int rc;
+    bool w_done = false, f1_done = false;
+    ForkScope f1_fork, w_fork;                             // joined below, or by the scope on an error return
+    std::optional<ProfScope> pair_ps;
+    if (rt.gd_first) {                                     // (bit 0: the likelihood's last pass made gdT)
+        hipLaunchKernelGGL(k_mvn_gd, dim3(num_cu() * 8), dim3(256), 0, st, (const float4*)a.gxT, (const float4*)a.epsT,
+                           (const float4*)a.ldT, cfg->scale, a.nb * cfg->D / 4, (float4*)c.gdT);
+        VX_CHECK_LAUNCH();
+    }
+    if (rt.packed) {
         // the bracket of the PAIR on the launch stream: from in front of the fork to behind the join of the head weight gradient's
         // stream = the span of {hidden gradient | head weight gradient} side by side (what bench.py prices with the sum of the two
         // kernels' flops); dropped at once when the two do not run side by side
         pair_ps.emplace("k_mvn_enc_bwd_h_b2 | k_mvn_enc_bwd_w_b side by side", st);
-        if ((gd_ready & 4) && (gd_ready & 2) && (gd_ready & 1) && hb_fw && use_t && p.bwb && p.bwh_t && p.side_streams &&
-            bwb_fork.fork(side_stream(1, st), st)) {
+        if (rt.pair && w_fork.fork(side_stream(1, st), st)) {
             // The head weight gradient needs nothing the hidden gradient makes once the step's operand maxima are there (bit 2:
             // vx_irt_lik_grad collected them): it starts NOW on a second stream, and the hidden gradient and then the fc1
             // gradient run beside it on the launch stream.  The two large kernels each fill the chip alone; side by side
@@ -1232,291 +1532,48 @@ static int mvn_enc_backward_impl(const vx_irt_cfg* cfg, const uint8_t* y, const 
             // for the backward phase of the 1M step.  (The hidden-gradient kernels still add their waves' maxima to the same
             // words: values that are already there, so the words do not change under the reader.)
             // (launched before or behind the hidden gradient: 9.63 against 9.62 ms -- the order does not matter)
-            bwb_done = true;
-            // (its own bracket on ITS stream: the kernel's span while it shares the chip with the hidden gradient)
-            ProfScope ps("k_mvn_enc_bwd_w_b beside k_mvn_enc_bwd_h_b2", bwb_fork.side());
-            rc = launch_bwb_on(bwb_fork.side());
+            w_done = true;
+            rc = bwd_weights(c, w_fork.side());
             if (rc) return rc;
         } else {
             pair_ps->cancel();                                 // one kernel after the other: each has a bracket of its own
         }
-        if (use_t && p.bwh_t) {
-            const float* WpT = packws + pk.wpT;
-            const size_t lds = bh_lds_bytes(dm.D);
-            rc = set_lds(k_mvn_enc_bwd_h_t, lds);
-            if (rc) return rc;
-            f1t = yT && !rows && yT_stride % 16 == 0 && yT_stride >= nb && aligned16(yT) && cfg->J >= 32 &&
-                  f1_lds_bytes(cfg->J) <= 160 * 1024;
-            if (p.bwhb) {
-                // the unit images: made by the forward call's pack launches (hb_fw: k_pack_fused.hip), or here
-                uint8_t* himg = (uint8_t*)(hb_fw ? const_cast<float*>(packws) + pk.himg : workspace + p.himg);
-                if (!hb_fw) {
-                    hipLaunchKernelGGL(k_pack_heads_hb, dim3(hb_units(dm.D)), dim3(256), 0, st, dm.D, W21, W22, sc, himg, maxw);
-                    VX_CHECK_LAUNCH();
-                }
-                maxw_ready = true;
-                const size_t ldsh = hb_lds_bytes(dm.D);
-                // (beside the head weight gradient the bracket spans both kernels: filed under a name of its own, not priced)
-                ProfScope ps(bwb_done ? "k_mvn_enc_bwd_h_b2 beside k_mvn_enc_bwd_w_b" : "k_mvn_enc_bwd_h_b", st);
-                if (nb <= HB_SPLIT_MAX) {                               // small batch: the eight waves of a workgroup share the units
-                    rc = set_lds(k_mvn_enc_bwd_h_b<true>, ldsh);
-                    if (rc) return rc;
-                    hipLaunchKernelGGL(k_mvn_enc_bwd_h_b<true>, dim3((unsigned)((nb + 31) / 32)), dim3(HB_THREADS), ldsh, st, dm,
-                                       (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT, f1t ? (float*)nullptr : ghpre, hT,
-                                       f1t ? ghpre : (float*)nullptr, maxw);
-                } else if (dm.D <= 112 && hb2_lds_bytes(dm.D) <= 160 * 1024) {
-                    // large batch: 64 persons per wave, batches of four units per barrier (k_mvn_bwd_hb2.hip)
-                    const size_t lds2 = hb2_lds_bytes(dm.D);
-                    constexpr int HNSET = 1;                              // eight waves of 32 persons (k_mvn_bwd_hb2.hip)
-                    rc = set_lds((k_mvn_enc_bwd_h_b2<7, HNSET>), lds2);
-                    if (rc) return rc;
-                    // its workgroups take 256 persons: a last round that fills less than half the chip goes to the 32-persons-
-                    // per-wave kernel instead (1M persons: 15 full rounds + 16 960 persons), as in the forward
-                    const int64_t round2 = (int64_t)256 * num_cu();
-                    const int64_t rem = nb % round2;
-                    const int64_t n_done = (rem > 0 && 2 * rem <= round2 && nb > round2) ? nb - rem : nb;
-                    // the short last round on the second stream beside the whole rounds (launched first), as in the forward
-                    ForkScope tail_fork;
-                    const bool beside = n_done < nb && p.side_streams && tail_fork.fork(side_stream(0, st), st);
-                    const hipStream_t ts = beside ? tail_fork.side() : st;
-                    auto launch_tail = [&]() -> int {
-                        int r = set_lds(k_mvn_enc_bwd_h_b<false>, ldsh);
-                        if (r) return r;
-                        hipLaunchKernelGGL(k_mvn_enc_bwd_h_b<false>, dim3((unsigned)((nb - n_done + 32 * HB_WAVES - 1) / (32 * HB_WAVES))),
-                                           dim3(HB_THREADS), ldsh, ts, dm, (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT,
-                                           f1t ? (float*)nullptr : ghpre, hT, f1t ? ghpre : (float*)nullptr, maxw, n_done);
-                        VX_CHECK_LAUNCH();
-                        return VX_OK;
-                    };
-                    if (beside) {
-                        rc = launch_tail();
-                        if (rc) return rc;                                  // (the scope joins)
-                    }
-                    hipLaunchKernelGGL((k_mvn_enc_bwd_h_b2<7, HNSET>), dim3((unsigned)((n_done + 255) / 256)),
-                                       dim3(64 * HB2_WAVES_OF(HNSET)), lds2, st, dm, (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT,
-                                       f1t ? (float*)nullptr : ghpre, hT, f1t ? ghpre : (float*)nullptr, maxw);
-                    if (beside) {
-                        VX_CHECK_LAUNCH();
-                        rc = tail_fork.join();
-                        if (rc) return rc;
-                    } else if (n_done < nb) {
-                        VX_CHECK_LAUNCH();
-                        rc = launch_tail();
-                        if (rc) return rc;
-                    }
-                } else {
-                    rc = set_lds(k_mvn_enc_bwd_h_b<false>, ldsh);
-                    if (rc) return rc;
-                    hipLaunchKernelGGL(k_mvn_enc_bwd_h_b<false>, dim3((unsigned)((nb + 32 * HB_WAVES - 1) / (32 * HB_WAVES))), dim3(HB_THREADS), ldsh, st, dm,
-                                       (const uint8_t*)himg, sc, h, eps, gxT, (const float*)gdT, f1t ? (float*)nullptr : ghpre, hT,
-                                       f1t ? ghpre : (float*)nullptr, maxw);
-                }
-                VX_CHECK_LAUNCH();
-            } else {
-            ProfScope ps("k_mvn_enc_bwd_h_t", st);
-            hipLaunchKernelGGL(k_mvn_enc_bwd_h_t, dim3((unsigned)((nb + BH_P - 1) / BH_P)), dim3(BH_THREADS), lds, st, dm,
-                               cfg->scale, WpT, gtab, h, eps, ldT, gxT, gdT, f1t ? (float*)nullptr : ghpre, hT,
-                               f1t ? ghpre : (float*)nullptr);
-            VX_CHECK_LAUNCH();
-            }
-        } else {
-            if (!gx) return VX_EINVAL;                     // the person-major kernel needs gx[nb][D]
-            if (hb_fw) {
-                // the forward call packed for the f16x2 hidden gradient and made no packed copy of the heads (k_pack_fused.hip,
-                // direct): this kernel reads one
-                hipLaunchKernelGGL(k_pack_heads, dim3((unsigned)Rp), dim3(64), 0, st, (int)cfg->D, 64, W21, (const float*)nullptr,
-                                   W22, (const float*)nullptr, const_cast<float*>(packws), (float*)nullptr,
-                                   const_cast<uint32_t*>(gtab), (float*)nullptr);
-                VX_CHECK_LAUNCH();
-            }
-            const size_t lds = enc_bwdh_p_lds_floats(dm.D) * sizeof(float);
-            rc = set_lds(k_mvn_enc_bwd_h_p, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_mvn_enc_bwd_h_p, dim3((unsigned)((nb + ENC_P - 1) / ENC_P)), dim3(ENC_THREADS), lds, st,
-                               dm, cfg->scale, Wp, gtab, h, eps, ldT, gx, ghpre);
-            VX_CHECK_LAUNCH();
-        }
-        if (nb > 0 && f1t && p.fc1_16 && p.side_streams && f1_fork.fork(side_stream(0, st), st)) {
-            // the fc1 weight gradient needs ghpre only: it runs on a second stream beside the head weight gradient below
-            // (0.33 ms of a 1M step that used to follow it) and is joined before this call returns (also on an error return)
-            const hipStream_t fs = f1_fork.side();
-            {
-                rc = launch_fc1_c(fs);                                  // operands through LDS (k_fc1_bwd_c.hip)
-                if (rc) return rc;
-            }
-            rc = vx_reduce_slabs(slabs_f, n_prf, lenf, -1.0f, genc, (void*)fs);
-            if (rc) return rc;
-            f1_done = true;
-        }
-        if (bwb_done) {
-            rc = bwb_fork.join();
-            if (rc) return rc;
-            pair_ps.reset();                                   // the launch stream is behind both kernels here
-        } else if (use_t && p.bwb) {
-            if (!(gd_ready & 2)) {                             // bit 1: the forward call already wrote the fp16 terms of hT here
-                hipLaunchKernelGGL(k_split2_f16, dim3(num_cu() * 8), dim3(256), 0, st, hT, nb * 64, packws + pk.hscale, hs3);
-                VX_CHECK_LAUNCH();
-            }
-            if (!maxw_ready) {                                 // the operand maxima, normally collected by k_mvn_enc_bwd_h_b
-                hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(64), 0, st, maxw, 4);
-                hipLaunchKernelGGL(k_absmax3, dim3(grid_1d(nb * cfg->D, 1024)), dim3(256), 0, st, gxT, (const float*)gdT, epsT, nb * D, maxw);
-                VX_CHECK_LAUNCH();
-            }
-            ProfScope ps("k_mvn_enc_bwd_w_b", st);
-            rc = launch_bwb_on(st);
-            if (rc) return rc;
-        } else if (use_t) {
-            size_t lds = bt_lds_bytes(dm.D);
-            const int n_jg1 = (int)((cfg->J + 127) / 128);
-            if (!f1_done && !f1t && dm.Hp == 64 && (int64_t)n_jg * n_prf * 16 <= num_cu() && BT_THREADS == ENC_THREADS) {
-                // a small batch: the fc1 weight gradient (k_fc1_bwd<2, 1>) rides in the same launch (k_bwd_wt_fc1)
-                const size_t ldsf = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
-                if (ldsf > lds) lds = ldsf;
-                rc = set_lds(k_bwd_wt_fc1, lds);
-                if (rc) return rc;
-                const int f1fast = f1fast_ok(cfg, ghpre, y);
-                ProfScope ps("k_mvn_enc_bwd_w_t + k_fc1_bwd", st);
-                hipLaunchKernelGGL(k_bwd_wt_fc1, dim3((unsigned)(n_rowslabs * n_prw + n_jg1 * n_prf)), dim3(BT_THREADS), lds, st, dm, hT,
-                                   epsT, (const float*)gdT, gxT, gtab, slabs_w, Rp * (H + 1), n_rowslabs, n_prw, y, rows,
-                                   (const float*)ghpre, slabs_f, lenf, f1fast, n_jg1, n_prf);
-                VX_CHECK_LAUNCH();
-                f1_launched = true;
-            } else {
-                rc = set_lds(k_mvn_enc_bwd_w_t, lds);
-                if (rc) return rc;
-                ProfScope ps("k_mvn_enc_bwd_w_t", st);
-                hipLaunchKernelGGL(k_mvn_enc_bwd_w_t, dim3((unsigned)n_rowslabs, (unsigned)n_prw), dim3(BT_THREADS), lds, st,
-                                   dm, hT, epsT, gdT, gxT, gtab, slabs_w, Rp * (H + 1));
-                VX_CHECK_LAUNCH();
-            }
-        } else {
-            const size_t lds = enc_bwdw_fast_lds_floats(dm.D) * sizeof(float);
-            rc = set_lds(k_mvn_enc_bwd_w_fast<true>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_mvn_enc_bwd_w_fast<true>, dim3((unsigned)n_rowslabs, (unsigned)n_prw), dim3(ENC_THREADS),
-                               lds, st, dm, cfg->scale, h, eps, ldT, gx, gtab, slabs_w, Rp * (H + 1));
-            VX_CHECK_LAUNCH();
-        }
     }
-    const bool fast = !packed && p.encb_fast && aligned16(W21) && aligned16(W22) && aligned16(h) && aligned16(eps) &&
-                      aligned16(gx) && aligned16(ghpre);
-    if (nb > 0 && fast) {
-        {
-            const size_t lds = enc_bwdh_fast_lds_floats(dm.D) * sizeof(float);
-            rc = set_lds(k_mvn_enc_bwd_h_fast, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_mvn_enc_bwd_h_fast, dim3((unsigned)((nb + ENC_P - 1) / ENC_P)), dim3(ENC_THREADS), lds,
-                               st, dm, cfg->scale, W21, W22, h, eps, ldT, gx, ghpre);
-            VX_CHECK_LAUNCH();
-        }
-        {
-            const size_t lds = enc_bwdw_fast_lds_floats(dm.D) * sizeof(float);
-            rc = set_lds(k_mvn_enc_bwd_w_fast<false>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_mvn_enc_bwd_w_fast<false>, dim3((unsigned)n_rowslabs, (unsigned)n_prw), dim3(ENC_THREADS),
-                               lds, st, dm, cfg->scale, h, eps, ldT, gx, (const uint32_t*)nullptr, slabs_w, lenw);
-            VX_CHECK_LAUNCH();
-        }
-    } else if (nb > 0 && !packed) {
-        // the plan may have assumed the fast row-slab size (misaligned buffers): re-derive for this kernel
-        n_rowslabs = (int)(((int64_t)dm.T + dm.D + BW_ROWS - 1) / BW_ROWS);
-        {
-            const size_t lds = enc_bwdh_lds_floats(dm.D, dm.Hp) * sizeof(float);
-            const dim3 grid((unsigned)((nb + ENC_P - 1) / ENC_P));
-#define LAUNCH_BH(HT)                                                                                        \
-    rc = set_lds(k_mvn_enc_bwd_h<HT>, lds);                                                                  \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_mvn_enc_bwd_h<HT>, grid, dim3(ENC_THREADS), lds, st, dm, cfg->scale, W21, W22, h, eps, \
-                       ldT, gx, ghpre)
-            if (dm.Hp == 32) { LAUNCH_BH(1); } else if (dm.Hp == 64) { LAUNCH_BH(2); } else if (dm.Hp == 96) { LAUNCH_BH(3); } else { LAUNCH_BH(4); }
-#undef LAUNCH_BH
-            VX_CHECK_LAUNCH();
-        }
-        {
-            const size_t lds = enc_bwdw_lds_floats(dm.D, dm.Hp) * sizeof(float);
-            const dim3 grid((unsigned)n_rowslabs, (unsigned)n_prw);
-#define LAUNCH_BW(HT)                                                                                        \
-    rc = set_lds(k_mvn_enc_bwd_w<HT>, lds);                                                                  \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_mvn_enc_bwd_w<HT>, grid, dim3(ENC_THREADS), lds, st, dm, cfg->scale, h, eps, ldT, gx,  \
-                       slabs_w, lenw)
-            if (dm.Hp == 32) { LAUNCH_BW(1); } else if (dm.Hp == 64) { LAUNCH_BW(2); } else if (dm.Hp == 96) { LAUNCH_BW(3); } else { LAUNCH_BW(4); }
-#undef LAUNCH_BW
-            VX_CHECK_LAUNCH();
-        }
+    rc = bwd_hidden(c, w_done);
+    if (rc) return rc;
+    if (rt.fc1_side && f1_fork.fork(side_stream(0, st), st)) {
+        // the fc1 weight gradient needs ghpre only: it runs on a second stream beside the head weight gradient below
+        // (0.33 ms of a 1M step that used to follow it) and is joined before this call returns (also on an error return)
+        rc = bwd_fc1(c, f1_fork.side());
+        if (rc) return rc;
+        rc = vx_reduce_slabs(c.slabs_f, p.n_prf, p.lenf, -1.0f, a.genc, (void*)f1_fork.side());
+        if (rc) return rc;
+        f1_done = true;
     }
-    if (f1_done || f1_launched) {
-        // (joined below | launched with the head weight gradient: its slabs are summed below)
-    } else if (nb > 0 && f1t && p.fc1_16) {
-        rc = launch_fc1_c(st);
+    if (w_done) {
+        rc = w_fork.join();
         if (rc) return rc;
-    } else if (nb > 0 && f1t) {
-        const size_t lds = f1_lds_bytes(cfg->J);
-        rc = set_lds(k_fc1_bwd_t, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_fc1_bwd_t, dim3((unsigned)((cfg->J + 511) / 512), (unsigned)n_prf), dim3(F1_THREADS), lds, st, dm,
-                           yT, yT_stride, ghpre, slabs_f, lenf);
-        VX_CHECK_LAUNCH();
-    } else if (nb > 0) {
-        {
-            const size_t lds = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
-            const dim3 grid((unsigned)n_jg, (unsigned)n_prf);
-            const int f1fast = f1fast_ok(cfg, ghpre, y);
-#define LAUNCH_F1(HT)                                                                                        \
-    rc = set_lds(k_fc1_bwd<HT>, lds);                                                                        \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_fc1_bwd<HT>, grid, dim3(ENC_THREADS), lds, st, dm, y, rows, ghpre, slabs_f, lenf, f1fast)
-            if (dm.Hp == 64 && (int64_t)n_jg * n_prf * 16 <= num_cu()) {
-                // a small batch (the reference's B = 100: two person tiles): 128 items a workgroup instead of 512 -- four times the
-                // workgroups, a quarter of the MFMA chain, the response words and the slab piece each
-                rc = set_lds((k_fc1_bwd<2, 1>), lds);
-                if (rc) return rc;
-                hipLaunchKernelGGL((k_fc1_bwd<2, 1>), dim3((unsigned)((cfg->J + 127) / 128), (unsigned)n_prf), dim3(ENC_THREADS), lds, st, dm, y,
-                                   rows, ghpre, slabs_f, lenf, f1fast);
-            } else if (dm.Hp == 32) { LAUNCH_F1(1); } else if (dm.Hp == 64) { LAUNCH_F1(2); } else if (dm.Hp == 96) { LAUNCH_F1(3); } else { LAUNCH_F1(4); }
-#undef LAUNCH_F1
-            VX_CHECK_LAUNCH();
-        }
+        pair_ps.reset();                                   // the launch stream is behind both kernels here
     } else {
-        hipError_t he = hipMemsetAsync(slabs_w, 0, sizeof(float) * (size_t)(n_prw * lenw + n_prf * lenf), st);
-        if (he != hipSuccess) return (int)he;
+        rc = bwd_weights(c, st);
+        if (rc) return rc;
     }
-    // flat encoder-gradient layout = nn.Linear order: [W1 | b1 | W21 | b21 | W22 | b22]; loss grads = -dELBO
     if (f1_done) {
         rc = f1_fork.join();                               // the fc1 gradient is in genc
         if (rc) return rc;
-    }
-    if (packed) {
-        // ONE launch ends the call (k_enc_bwd_tail): the head gradients back in the reference layout, the fc1 slabs summed
-        // (unless the side stream did), the loss of a small batch -- three launches of ~5 us until round 5
-        const int n_unpack = (int)((Rp + 3) / 4);
-        const int n_f1 = f1_done ? 0 : grid_1d(lenf, 64);
-        const bool loss_here = tail && nb <= 4096;
-        hipLaunchKernelGGL(k_enc_bwd_tail, dim3((unsigned)(n_unpack + n_f1 + (loss_here ? 1 : 0))), dim3(256), 0, st, (int)D, (int)H,
-                           slabs_w, n_prw, Rp * (H + 1), -1.0f, genc + lenf, n_unpack, (const float*)slabs_f, (int64_t)n_prf, lenf,
-                           genc, n_f1, loss_here ? tail->ll : nullptr, loss_here ? tail->ent : nullptr, nb,
-                           loss_here ? tail->alpha : 0.f, loss_here ? tail->loss : nullptr, loss_here ? tail->sum_ws : nullptr,
-                           loss_here ? const_cast<uint32_t*>(cfg->step_dev) : nullptr);
-        VX_CHECK_LAUNCH();
-        if (tail && !loss_here) return vx_sum2(tail->ll, tail->ent, nb, tail->alpha, tail->loss, tail->sum_ws, const_cast<uint32_t*>(cfg->step_dev), hs);
-        return VX_OK;
-    }
-    if (!f1_done) {
-        rc = vx_reduce_slabs(slabs_f, n_prf, lenf, -1.0f, genc, hs);
+    } else {
+        rc = bwd_fc1(c, st);
         if (rc) return rc;
     }
-    rc = vx_reduce_slabs(slabs_w, n_prw, p.lenw_ref, -1.0f, genc + lenf, hs);
-    if (rc) return rc;
-    if (tail) return vx_sum2(tail->ll, tail->ent, nb, tail->alpha, tail->loss, tail->sum_ws, const_cast<uint32_t*>(cfg->step_dev), hs);
-    return VX_OK;
+    return bwd_tail(c, f1_done);
 }
 
 int vx_mvn_enc_backward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb,
                         const float* W21, const float* W22, const float* h, const float* eps, const float* ldT,
                         const float* gx, const float* hT, const float* epsT, const float* gxT, const uint8_t* yT,
                         int64_t yT_stride, float* genc, float* workspace, const float* packws, int32_t gd_ready, void* hs) {
-    return mvn_enc_backward_impl(cfg, y, rows, nb, W21, W22, h, eps, ldT, gx, hT, epsT, gxT, yT, yT_stride, genc, workspace,
-                                 packws, gd_ready, hs, nullptr);
+    return mvn_enc_backward_impl(cfg, BwdArgs{y, rows, nb, W21, W22, h, eps, ldT, gx, hT, epsT, gxT, yT, yT_stride, genc, workspace,
+                                              packws, gd_ready, nullptr}, hs);
 }
 
 int vx_mvn_enc_backward_loss(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb,
@@ -1526,8 +1583,8 @@ int vx_mvn_enc_backward_loss(const vx_irt_cfg* cfg, const uint8_t* y, const int6
                              const float* ll, const float* ent, float loss_alpha, float* loss, float* sum_workspace, void* hs) {
     if (!ll || !ent || !loss || !sum_workspace) return VX_EINVAL;
     const LossTail tail{ll, ent, loss_alpha, loss, sum_workspace};
-    return mvn_enc_backward_impl(cfg, y, rows, nb, W21, W22, h, eps, ldT, gx, hT, epsT, gxT, yT, yT_stride, genc, workspace,
-                                 packws, gd_ready, hs, &tail);
+    return mvn_enc_backward_impl(cfg, BwdArgs{y, rows, nb, W21, W22, h, eps, ldT, gx, hT, epsT, gxT, yT, yT_stride, genc, workspace,
+                                              packws, gd_ready, &tail}, hs);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1877,7 +1934,6 @@ int vx_norm_enc_forward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* 
     if (nb == 0) return VX_OK;
     EncDims dm;
     dm.D = 1; dm.J = cfg->J; dm.H = cfg->H; dm.Hp = (cfg->H + 31) / 32 * 32; dm.DS = 3; dm.T = 1; dm.nb = nb;
-    int rc;
     if (packws && nb >= NH_MIN_PERSONS && nenc_h_shape(cfg) && aligned16(packws) && aligned16(y) && aligned16(W1) &&
         aligned16(b1) && aligned16(h)) {
         uint8_t* w1img = (uint8_t*)packws;
@@ -1889,47 +1945,28 @@ int vx_norm_enc_forward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* 
         hipLaunchKernelGGL(k_norm_pack_w1, dim3((unsigned)n_ks), dim3(256), 0, (hipStream_t)hs, (int)cfg->J, W1, (const float*)part, sc,
                            w1img);
         VX_CHECK_LAUNCH();
-        const size_t ldsh = nh_lds_bytes<NH_NP>(cfg->J);
-        rc = set_lds((k_norm_enc_fwd_h<NH_NP, NH_PF>), ldsh);
-        if (rc) return rc;
         ProfScope ps("k_norm_enc_fwd_h", (hipStream_t)hs);
-        hipLaunchKernelGGL((k_norm_enc_fwd_h<NH_NP, NH_PF>), dim3((unsigned)((nb + 127) / 128)), dim3(64 * (4 / NH_NP)), ldsh,
-                           (hipStream_t)hs, dm, y, rows, (const uint8_t*)w1img, (const float*)sc, b1, W21, b21, W22, b22, h, loc, raw);
-        VX_CHECK_LAUNCH();
-        return VX_OK;
+        return launch_lds(k_norm_enc_fwd_h<NH_NP, NH_PF>, dim3((unsigned)((nb + 127) / 128)), dim3(64 * (4 / NH_NP)), nh_lds_bytes<NH_NP>(cfg->J),
+                          (hipStream_t)hs, dm, y, rows, (const uint8_t*)w1img, (const float*)sc, b1, W21, b21, W22, b22, h, loc, raw);
     }
     if (!force_generic() && seams().fwd16 && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(y) && aligned16(W1) &&
         aligned16(b1) && aligned16(h) && nb_lds_bytes(cfg->J) <= 160 * 1024) {
-        const size_t ldsb = nb_lds_bytes(cfg->J);                       // fc1 on the bf16 MFMA, W1 shared by the workgroup
-        rc = set_lds(k_norm_enc_fwd_b, ldsb);
-        if (rc) return rc;
-        ProfScope ps("k_norm_enc_fwd_b", (hipStream_t)hs);
-        hipLaunchKernelGGL(k_norm_enc_fwd_b, dim3((unsigned)((nb + NB_WAVES * EP_WP - 1) / (NB_WAVES * EP_WP))),
-                           dim3(NB_THREADS), ldsb, (hipStream_t)hs, dm, y, rows, W1, b1, W21, b21, W22, b22, h, loc, raw);
-        VX_CHECK_LAUNCH();
-        return VX_OK;
+        ProfScope ps("k_norm_enc_fwd_b", (hipStream_t)hs);                // fc1 on the bf16 MFMA, W1 shared by the workgroup
+        return launch_lds(k_norm_enc_fwd_b, dim3((unsigned)((nb + NB_WAVES * EP_WP - 1) / (NB_WAVES * EP_WP))), dim3(NB_THREADS),
+                          nb_lds_bytes(cfg->J), (hipStream_t)hs, dm, y, rows, W1, b1, W21, b21, W22, b22, h, loc, raw);
     }
     if (!force_generic() && cfg->H == 64 && cfg->J % 4 == 0 && aligned16(y) && aligned16(W1) && aligned16(b1) &&
         aligned16(h) && NE_WAVES * norm_fast_wave_floats(cfg->J) * sizeof(float) <= 160 * 1024) {
-        const size_t ldsf = NE_WAVES * norm_fast_wave_floats(cfg->J) * sizeof(float);
-        rc = set_lds(k_norm_enc_fwd_fast, ldsf);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_norm_enc_fwd_fast, dim3((unsigned)((nb + NE_WAVES * EP_WP - 1) / (NE_WAVES * EP_WP))),
-                           dim3(NE_THREADS), ldsf, (hipStream_t)hs, dm, y, rows, W1, b1, W21, b21, W22, b22, h, loc, raw);
-        VX_CHECK_LAUNCH();
-        return VX_OK;
+        return launch_lds(k_norm_enc_fwd_fast, dim3((unsigned)((nb + NE_WAVES * EP_WP - 1) / (NE_WAVES * EP_WP))), dim3(NE_THREADS),
+                          NE_WAVES * norm_fast_wave_floats(cfg->J) * sizeof(float), (hipStream_t)hs, dm, y, rows, W1, b1, W21, b21, W22,
+                          b22, h, loc, raw);
     }
     const size_t lds = norm_enc_fwd_lds_floats(dm.Hp) * sizeof(float);
     const dim3 grid((unsigned)((nb + ENC_P - 1) / ENC_P));
-#define LAUNCH_NF(HT)                                                                                        \
-    rc = set_lds(k_norm_enc_fwd<HT>, lds);                                                                   \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_norm_enc_fwd<HT>, grid, dim3(ENC_THREADS), lds, (hipStream_t)hs, dm, y, rows, W1, b1, W21,  \
-                       b21, W22, b22, h, loc, raw)
-    if (dm.Hp == 32) { LAUNCH_NF(1); } else if (dm.Hp == 64) { LAUNCH_NF(2); } else if (dm.Hp == 96) { LAUNCH_NF(3); } else { LAUNCH_NF(4); }
-#undef LAUNCH_NF
-    VX_CHECK_LAUNCH();
-    return VX_OK;
+    return with_hidden_width(dm.Hp, [&](auto ht) -> int {
+        return launch_lds(k_norm_enc_fwd<decltype(ht)::value>, grid, dim3(ENC_THREADS), lds, (hipStream_t)hs, dm, y, rows, W1, b1, W21, b21,
+                          W22, b22, h, loc, raw);
+    });
 }
 
 int64_t vx_norm_enc_bwd_workspace_floats(const vx_irt_cfg* cfg, int64_t nb) {
@@ -1989,22 +2026,9 @@ int vx_norm_enc_backward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t*
         hipLaunchKernelGGL(k_norm_enc_bwd_small, dim3(nblk), dim3(256), 2 * 256 * sizeof(float), st, (int)H, nb, W21, W22,
                            h, gloc, graw, ghpre, slabs_h);
         VX_CHECK_LAUNCH();
-        const size_t lds = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
-        const dim3 grid((unsigned)n_jg, (unsigned)n_prf);
-        const int f1fast = f1fast_ok(cfg, ghpre, y);
-#define LAUNCH_F1(HT)                                                                                        \
-    rc = set_lds(k_fc1_bwd<HT>, lds);                                                                        \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_fc1_bwd<HT>, grid, dim3(ENC_THREADS), lds, st, dm, y, rows, ghpre, slabs_f, lenf, f1fast)
-        if (dm.Hp == 64 && (int64_t)n_jg * n_prf * 16 <= num_cu()) {
-            // a small batch: 128 items a workgroup instead of 512 (the form the multivariate guide's small batches take above)
-            rc = set_lds((k_fc1_bwd<2, 1>), lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_fc1_bwd<2, 1>), dim3((unsigned)((cfg->J + 127) / 128), (unsigned)n_prf), dim3(ENC_THREADS), lds, st, dm, y,
-                               rows, ghpre, slabs_f, lenf, f1fast);
-        } else if (dm.Hp == 32) { LAUNCH_F1(1); } else if (dm.Hp == 64) { LAUNCH_F1(2); } else if (dm.Hp == 96) { LAUNCH_F1(3); } else { LAUNCH_F1(4); }
-#undef LAUNCH_F1
-        VX_CHECK_LAUNCH();
+        // (a small batch: 128 items a workgroup, the form the multivariate guide's small batches take above)
+        rc = fc1_bwd_person_major(dm, fc1_small_batch(dm.Hp, n_jg, n_prf), n_jg, n_prf, y, rows, ghpre, slabs_f, lenf, f1fast_ok(cfg, ghpre, y), st);
+        if (rc) return rc;
     }
     rc = vx_reduce_slabs(slabs_f, n_prf, lenf, -1.0f, genc, hs);
     if (rc) return rc;
@@ -2334,22 +2358,9 @@ int vx_bin_enc_backward(const vx_hodina_cfg* cfg, const uint8_t* y, const int64_
         VX_CHECK_LAUNCH();
         EncDims dm;
         dm.D = 1; dm.J = cfg->J; dm.H = cfg->H; dm.Hp = (cfg->H + 31) / 32 * 32; dm.DS = 3; dm.T = 1; dm.nb = nb;
-        const size_t lds = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
-        const dim3 grid((unsigned)n_jg, (unsigned)n_prf);
-        int rc;
-#define LAUNCH_F1(HT)                                                                                        \
-    rc = set_lds(k_fc1_bwd<HT>, lds);                                                                        \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_fc1_bwd<HT>, grid, dim3(ENC_THREADS), lds, st, dm, y, rows, ghpre, slabs_f, lenf, 0)
-        if (dm.Hp == 64 && (int64_t)n_jg * n_prf * 16 <= num_cu()) {
-            // a small batch: 128 items a workgroup instead of 512 (the form the multivariate guide's small batches take above)
-            rc = set_lds((k_fc1_bwd<2, 1>), lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_fc1_bwd<2, 1>), dim3((unsigned)((cfg->J + 127) / 128), (unsigned)n_prf), dim3(ENC_THREADS), lds, st, dm, y,
-                               rows, ghpre, slabs_f, lenf, 0);
-        } else if (dm.Hp == 32) { LAUNCH_F1(1); } else if (dm.Hp == 64) { LAUNCH_F1(2); } else if (dm.Hp == 96) { LAUNCH_F1(3); } else { LAUNCH_F1(4); }
-#undef LAUNCH_F1
-        VX_CHECK_LAUNCH();
+        // (a small batch: 128 items a workgroup, the form the multivariate guide's small batches take above)
+        const int rc = fc1_bwd_person_major(dm, fc1_small_batch(dm.Hp, n_jg, n_prf), n_jg, n_prf, y, rows, ghpre, slabs_f, lenf, 0, st);
+        if (rc) return rc;
     }
     // flat layout = nn.Linear order of BinEncoder (vi.py:462-463): [W1 | b1 | W2 | b2]; ghpre already is d LOSS
     int rc2 = vx_reduce_slabs(slabs_f, n_prf, lenf, 1.0f, genc, hs);
@@ -2535,22 +2546,9 @@ int vx_sm_enc_backward(const vx_hodina_cfg* cfg, const uint8_t* y, const int64_t
         VX_CHECK_LAUNCH();
         EncDims dm;
         dm.D = 1; dm.J = cfg->J; dm.H = cfg->H; dm.Hp = (cfg->H + 31) / 32 * 32; dm.DS = 3; dm.T = 1; dm.nb = nb;
-        const size_t lds = fc1_bwd_lds_floats(dm.Hp) * sizeof(float);
-        const dim3 grid((unsigned)n_jg, (unsigned)n_prf);
-        int rc;
-#define LAUNCH_F1(HT)                                                                                        \
-    rc = set_lds(k_fc1_bwd<HT>, lds);                                                                        \
-    if (rc) return rc;                                                                                       \
-    hipLaunchKernelGGL(k_fc1_bwd<HT>, grid, dim3(ENC_THREADS), lds, st, dm, y, rows, ghpre, slabs_f, lenf, 0)
-        if (dm.Hp == 64 && (int64_t)n_jg * n_prf * 16 <= num_cu()) {
-            // a small batch: 128 items a workgroup instead of 512 (the form the multivariate guide's small batches take above)
-            rc = set_lds((k_fc1_bwd<2, 1>), lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_fc1_bwd<2, 1>), dim3((unsigned)((cfg->J + 127) / 128), (unsigned)n_prf), dim3(ENC_THREADS), lds, st, dm, y,
-                               rows, ghpre, slabs_f, lenf, 0);
-        } else if (dm.Hp == 32) { LAUNCH_F1(1); } else if (dm.Hp == 64) { LAUNCH_F1(2); } else if (dm.Hp == 96) { LAUNCH_F1(3); } else { LAUNCH_F1(4); }
-#undef LAUNCH_F1
-        VX_CHECK_LAUNCH();
+        // (a small batch: 128 items a workgroup, the form the multivariate guide's small batches take above)
+        const int rc = fc1_bwd_person_major(dm, fc1_small_batch(dm.Hp, n_jg, n_prf), n_jg, n_prf, y, rows, ghpre, slabs_f, lenf, 0, st);
+        if (rc) return rc;
     }
     // gz / ghpre are d ELBO: loss gradients = -(.)   flat layout [W1 | b1 | W2 | b2] (SoftmaxEncoder, vi.py:477-478)
     int rc2 = vx_reduce_slabs(slabs_f, n_prf, lenf, -1.0f, genc, hs);
