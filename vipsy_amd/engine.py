@@ -9,6 +9,7 @@ is in the HIP kernels behind vipsy_amd/_hip.py.
 import ctypes
 import os
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -504,11 +505,12 @@ class _EngineBase(object):
         """What every constructor starts with: the backend, this rank's shard of the responses and where it sits among the
         n_global persons."""
         self.be = backend if backend is not None else HipBackend()
+        self._hip = isinstance(self.be, HipBackend)     # asked once: the CPU rehearsal backends of tests/ take narrower calls
         self.y = y_u8.contiguous()
         assert self.y.dtype == torch.uint8 and self.y.dim() == 2
         self.dev = self.y.device
         self.n_local, self.J = self.y.shape
-        self.y_lik = None                    # the copy the likelihood reads when it is not self.y (IrtEngine.__init__)
+        self.y_lik = None                    # the copy the likelihood reads when it is not self.y (IrtEngine._decide_shapes)
         self.N = int(n_global) if n_global is not None else self.n_local
         self.gid0 = int(gid0)
         self.seed, self.group = int(seed), group
@@ -532,6 +534,15 @@ class _EngineBase(object):
             o += int(np.prod(shp))
         self.n_enc = o - self.enc_off0
         return o
+
+    def _fill_encoder(self, init, J, H):
+        """The encoder's initial values `init`, given over J items and H hidden units, into segments that may be larger: zeros
+        behind them in every tensor -- phantom items are zero columns of fc1.weight, phantom hidden units zero rows of fc1 and
+        zero columns of the heads, phantom dimensions zero rows of the heads."""
+        for k, full in self.enc_shapes.items():
+            w = torch.as_tensor(init[k], dtype=torch.float32)
+            w = w.reshape((H, J) if k == "fc1.weight" else (-1, H) if k.endswith("weight") else (-1,))
+            self.view("encoder$$$" + k).copy_(_grown(w, full).reshape(-1))
 
     def _init_g_s(self):
         """g = s = 0.1 through the interval(0, 1) transform (vi.py:748-749, 844-845, 875-876, 901-904)."""
@@ -616,7 +627,7 @@ class _EngineBase(object):
 
     def _padded_y(self, lik=False):
         """The responses with the phantom persons of _pad_persons appended (made once; the responses themselves when none
-        are).  lik: the copy the likelihood reads (phantom ITEMS absent instead of zero, IrtEngine.__init__)."""
+        are).  lik: the copy the likelihood reads (phantom ITEMS absent instead of zero, IrtEngine._decide_shapes)."""
         y = self.y_lik if (lik and self.y_lik is not None) else self.y
         n_pad = self._n_pad
         if n_pad == self.n_local:
@@ -770,8 +781,7 @@ class _EngineBase(object):
         by_hyper, pp_hyper = self._optim_segments(lrs)
         sd = self._step_dev
         kw = {"t_dev": sd} if sd is not None else {}         # captured step: Adam's t = the (already advanced) device counter
-        hip = isinstance(self.be, HipBackend)
-        if hip:                                              # the first optimiser launch also files the step's loss in the ring
+        if self._hip:                                        # the first optimiser launch also files the step's loss in the ring
             kw["loss"] = (self.G[self.n_params:self.n_params + 1], self.loss_ring)
         if len(by_hyper) == 1 and len(pp_hyper) == 1 and list(by_hyper) == list(pp_hyper):
             (betas, eps), segs = next(iter(by_hyper.items()))          # the usual case: one launch for both buffers
@@ -786,7 +796,7 @@ class _EngineBase(object):
             for (betas, eps), segs in pp_hyper.items():
                 self.be.adam(self.PP, self.GP, self.MP, self.VP, None, self.pp_len, _merge_segments(segs), self.t, betas, eps, **kw)
                 kw.pop("loss", None)
-        if not hip or "loss" in kw:
+        if not self._hip or "loss" in kw:
             # the CPU rehearsal backends of tests/ -- or a HIP step that launched no optimiser kernel at all (no trainable
             # segment): nothing filed the loss, so it is copied into its slot here
             self.loss_ring[self.t % LOSS_RING] = self.G[self.n_params]
@@ -845,7 +855,7 @@ class _EngineBase(object):
     def _graph_mode(self, rows, b_global, eps, S):
         """The captured form this call can replay -- ('full' | 'rows', nb, b_global) and, with S > 1 particles, S as a fourth
         entry -- or None for an eager step."""
-        if not (self.use_graph and eps is None and self.events is None and isinstance(self.be, HipBackend)):
+        if not (self.use_graph and eps is None and self.events is None and self._hip):
             return None
         if S > 1:
             # Trace_ELBO(num_particles = S) (test.py:430: 20, test.py:607: 10): the S passes, their accumulation and the one
@@ -1187,13 +1197,42 @@ class _EngineBase(object):
                 sd.sub_(1)
         self._mean_of_passes(S, one_pass)
 
-    def _score_baseline(self, baseline_buf, guide_grads):
-        """(control variate, decay rate or -1, indexed-by-row flag) of the score-function estimator for this pass."""
+    def _score_pass(self, key, nb, stream_id, baseline_buf, guide_grads):
+        """What a pass of the score-function estimator hands its kernel: (log_r, control variate, decay rate or -1,
+        indexed-by-row flag).  log_r is buffer `key` -- in the first pass of 'loo' (guide_grads False) one per particle -- and
+        is recorded as self.last_log_r; baseline_buf: the leave-one-out means of 'loo's second pass."""
+        log_r = self.last_log_r = self._buf("%s%d" % (key, stream_id) if not guide_grads else key, nb)
         if baseline_buf is not None:
-            return baseline_buf, -1.0, 0
+            return log_r, baseline_buf, -1.0, 0
         if self.baseline == "avg":
-            return self.base, (self.baseline_beta if guide_grads else -1.0), 1
-        return None, -1.0, 0
+            return log_r, self.base, (self.baseline_beta if guide_grads else -1.0), 1
+        return log_r, None, -1.0, 0
+
+    # -- the 1-D normal encoder (NormEncoder, vi.py:417-455) in front of a step kernel: IrtEngine x_feature == 1, HoDinaEngine --
+    def _norm_enc_forward(self, cfg, y, rows, nb):
+        """The encoder's forward call over nb persons of y; returns what the backward call takes up again: the arguments the two
+        share, fw = {h, loc, raw [, packws]}, the gradient targets gloc / graw the step kernel fills in between, the workspace."""
+        fw = {"h": self._buf("h", nb * self.H), "loc": self._buf("loc", nb), "raw": self._buf("raw", nb)}
+        n_pk = self.be.norm_enc_pack_floats(cfg)
+        if n_pk > 0:
+            fw["packws"] = self._buf("nenc_packws", n_pk)            # the forward's fp16-pair images of W1 (large batches)
+        ne = SimpleNamespace(args=(cfg, y, rows, nb, self._enc()), fw=fw, gloc=self._buf("gloc", nb), graw=self._buf("graw", nb),
+                             ws=self._buf("nencb_ws", self.be.norm_enc_bwd_workspace(cfg, nb)))
+        with self._phase("guide_forward"):
+            self.be.norm_enc_forward(*ne.args, fw)
+        return ne
+
+    def _norm_enc_backward(self, ne, yT):
+        """... and its backward call (inside the caller's guide_backward phase); yT: the item-major responses, or None."""
+        self.be.norm_enc_backward(*ne.args, ne.fw["h"], ne.gloc, ne.graw, self.G[self.enc_off0:self.enc_off0 + self.n_enc],
+                                  ne.ws, yT=yT)
+
+    def _zero_phantom_unit_grads(self):
+        """Phantom hidden units of a three-layer encoder (fc1, two heads): their activation is softplus(0) = log 2, not zero,
+        so their COLUMNS of both heads' weight gradients are zeroed behind the backward call and the columns stay zero."""
+        if self.amortized and self.H != self.H_model:
+            for k in ("fc21.weight", "fc22.weight"):
+                self.view("encoder$$$" + k, self.G).view(-1, self.H)[:, self.H_model:].zero_()
 
     def _loo_step(self, lrs, rows, b_global, eps, S):
         """A step with the leave-one-out control variate of the score-function estimator (baseline 'loo', S >= 2 particles
@@ -1275,6 +1314,15 @@ class IrtEngine(_EngineBase):
 
     Flat parameter buffer: [a: D*J | b: J | c_un: J | d_un: J | encoder (nn.Linear order, amortized only)]."""
 
+    # test seams, read from the environment once at import; an instance attribute overrides one (eng.pad_batch = False)
+    pad_items = os.environ.get("VX_PAD_ITEMS", "1") != "0"          # 0 = the kernels see the problem's own item count
+    pad_hidden = os.environ.get("VX_PAD_HIDDEN", "1") != "0"        # 0 = the kernels see the encoder's own width
+    pad_dims = os.environ.get("VX_PAD_DIMS", "1") != "0"            # 0 = the kernels see the model's own dimensions
+    pad_persons = os.environ.get("VX_PAD_PERSONS", "1") != "0"      # 0 = a full batch is launched over the shard's own count
+    pad_batch = os.environ.get("VX_PAD_BATCH", "1") != "0"          # 0 = a subsample is launched over its own size
+    score_mfma = os.environ.get("VX_SCORE_MFMA", "1") != "0"        # 0 = the scalar score-operand kernel for every shape
+    graph_max_persons = int(os.environ.get("VX_GRAPH_MAX_PERSONS", str(1 << 40)))    # (_replayable)
+
     def __init__(self, y_u8, model="irt_2pl", D=1, Dc=1.0, n_global=None, gid0=0, amortized=False, H=64,
                  share_cov=False, a_free=None, a0=None, b0=None, encoder_init=None, seed=1234, group=None,
                  backend=None, observed_lists=True, estimator="pathwise", baseline="none", baseline_beta=0.9):
@@ -1293,44 +1341,8 @@ class IrtEngine(_EngineBase):
         self.estimator, self.baseline, self.baseline_beta = estimator, baseline, float(baseline_beta)
         self._preamble(y_u8, backend, n_global, gid0, seed, group)
         self.observed_lists = bool(observed_lists) and estimator == "pathwise"
-        self.J_items = self.J
-        self.H_model = int(H) if amortized else 0                  # the encoder's hidden units; self.H: what the kernels see
-        if amortized and 0 < int(H) < 64 and isinstance(self.be, HipBackend) and self.pad_hidden:
-            # PHANTOM HIDDEN UNITS up to 64, the width the MFMA kernels are built for (hidden_dim 32: 23.6 ms a step where 64
-            # takes 2.4, tools/hidden_cliffs.py).  A phantom unit has a zero row of fc1 (weight and bias) and zero columns in
-            # both heads.  Its activation is softplus(0) = log 2, not zero (vi.py:430,447), so the heads' columns WOULD take
-            # gradients: they are zeroed behind the backward call (_zero_phantom_head_grads) and the columns stay zero; d ELBO /
-            # d h_u is a sum over head rows times those zero columns, so fc1's row takes no gradient at all.
-            H = 64
-        if (amortized and int(H) == 64 and self.J_items % 4 != 0 and self.J_items > 0
-                and isinstance(self.be, HipBackend) and self.pad_items):
-            # PHANTOM ITEMS up to a multiple of 4: the MFMA kernels of the amortized guides read response rows in
-            # 16-byte pieces and refuse other item counts (J = 499: 18.0 ms a step where J = 500 takes 2.1, tools/shape_cliffs.py).
-            # A phantom item is ABSENT for the likelihood (byte 254, "outside the problem": no log-probability, no gradient)
-            # and ZERO for the encoder (its input and the fc1 gradient's activation), so there are two copies of the responses:
-            # self.y (phantom byte 0) for the guide's forward / backward calls, self.y_lik (254) for the likelihood call and
-            # the item-major copy.  Its parameters -- a column of a, entries of b / c / d, a column of fc1.weight -- take
-            # zero gradients for ever (Adam leaves them where they start) and are not visible through unconstrained() / param().
-            # (The observed-cell lists of the 1-D step count a phantom among a person's J - n_observed unobserved items, each
-            # of which carries the reference's constant log Bern(0 | clamp(0)) = -1.19e-7: 1e-9 of a person's ELBO.)
-            pad = (-self.J_items) % 4
-            self.y_lik = torch.cat([self.y, torch.full((self.n_local, pad), 254, dtype=torch.uint8, device=self.dev)], 1).contiguous()
-            self.y = torch.cat([self.y, torch.zeros((self.n_local, pad), dtype=torch.uint8, device=self.dev)], 1).contiguous()
-        self.J = int(self.y.shape[1])                              # items the kernels see (J_items + phantoms)
-        self.model, self.D, self.Dc = model, int(D), float(Dc)
-        self.D_model = self.D                                      # the model's latent dimensions; self.D: what the kernels see
-        if (amortized and self.D > 1 and self.D % 4 != 0 and self.D + 3 <= 124 and int(H) == 64 and isinstance(self.be, HipBackend)
-                and self.pad_dims):
-            # PHANTOM DIMENSIONS up to a multiple of 4 (the MFMA kernels' other shape condition: D = 99: 31 ms a step where
-            # D = 100 takes 2.1).  A phantom dimension k has a_k = 0 for ever (free mask 0: it never reaches a logit) and head
-            # rows (fc21 row k, the fc22 rows (k, .), their biases) that start at ZERO and are kept there by zeroing their
-            # gradients behind the backward call: mu_k = 0, L_kk = e^0 = 1, L_kl = 0, so x_k = eps_k and the phantom's
-            # terms of the ELBO cancel (-x_k^2 / 2 from the prior, +eps_k^2 / 2 + M_kk from the entropy), and the shared
-            # hidden layer gets nothing from it (its rows of the head weights are what the hidden gradient multiplies by).
-            # The draws of the real dimensions are the same (Philox blocks of four dimensions), tril order puts the real
-            # fc22 rows first.  Not visible through unconstrained() / param().
-            self.D = (self.D + 3) // 4 * 4
-        self.amortized, self.H, self.share_cov = bool(amortized), int(H) if amortized else 0, bool(share_cov)
+        self.model, self.Dc, self.share_cov = model, float(Dc), bool(share_cov)
+        self._decide_shapes(int(D), bool(amortized), int(H))
         J, Dd = self.J, self.D
         self.off = {"a": 0, "b": Dd * J, "c": Dd * J + J, "d": Dd * J + 2 * J}
         self.shape = {"a": (Dd, J), "b": (1, J), "c": (1, J), "d": (1, J)}
@@ -1351,14 +1363,57 @@ class IrtEngine(_EngineBase):
                 else:
                     self.pp_shape = {"x_local": (self.n_local, Dd), "x_scale": (self.n_local, Dd, Dd)}
         self._alloc(o, self.n_local, per_person=not self.amortized)
-        # reference initial values (vi.py:567-587), over the problem's own items; phantom items (above) start at zero
-        Ji, Dm = self.J_items, self.D_model
+        self._fill_initial_values(a0, b0, a_free, encoder_init, seed)
+        self.base = (torch.zeros(max(self.n_local, 1), dtype=torch.float32, device=self.dev)
+                     if (estimator == "score" and baseline == "avg") else None)
+        self._sp = self._y_ext = self._y_ext_lik = None      # made on first use (_sparse_lists, _pad_batch)
+        self._phantom_rows = 0                               # phantom rows at the tail of the subsamples steps() is running
+        # the pass of this guide (loss_and_grads), by name: a bound method kept on the instance would be a reference cycle
+        self._guide_pass = "_pass_1d" if self.D == 1 else ("_pass_mvn_enc" if self.amortized else "_pass_mvn_pp")
 
-        def pad_j(t):                                              # [..., J_items] -> [..., J]
-            return t if J == Ji else torch.nn.functional.pad(t, (0, J - Ji))
+    def _decide_shapes(self, D, amortized, H):
+        """The shapes the kernels see -- self.J, self.D, self.H, at or above the problem's own J_items, D_model, H_model -- and,
+        with phantom items, the two copies of the responses.  Three kinds of phantom are decided here, each beside the argument
+        why it is harmless; phantom persons and phantom subsample rows depend on the call (_pad_persons, _pad_batch)."""
+        mfma = amortized and self._hip                             # the kernels whose shape conditions the phantoms meet
+        self.J_items, self.D_model, self.H_model = self.J, D, (H if amortized else 0)     # the problem's own
+        if mfma and 0 < H < 64 and self.pad_hidden:
+            # PHANTOM HIDDEN UNITS up to 64, the width the MFMA kernels are built for (hidden_dim 32: 23.6 ms a step where 64
+            # takes 2.4, tools/hidden_cliffs.py).  A phantom unit has a zero row of fc1 (weight and bias) and zero columns in
+            # both heads.  Its activation is softplus(0) = log 2, not zero (vi.py:430,447), so the heads' columns WOULD take
+            # gradients: they are zeroed behind the backward call (_zero_phantom_head_grads) and the columns stay zero; d ELBO /
+            # d h_u is a sum over head rows times those zero columns, so fc1's row takes no gradient at all.
+            H = 64
+        if mfma and H == 64 and self.J_items % 4 != 0 and self.J_items > 0 and self.pad_items:
+            # PHANTOM ITEMS up to a multiple of 4: the MFMA kernels of the amortized guides read response rows in
+            # 16-byte pieces and refuse other item counts (J = 499: 18.0 ms a step where J = 500 takes 2.1, tools/shape_cliffs.py).
+            # A phantom item is ABSENT for the likelihood (byte 254, "outside the problem": no log-probability, no gradient)
+            # and ZERO for the encoder (its input and the fc1 gradient's activation), so there are two copies of the responses:
+            # self.y (phantom byte 0) for the guide's forward / backward calls, self.y_lik (254) for the likelihood call and
+            # the item-major copy.  Its parameters -- a column of a, entries of b / c / d, a column of fc1.weight -- take
+            # zero gradients for ever (Adam leaves them where they start) and are not visible through unconstrained() / param().
+            # (The observed-cell lists of the 1-D step count a phantom among a person's J - n_observed unobserved items, each
+            # of which carries the reference's constant log Bern(0 | clamp(0)) = -1.19e-7: 1e-9 of a person's ELBO.)
+            pad = (-self.J_items) % 4
+            self.y_lik = torch.cat([self.y, torch.full((self.n_local, pad), 254, dtype=torch.uint8, device=self.dev)], 1).contiguous()
+            self.y = torch.cat([self.y, torch.zeros((self.n_local, pad), dtype=torch.uint8, device=self.dev)], 1).contiguous()
+        self.J = int(self.y.shape[1])                              # items the kernels see (J_items + phantoms)
+        if mfma and D > 1 and D % 4 != 0 and D + 3 <= 124 and H == 64 and self.pad_dims:
+            # PHANTOM DIMENSIONS up to a multiple of 4 (the MFMA kernels' other shape condition: D = 99: 31 ms a step where
+            # D = 100 takes 2.1).  A phantom dimension k has a_k = 0 for ever (free mask 0: it never reaches a logit) and head
+            # rows (fc21 row k, the fc22 rows (k, .), their biases) that start at ZERO and are kept there by zeroing their
+            # gradients behind the backward call: mu_k = 0, L_kk = e^0 = 1, L_kl = 0, so x_k = eps_k and the phantom's
+            # terms of the ELBO cancel (-x_k^2 / 2 from the prior, +eps_k^2 / 2 + M_kk from the entropy), and the shared
+            # hidden layer gets nothing from it (its rows of the head weights are what the hidden gradient multiplies by).
+            # The draws of the real dimensions are the same (Philox blocks of four dimensions), tril order puts the real
+            # fc22 rows first.  Not visible through unconstrained() / param().
+            D = (D + 3) // 4 * 4
+        self.D, self.amortized, self.H = D, amortized, H if amortized else 0      # dimensions, hidden units the kernels see
 
-        def pad_rows(t, n):                                        # [r, ...] -> [n, ...], zero rows behind
-            return t if t.shape[0] == n else torch.cat([t, torch.zeros((n - t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype)])
+    def _fill_initial_values(self, a0, b0, a_free, encoder_init, seed):
+        """The reference's initial values (vi.py:567-587) over the problem's own items, dimensions and hidden units; every
+        phantom's parameters start at zero (_decide_shapes says why they stay there)."""
+        model, J, Dd, Ji, Dm = self.model, self.J, self.D, self.J_items, self.D_model
         a_init = torch.ones(Dm, Ji) if a0 is None else torch.as_tensor(a0, dtype=torch.float32).reshape(Dm, Ji).clone()
         if a_free is None and Dm > 1:
             af = torch.ones(Dm, Ji)
@@ -1369,39 +1424,23 @@ class IrtEngine(_EngineBase):
         if Dd != Dm and a_free is None:
             a_free = torch.ones(Dm, Ji)
         if model != "irt_1pl":
-            self.view("a").copy_(pad_rows(pad_j(a_init), Dd).reshape(-1))
+            self.view("a").copy_(_grown(a_init, (Dd, J)).reshape(-1))
             if a_free is not None:
-                self.free[self.off["a"]:self.off["a"] + Dd * J] = pad_rows(pad_j(
-                    torch.as_tensor(a_free, dtype=torch.float32).reshape(Dm, Ji)), Dd).reshape(-1)
+                self.view("a", self.free).copy_(_grown(torch.as_tensor(a_free, dtype=torch.float32).reshape(Dm, Ji), (Dd, J)).reshape(-1))
         if b0 is not None:
-            self.view("b").copy_(pad_j(torch.as_tensor(b0, dtype=torch.float32).reshape(1, Ji)).reshape(-1))
+            self.view("b").copy_(_grown(torch.as_tensor(b0, dtype=torch.float32).reshape(1, Ji), (1, J)).reshape(-1))
         if model in ("irt_3pl", "irt_4pl"):
             self.view("c").fill_(float(np.float32(_logit(np.float32(0.1)))))
         if model == "irt_4pl":
             self.view("d").fill_(float(np.float32(_logit(np.float32(1.0) - np.float32(0.1)))))
         if self.amortized:
-            Hm = self.H_model
-            if encoder_init is None:
-                encoder_init = default_encoder_init(Ji, Dm, Hm, seed)
-            for k in ENC_KEYS:
-                w = torch.as_tensor(encoder_init[k], dtype=torch.float32)
-                if k == "fc1.weight":
-                    w = pad_rows(pad_j(w.reshape(Hm, Ji)), self.H)       # phantom items: zero columns; phantom units: zero rows
-                elif k == "fc1.bias":
-                    w = pad_rows(w.reshape(-1), self.H)
-                else:                                              # the heads: zero columns for the phantom units, zero rows
-                    if k.endswith("weight"):                       # for the phantom dimensions
-                        w = torch.nn.functional.pad(w.reshape(-1, Hm), (0, self.H - Hm))
-                    w = pad_rows(w.reshape((-1, self.H) if k.endswith("weight") else (-1,)), self.enc_shapes[k][0])
-                self.view("encoder$$$" + k).copy_(w.reshape(-1))
-        self.base = (torch.zeros(max(self.n_local, 1), dtype=torch.float32, device=self.dev)
-                     if (estimator == "score" and baseline == "avg") else None)
-        self._sp = self._y_ext = self._y_ext_lik = None      # made on first use (_sparse_lists, _pad_batch)
-        self._phantom_rows = 0                               # phantom rows at the tail of the subsamples steps() is running
+            self._fill_encoder(default_encoder_init(Ji, Dm, self.H_model, seed) if encoder_init is None else encoder_init,
+                               Ji, self.H_model)
 
-    pad_items = os.environ.get("VX_PAD_ITEMS", "1") != "0"          # test seam: 0 = the kernels see the problem's own item count
-
-    pad_batch = os.environ.get("VX_PAD_BATCH", "1") != "0"          # test seam: 0 = a subsample is launched over its own size
+    def _dim_major(self, cfg, n):
+        """Whether the dimension-major backward kernels take n persons of this shape: the backward call then reads gxT and gdT
+        and no gx, and a phantom person or row can leave the step as a column of those two (_take_out_phantoms)."""
+        return self.be.mvn_enc_bwd_layout(cfg, n) == 1 and self.be.mvn_enc_bwd_gd_offset(cfg, n) >= 0
 
     def _pad_batch(self, rows, b_global, eps):
         """A SUBSAMPLE whose size is no multiple of 4 (B = 50: 315 us a step where B = 100 takes 144 -- the person-major
@@ -1412,7 +1451,7 @@ class IrtEngine(_EngineBase):
         pathwise estimator, HIP backend; rows: one tensor or a list of them.  Only steps() pads: step() launches a subsample
         over its own size."""
         if (rows is None or eps is not None or not self.pad_batch or not (self.amortized and self.D > 1 and self.H == 64)
-                or not isinstance(self.be, HipBackend) or self.estimator != "pathwise"):
+                or not self._hip or self.estimator != "pathwise"):
             return rows, b_global
         many = isinstance(rows, (list, tuple))
         rs = list(rows) if many else [rows]
@@ -1423,7 +1462,7 @@ class IrtEngine(_EngineBase):
         if pad == 0 or n == 0:
             return rows, b_global
         cfg = self.be.cfg(self.model, self.D, self.J, self.H, self.Dc, 1.0, self.seed, 0, 0)
-        if self.be.mvn_enc_bwd_layout(cfg, n + pad) != 1 or self.be.mvn_enc_bwd_gd_offset(cfg, n + pad) < 0:
+        if not self._dim_major(cfg, n + pad):
             return rows, b_global
         if self._y_ext is None:
             miss = torch.full((1, self.J), 255, dtype=torch.uint8, device=self.dev)
@@ -1457,23 +1496,36 @@ class IrtEngine(_EngineBase):
         finally:
             self._phantom_rows = 0
 
-    def _pad_persons(self, be, cfg, rows):
-        """Persons the full-batch kernels of the amortized multivariate guide are launched over: the shard's own count, or --
-        when that is not a multiple of 8 -- the next one.  The dimension-major operands of the large-batch kernels are rows of
-        `nb` floats (fp16 planes: `nb` halves) read in 16-byte pieces, so a count that is not a multiple of 8 sends the head
-        weight gradient (and, below a multiple of 4, everything) to the fp32-MFMA generation: 13.9 ms a step at 1 000 004
-        persons, 26.3 at 999 999, against 9.1 at 1 000 000.  The 1-7 PHANTOM persons appended instead have every response
-        missing (byte 255: a finite guide sample, no likelihood term) and are taken out of the step behind the likelihood:
-        their columns of gxT / gdT (everything the backward kernels see of a person) and their entries of ll / ent are zeroed,
-        so they add nothing to any gradient or to the loss.  Pathwise estimator, HIP backend, full batch only."""
+    def _pad_persons(self, rows, eps, cfg=None):
+        """How many PHANTOM persons (0-7) the full-batch kernels of an amortized guide are launched over behind the shard's
+        own: up to the next multiple of 8.  The dimension-major operands of the large-batch kernels are rows of `nb` floats
+        (fp16 planes: `nb` halves) read in 16-byte pieces, so a count that is not a multiple of 8 sends the head weight gradient
+        (and, below a multiple of 4, everything) to the fp32-MFMA generation: 13.9 ms a step at 1 000 004 persons, 26.3 at
+        999 999, against 9.1 at 1 000 000 (the 1-D guide's encoder: 2.0 against 0.87 ms at 999 999 x 500).  A phantom has every
+        response missing (byte 255: a finite guide sample, no likelihood term) and is zeroed out of the step in front of the
+        guide's backward call (_take_out_phantoms; _pass_1d: gloc / graw), so it adds nothing to any gradient or to the loss.
+        Pathwise estimator, HIP backend, the kernels' own draws, full batch only.  cfg: the multivariate guide's, whose backward
+        must take the padded count dimension-major (the phantoms leave as columns of its operands); the 1-D guide: None."""
         n = self.n_local
-        if (rows is not None or n % 8 == 0 or n < 8 or not isinstance(be, HipBackend)
+        if (rows is not None or eps is not None or n % 8 == 0 or n < 8 or not self._hip
                 or self.estimator != "pathwise" or not self.pad_persons):
-            return n
-        n_pad = (n + 7) // 8 * 8
-        return n_pad if (be.mvn_enc_bwd_layout(cfg, n_pad) == 1 and be.mvn_enc_bwd_gd_offset(cfg, n_pad) >= 0) else n
+            return 0
+        pad = (-n) % 8
+        return pad if (cfg is None or self._dim_major(cfg, n + pad)) else 0
 
-    pad_persons = os.environ.get("VX_PAD_PERSONS", "1") != "0"      # test seam: 0 = launch over the shard's own count
+    @staticmethod
+    def _take_out_phantoms(D, nb, gxT, gdT, ll, ent, n_valid=None, keep=None):
+        """Where phantoms leave a multivariate step, behind the likelihood: their columns of gxT / gdT ([D][nb]: all the
+        backward kernels see of a person) and their entries of ll / ent.  Phantom PERSONS stand behind the n_valid real ones and
+        are zeroed, whatever the kernels left there; phantom ROWS of a padded subsample stand wherever the draw put them and are
+        multiplied by keep (0 for a phantom, 1 for a row of the shard).  They occur in different steps and stay two operations."""
+        gxm, gdm = gxT[:nb * D].view(D, nb), gdT[:nb * D].view(D, nb)
+        if n_valid is not None:
+            for t in (gxm[:, n_valid:], gdm[:, n_valid:], ll[n_valid:nb], ent[n_valid:nb]):
+                t.zero_()
+        if keep is not None:
+            for t in (gxm, gdm, ll[:nb], ent[:nb]):
+                t.mul_(keep)
 
     def _sparse_lists(self, rows):
         """Observed-cell lists for the D = 1 kernel (include/vipsy_amd.h, vx_irt1d_sparse_grad): built once -- the
@@ -1517,8 +1569,7 @@ class IrtEngine(_EngineBase):
         """What vx_irt1d_grad_adam needs to run Adam in the launch that sums the step's slabs -- or None when this step has
         to keep loss_and_grads | all-reduce | optimiser apart (a process group, an amortized or multivariate guide, a
         subsample whose gradients are scattered afterwards, the score-function estimator, more than one (betas, eps))."""
-        if not (self.fuse_tail and self.group is None and S == 1 and rows is None and isinstance(self.be, HipBackend)
-                and self.D == 1 and not self.amortized and self.per_person
+        if not (self.fuse_tail and self.group is None and S == 1 and rows is None and self._hip and self.D == 1 and not self.amortized and self.per_person
                 and self.estimator == "pathwise" and self.events is None and self.n_params == 4 * self.J):
             return None
         by_hyper, pp_hyper = self._optim_segments(lrs)
@@ -1545,11 +1596,6 @@ class IrtEngine(_EngineBase):
             return False
         return not (full and self.amortized and self.D > 1 and self.n_local > self.graph_max_persons)
 
-    score_mfma = os.environ.get("VX_SCORE_MFMA", "1") != "0"      # test seam: 0 = the scalar score-operand kernel for every shape
-    graph_max_persons = int(os.environ.get("VX_GRAPH_MAX_PERSONS", str(1 << 40)))
-    pad_hidden = os.environ.get("VX_PAD_HIDDEN", "1") != "0"        # test seam: 0 = the kernels see the encoder's own width
-    pad_dims = os.environ.get("VX_PAD_DIMS", "1") != "0"            # test seam: 0 = the kernels see the model's own dimensions
-
     def unconstrained(self, name, buf=None):
         u = super().unconstrained(name, buf)
         if self.J != self.J_items and name in ("a", "b", "c", "d", "encoder$$$fc1.weight"):
@@ -1568,15 +1614,13 @@ class IrtEngine(_EngineBase):
 
     def _zero_phantom_head_grads(self):
         """Phantom dimensions: the gradients of their head rows go back to zero; phantom hidden units: the gradients of their
-        head columns (IrtEngine.__init__)."""
-        Dm, Dp, H, Hm = self.D_model, self.D, self.H, self.H_model
-        if Dp != Dm:
+        head columns (_decide_shapes)."""
+        Dm, H = self.D_model, self.H
+        if self.D != Dm:
             Tm = Dm * (Dm + 1) // 2
             for k, lo in (("fc21.weight", Dm * H), ("fc21.bias", Dm), ("fc22.weight", Tm * H), ("fc22.bias", Tm)):
                 self.view("encoder$$$" + k, self.G)[lo:].zero_()
-        if self.amortized and H != Hm:
-            for k in ("fc21.weight", "fc22.weight"):
-                self.view("encoder$$$" + k, self.G).view(-1, H)[:, Hm:].zero_()
+        self._zero_phantom_unit_grads()
 
     # -- parameter access (constrained values as pyro.param(name) returns them) -----------------
     def names(self):
@@ -1646,227 +1690,225 @@ class IrtEngine(_EngineBase):
         """Fills self.G (flat grads + loss slot) and per-person grads for ONE particle.
         rows: int64 device tensor of LOCAL row indices (None = all local rows, i.e. full batch).
         baseline_buf / guide_grads: the 'loo' mode of the score-function estimator (step())."""
-        be = self.be
         nb, scale, sdc = self._call(rows, b_global)       # (sdc: a captured step's count lives in device memory)
-        cfg = be.cfg(self.model, self.D, self.J, self.H, self.Dc, scale, self.seed, self.t, stream_id, **sdc)
-        c_un = self.view("c") if self.model in ("irt_3pl", "irt_4pl") else None
-        d_un = self.view("d") if self.model == "irt_4pl" else None
-        a = self.view("a") if self.model != "irt_1pl" else None
-        gitem = self.G[:self.n_item]
-        lossslot = self.G[self.n_params:self.n_params + 1]
-        if self.D > 1 and not self.amortized:
-            D, n = self.D, self.n_local
-            fw = {"x": self._buf("x", nb * D), "eps": self._buf("eps", nb * D), "ent": self._buf("ent", nb)}
-            gx, ll = self._buf("gx", nb * D), self._buf("ll", nb)
-            lik_ws = self._buf("lik_ws", be.lik_workspace(cfg, nb))
-            loc = self.PP[:n * D]
-            if self.share_cov:
-                Mq, gM = self.view("x_scale"), self.view("x_scale", self.G)
-            else:
-                Mq, gM = self.PP[n * D:], self.GP[n * D:]
-            with self._phase("guide_forward"):
-                be.mvn_bbvi_forward(cfg, nb, rows, self.gid0, loc, Mq, self.share_cov, eps, fw["x"], fw["eps"], fw["ent"])
-            with self._phase("likelihood"):
-                be.lik_grad(cfg, self.y, rows, nb, fw["x"], a, self.view("b"), c_un, d_un, gx, ll, gitem, lik_ws)
-            cfg_b = cfg
-            if self.estimator == "score":
-                # the guide's score-function gradient in place of the pathwise one: gx <- w_i L_i^-T eps_i, and the diagonal
-                # term -w_i in place of the entropy's +scale (k_mvn_score.hip); item gradients and loss stand
-                with self._phase("mvn_score"):
-                    w_sf, log_r = self._buf("sf_w", nb), self._buf("sf_lr%d" % stream_id if not guide_grads else "sf_lr", nb)
-                    base, beta, by_row = self._score_baseline(baseline_buf, guide_grads)
-                    be.mvn_score_operands(cfg, nb, rows, 2 if self.share_cov else 1, None, None, None, Mq, fw["eps"], ll,
-                                          fw["ent"], base, beta, by_row, log_r, w_sf, gx, None, None)
-                    self.last_log_r = log_r
-                cfg_b = be.cfg(self.model, self.D, self.J, self.H, self.Dc, 0.0, self.seed, self.t, stream_id)
-            with self._phase("guide_backward"):
-                self.GP.zero_()                                       # dense per-person grads: zero off the batch
-                if self.share_cov:
-                    gM.zero_()
-                be.mvn_bbvi_backward(cfg_b, nb, rows, Mq, self.share_cov, gx, fw["eps"], self.GP[:n * D], gM,
-                                     self._buf("bbvi_ws", be.mvn_bbvi_bwd_workspace(cfg, nb, self.share_cov)))
-                if self.estimator == "score":
-                    be.mvn_score_diag(cfg, nb, rows, w_sf, self.share_cov, gM)
-            be.sum2_into(ll, fw["ent"], nb, -scale, lossslot, self.sum_ws, **sdc)   # loss = -scale * sum_i (ll_i + ent_i)
-            self.last = {"fw": fw, "gx": gx, "ll": ll, "nb": nb}
-        elif self.D > 1:
-            D, H = self.D, self.H
-            if eps is not None and D != self.D_model:      # a caller's draws are the model's: the phantom dimensions draw zero
-                e_p = torch.zeros(nb, D, dtype=torch.float32, device=self.dev)
-                e_p[:, :self.D_model] = eps.reshape(nb, self.D_model)
-                eps = e_p
-            n_valid, y_k, y_l = nb, self.y, (self.y_lik if self.y_lik is not None else self.y)
-            keep = None
-            phantoms = self._phantom_rows if rows is not None else 0
-            ext = rows is not None and self._y_ext is not None
-            if ext:
-                # rows of a padded subsample may point at the phantom person behind the shard's own (_pad_batch)
-                y_k, y_l = self._y_ext, self._y_ext_lik
-            if phantoms and not (ext and be.mvn_enc_bwd_layout(cfg, nb) == 1 and be.mvn_enc_bwd_gd_offset(cfg, nb) >= 0):
-                # the phantoms leave the step as columns of gxT / gdT: a launch without those operands would carry their
-                # entropy and prior into the loss and their gradients into the encoder's
-                raise RuntimeError("a subsample padded with %d phantom rows cannot be launched over %d rows of %s, D = %d, "
-                                   "J = %d, H = %d: the dimension-major backward kernels do not take this shape"
-                                   % (phantoms, nb, self.model, self.D, self.J, self.H))
-            if rows is None and eps is None:
-                self._n_pad = self._pad_persons(be, cfg, rows)
-                if self._n_pad != nb:                      # phantom persons up to a multiple of 8 (_pad_persons)
-                    nb, y_k, y_l = self._n_pad, self._padded_y(), self._padded_y(lik=True)
-            fw = {"h": self._buf("h", nb * H), "x": self._buf("x", nb * D), "eps": self._buf("eps", nb * D),
-                  "ldT": self._buf("ldT", nb * D), "ent": self._buf("ent", nb)}
-            fw["packws"] = self._buf("packws", be.mvn_pack_floats(cfg))
-            # dimension-major copies (person-contiguous rows) for the DMA-staged weight-gradient kernel
-            fw["hT"], fw["epsT"] = self._buf("hT", nb * H), self._buf("epsT", nb * D)
-            gxT = self._buf("gxT", nb * D)
-            yT = self._item_major_y(rows)
-            if yT is not None:
-                fw["yT"] = yT
-                n_img = be.lik_ximg_bytes(cfg, nb)        # x once more as the likelihood kernel's operand image
-                if n_img > 0:
-                    fw["ximg"] = self._buf("ximg", (n_img + 3) // 4)
-            gx, ll = self._buf("gx", nb * D), self._buf("ll", nb)
-            if be.mvn_enc_bwd_layout(cfg, nb) == 1:
-                gx = None                                  # the backward kernels read gxT only
-            enc = self._enc()
-            lik_ws = self._buf("lik_ws", be.lik_workspace(cfg, nb))
-            encb_ws = self._buf("encb_ws", be.mvn_enc_bwd_workspace(cfg, nb))
-            hs_off = be.mvn_enc_bwd_hs_offset(cfg, nb)     # the weight-gradient kernel's bf16 terms of hT, written by the forward
-            if hs_off >= 0:
-                fw["hs"] = encb_ws[hs_off:hs_off + nb * 64]
-            with self._phase("guide_forward"):
-                cfg_f = cfg
-                ring = self._capture_ring
-                if ring is not None and rows is not None and self._step_dev is not None and isinstance(be, HipBackend):
-                    # a captured subsampled step: the forward call's first launch fetches the step's draw from the pinned
-                    # host ring (vx_irt_cfg.rows_ring) -- no copy in front of every replay
-                    cfg_f = be.cfg(self.model, self.D, self.J, self.H, self.Dc, scale, self.seed, self.t, stream_id,
-                                   step_dev=self._step_dev, rows_ring=ring)
-                    self._capture_ring_used = True
-                be.mvn_enc_forward(cfg_f, y_k, rows, nb, self.gid0, enc, eps, fw)
-            if ext:
-                # behind the forward call: in a captured step `rows` holds this step's draw only once the forward's first launch
-                # has fetched it from the ring (in front of it: the draw of the step before)
-                keep = (rows != self.n_local).to(torch.float32)
-            gd_off = be.mvn_enc_bwd_gd_offset(cfg, nb)     # the backward's DIAG-row operand, made in the likelihood's last pass
-            gdT = encb_ws[gd_off:gd_off + nb * D] if gd_off >= 0 else None
-            # the step's largest |gx|, |gd|, |eps| (the head weight gradient's power of two), collected by the likelihood's last
-            # pass into words of packws that the forward call cleared -- unless the score-function mode replaces gxT / gdT below
-            opmax = None
-            if gdT is not None and self.estimator == "pathwise" and isinstance(be, HipBackend):
-                om = be.mvn_pack_opmax_offset(cfg, nb)
-                if om >= 0:
-                    opmax = fw["packws"][om:om + 3]
-            with self._phase("likelihood"):
-                be.lik_grad(cfg, y_l, rows, nb, fw["x"], a, self.view("b"), c_un, d_un, gx, ll, gitem, lik_ws,
-                            gxT=gxT, yT=yT, ximg=fw.get("ximg"), epsT=fw["epsT"] if gdT is not None else None,
-                            ldT=fw["ldT"] if gdT is not None else None, gdT=gdT, **({"opmax": opmax} if opmax is not None else {}))
-                if nb != n_valid:
-                    # the phantom persons leave the step here: nothing behind this line sees them but as zeros
-                    gxT[:nb * D].view(D, nb)[:, n_valid:].zero_()
-                    gdT[:nb * D].view(D, nb)[:, n_valid:].zero_()
-                    ll[n_valid:nb].zero_()
-                    fw["ent"][n_valid:nb].zero_()
-                if keep is not None and gdT is not None and gx is None:
-                    # (a padded subsample's phantom rows, wherever they stand.  Rows without phantoms on a shape that has no
-                    # gdT pass by: nothing to take out; rows WITH phantoms on such a shape were refused above)
-                    gxT[:nb * D].view(D, nb).mul_(keep)
-                    gdT[:nb * D].view(D, nb).mul_(keep)
-                    ll[:nb].mul_(keep)
-                    fw["ent"][:nb].mul_(keep)
-            if self.estimator == "score":
-                # gxT, gdT <- the score-function operands (k_mvn_score.hip); item gradients and loss stand
-                if gx is not None or gdT is None:
-                    raise NotImplementedError("the score-function estimator of the amortized multivariate guide runs on the "
-                                              "dimension-major backward kernels: hidden_dim 64, x_feature % 4 == 0 (<= 124), "
-                                              "item_size % 4 == 0, batch % 4 == 0")
-                with self._phase("mvn_score"):
-                    log_r = self._buf("sf_lr%d" % stream_id if not guide_grads else "sf_lr", nb)
-                    base, beta, by_row = self._score_baseline(baseline_buf, guide_grads)
-                    n_sh = be.mvn_score_heads_workspace(cfg) if (isinstance(be, HipBackend) and self.score_mfma) else -1
-                    if n_sh > 0:
-                        # u = L^-T eps on the fp16 MFMA, the head rows in column order (k_mvn_score_b.hip)
-                        be.mvn_score_heads(cfg, nb, rows, fw["h"], enc["fc22.weight"], enc["fc22.bias"], fw["packws"], fw["eps"],
-                                           ll, fw["ent"], base, beta, by_row, log_r, gxT, gdT,
-                                           self._buf("score_img", n_sh))
-                    else:
-                        be.mvn_score_operands(cfg, nb, rows, 0, fw["h"], enc["fc22.weight"], enc["fc22.bias"], None, fw["eps"], ll,
-                                              fw["ent"], base, beta, by_row, log_r, None, None, gxT, gdT)
-                    self.last_log_r = log_r
-            with self._phase("guide_backward"):
-                # loss = -scale * sum_i (ll_i + ent_i), from the backward call's last launch; a captured step's counter
-                # advances there, behind every kernel that read it
-                fused_loss = isinstance(be, HipBackend)
-                be.mvn_enc_backward(cfg, y_k, rows, nb, enc, fw, gx,
-                                    self.G[self.enc_off0:self.enc_off0 + self.n_enc], encb_ws, gxT=gxT,
-                                    gd_ready=gdT is not None, **({"opmax_ready": True} if opmax is not None else {}),
-                                    **({"loss": (ll, fw["ent"], -scale, lossslot, self.sum_ws)} if fused_loss else {}))
-            if not fused_loss:
-                be.sum2_into(ll, fw["ent"], nb, -scale, lossslot, self.sum_ws, **sdc)
-            self._zero_phantom_head_grads()
-            self.last = {"fw": fw, "gx": gx, "gxT": gxT, "ll": ll, "nb": nb, "n_valid": n_valid - phantoms}
+        model = self.model
+        getattr(self, self._guide_pass)(SimpleNamespace(                 # what every pass starts from
+            rows=rows, eps=eps, stream_id=stream_id, score=(baseline_buf, guide_grads), nb=nb, scale=scale, sdc=sdc,
+            cfg=self.be.cfg(model, self.D, self.J, self.H, self.Dc, scale, self.seed, self.t, stream_id, **sdc),
+            items=(self.view("a") if model != "irt_1pl" else None, self.view("b"),              # a, b, c_un, d_un
+                   self.view("c") if model in ("irt_3pl", "irt_4pl") else None, self.view("d") if model == "irt_4pl" else None),
+            gitem=self.G[:self.n_item], lossslot=self.G[self.n_params:self.n_params + 1]))
+
+    def _pass_mvn_pp(self, c):
+        """The per-person multivariate guide (VIRT, x_feature > 1): forward, likelihood, [score operands,] backward, loss."""
+        be, cfg, rows, nb = self.be, c.cfg, c.rows, c.nb
+        D, n, score = self.D, self.n_local, self.estimator == "score"
+        fw = {"x": self._buf("x", nb * D), "eps": self._buf("eps", nb * D), "ent": self._buf("ent", nb)}
+        gx, ll = self._buf("gx", nb * D), self._buf("ll", nb)
+        lik_ws = self._buf("lik_ws", be.lik_workspace(cfg, nb))
+        loc = self.PP[:n * D]
+        if self.share_cov:
+            Mq, gM = self.view("x_scale"), self.view("x_scale", self.G)
         else:
-            # D = 1: the flat item layout [a: J | b: J | c: J | d: J] IS the kernels' gradient layout -> written in place
-            g1d, i1d_ws = gitem, self._buf("i1d_ws", be.irt1d_workspace(cfg, nb))
-            elbo = self._buf("elbo", nb)
-            nb_e, y_e = nb, self.y                                 # persons the ENCODER kernels are launched over
-            if self.amortized:
-                H = self.H
-                enc = self._enc()
-                if (rows is None and eps is None and nb % 8 != 0 and nb >= 8 and isinstance(be, HipBackend)
-                        and self.estimator == "pathwise" and self.pad_persons):
-                    # phantom persons up to a multiple of 8 for the encoder's kernels only (their dimension-major operands want
-                    # 16-byte row starts: 2.0 against 0.87 ms a step at 999 999 x 500 persons); the step kernel below runs over
-                    # the shard's own persons, so the phantoms never reach the likelihood, the loss or the item gradients, and
-                    # their entries of gloc / graw -- all the encoder's backward sees of a person -- are zeroed
-                    self._n_pad = (nb + 7) // 8 * 8
-                    nb_e, y_e = self._n_pad, self._padded_y()
-                fw = {"h": self._buf("h", nb_e * H), "loc": self._buf("loc", nb_e), "raw": self._buf("raw", nb_e)}
-                n_pk = be.norm_enc_pack_floats(cfg) if hasattr(be, "norm_enc_pack_floats") else 0
-                if n_pk > 0:
-                    fw["packws"] = self._buf("nenc_packws", n_pk)      # the forward's fp16-pair images of W1 (large batches)
-                gloc, graw = self._buf("gloc", nb_e), self._buf("graw", nb_e)
-                nb_ws = self._buf("nencb_ws", be.norm_enc_bwd_workspace(cfg, nb_e))
-                with self._phase("guide_forward"):
-                    be.norm_enc_forward(cfg, y_e, rows, nb_e, enc, fw)
-                loc, raw = fw["loc"], fw["raw"]
+            Mq, gM = self.PP[n * D:], self.GP[n * D:]
+        with self._phase("guide_forward"):
+            be.mvn_bbvi_forward(cfg, nb, rows, self.gid0, loc, Mq, self.share_cov, c.eps, fw["x"], fw["eps"], fw["ent"])
+        with self._phase("likelihood"):
+            be.lik_grad(cfg, self.y, rows, nb, fw["x"], *c.items, gx, ll, c.gitem, lik_ws)
+        cfg_b = cfg
+        if score:
+            # the guide's score-function gradient in place of the pathwise one: gx <- w_i L_i^-T eps_i, and the diagonal
+            # term -w_i in place of the entropy's +scale (k_mvn_score.hip); item gradients and loss stand
+            with self._phase("mvn_score"):
+                w_sf = self._buf("sf_w", nb)
+                log_r, base, beta, by_row = self._score_pass("sf_lr", nb, c.stream_id, *c.score)
+                be.mvn_score_operands(cfg, nb, rows, 2 if self.share_cov else 1, None, None, None, Mq, fw["eps"], ll,
+                                      fw["ent"], base, beta, by_row, log_r, w_sf, gx, None, None)
+            cfg_b = be.cfg(self.model, self.D, self.J, self.H, self.Dc, 0.0, self.seed, self.t, c.stream_id)
+        with self._phase("guide_backward"):
+            self.GP.zero_()                                       # dense per-person grads: zero off the batch
+            if self.share_cov:
+                gM.zero_()
+            be.mvn_bbvi_backward(cfg_b, nb, rows, Mq, self.share_cov, gx, fw["eps"], self.GP[:n * D], gM,
+                                 self._buf("bbvi_ws", be.mvn_bbvi_bwd_workspace(cfg, nb, self.share_cov)))
+            if score:
+                be.mvn_score_diag(cfg, nb, rows, w_sf, self.share_cov, gM)
+        be.sum2_into(ll, fw["ent"], nb, -c.scale, c.lossslot, self.sum_ws, **c.sdc)   # loss = -scale * sum_i (ll_i + ent_i)
+        self.last = {"fw": fw, "gx": gx, "ll": ll, "nb": nb}
+
+    def _pass_mvn_enc(self, c):
+        """The amortized multivariate guide (VaeIRT, x_feature > 1: the headline workload), a function a stage."""
+        p = self._mvn_enc_plan(c)
+        keep = self._mvn_enc_forward(c, p)
+        self._mvn_enc_likelihood(c, p, keep)
+        if self.estimator == "score":
+            self._mvn_enc_score(c, p)
+        self._mvn_enc_backward(c, p)
+        self.last = {"fw": p.fw, "gx": p.gx, "gxT": p.gxT, "ll": p.ll, "nb": p.nb, "n_valid": p.n_valid - p.phantom_rows}
+
+    def _mvn_enc_plan(self, c):
+        """Everything the call decides, before its first launch: the persons it is launched over (nb, n_valid of them the
+        batch's own), the copies of the responses the guide (y_k) and the likelihood (y_l) read, the buffers, whether the shape
+        has a person-major gx, a gdT, operand maxima (opmax), forward-written bf16 terms of hT (fw["hs"]) -- and the refusal."""
+        be, cfg, rows, eps, nb, D, H = self.be, c.cfg, c.rows, c.eps, c.nb, self.D, self.H
+        if eps is not None and D != self.D_model:      # a caller's draws are the model's: the phantom dimensions draw zero
+            eps = _grown(eps.reshape(nb, self.D_model).to(device=self.dev, dtype=torch.float32), (nb, D))
+        phantom_rows = self._phantom_rows if rows is not None else 0
+        # rows of a padded subsample may point at the phantom person behind the shard's own (_pad_batch)
+        ext = rows is not None and self._y_ext is not None
+        y_k, y_l = (self._y_ext, self._y_ext_lik) if ext else (self.y, self.y_lik if self.y_lik is not None else self.y)
+        if phantom_rows and not (ext and self._dim_major(cfg, nb)):
+            # the phantoms leave the step as columns of gxT / gdT: a launch without those operands would carry their
+            # entropy and prior into the loss and their gradients into the encoder's
+            raise RuntimeError("a subsample padded with %d phantom rows cannot be launched over %d rows of %s, D = %d, "
+                               "J = %d, H = %d: the dimension-major backward kernels do not take this shape"
+                               % (phantom_rows, nb, self.model, self.D, self.J, self.H))
+        n_valid = nb
+        if rows is None and eps is None:
+            self._n_pad = nb = n_valid + self._pad_persons(rows, eps, cfg)
+            if nb != n_valid:                          # phantom persons up to a multiple of 8
+                y_k, y_l = self._padded_y(), self._padded_y(lik=True)
+        fw = {"h": self._buf("h", nb * H), "x": self._buf("x", nb * D), "eps": self._buf("eps", nb * D),
+              "ldT": self._buf("ldT", nb * D), "ent": self._buf("ent", nb)}
+        fw["packws"] = self._buf("packws", be.mvn_pack_floats(cfg))
+        # dimension-major copies (person-contiguous rows) for the DMA-staged weight-gradient kernel
+        fw["hT"], fw["epsT"] = self._buf("hT", nb * H), self._buf("epsT", nb * D)
+        gxT = self._buf("gxT", nb * D)
+        yT = self._item_major_y(rows)
+        if yT is not None:
+            fw["yT"] = yT
+            n_img = be.lik_ximg_bytes(cfg, nb)        # x once more as the likelihood kernel's operand image
+            if n_img > 0:
+                fw["ximg"] = self._buf("ximg", (n_img + 3) // 4)
+        gx, ll = self._buf("gx", nb * D), self._buf("ll", nb)
+        if be.mvn_enc_bwd_layout(cfg, nb) == 1:
+            gx = None                                  # the backward kernels read gxT only
+        lik_ws = self._buf("lik_ws", be.lik_workspace(cfg, nb))
+        encb_ws = self._buf("encb_ws", be.mvn_enc_bwd_workspace(cfg, nb))
+        hs_off = be.mvn_enc_bwd_hs_offset(cfg, nb)     # the weight-gradient kernel's bf16 terms of hT, written by the forward
+        if hs_off >= 0:
+            fw["hs"] = encb_ws[hs_off:hs_off + nb * 64]
+        gd_off = be.mvn_enc_bwd_gd_offset(cfg, nb)     # the backward's DIAG-row operand, made in the likelihood's last pass
+        gdT = encb_ws[gd_off:gd_off + nb * D] if gd_off >= 0 else None
+        # the step's largest |gx|, |gd|, |eps| (the head weight gradient's power of two), collected by the likelihood's last
+        # pass into words of packws that the forward call cleared -- unless the score-function mode replaces gxT / gdT
+        opmax = None
+        if gdT is not None and self.estimator == "pathwise" and self._hip:
+            om = be.mvn_pack_opmax_offset(cfg, nb)
+            if om >= 0:
+                opmax = fw["packws"][om:om + 3]
+        return SimpleNamespace(nb=nb, n_valid=n_valid, phantom_rows=phantom_rows, ext=ext, eps=eps, y_k=y_k, y_l=y_l, fw=fw,
+                               enc=self._enc(), gx=gx, gxT=gxT, gdT=gdT, ll=ll, yT=yT, opmax=opmax, lik_ws=lik_ws, encb_ws=encb_ws,
+                               lik_hip={"opmax": opmax} if self._hip else {})     # (the other backends' lik_grad is narrower)
+
+    def _mvn_enc_forward(self, c, p):
+        """The forward call; returns `keep`: 0 for the phantom rows of a padded subsample, 1 for the others (or None)."""
+        with self._phase("guide_forward"):
+            cfg_f = c.cfg
+            ring = self._capture_ring
+            if ring is not None and c.rows is not None and self._step_dev is not None and self._hip:
+                # a captured subsampled step: the forward call's first launch fetches the step's draw from the pinned
+                # host ring (vx_irt_cfg.rows_ring) -- no copy in front of every replay
+                cfg_f = self.be.cfg(self.model, self.D, self.J, self.H, self.Dc, c.scale, self.seed, self.t, c.stream_id,
+                                    step_dev=self._step_dev, rows_ring=ring)
+                self._capture_ring_used = True
+            self.be.mvn_enc_forward(cfg_f, p.y_k, c.rows, p.nb, self.gid0, p.enc, p.eps, p.fw)
+        # behind the forward call: in a captured step `rows` holds this step's draw only once the forward's first launch has
+        # fetched it from the ring (in front of it: the draw of the step before)
+        return (c.rows != self.n_local).to(torch.float32) if p.ext else None
+
+    def _mvn_enc_likelihood(self, c, p, keep):
+        """The likelihood call and, behind it, the phantoms taken out: nothing later in the step sees them but as zeros."""
+        fw, dm = p.fw, p.gdT is not None
+        with self._phase("likelihood"):
+            self.be.lik_grad(c.cfg, p.y_l, c.rows, p.nb, fw["x"], *c.items, p.gx, p.ll, c.gitem, p.lik_ws,
+                             gxT=p.gxT, yT=p.yT, ximg=fw.get("ximg"), epsT=fw["epsT"] if dm else None,
+                             ldT=fw["ldT"] if dm else None, gdT=p.gdT, **p.lik_hip)
+            # (a padded subsample's rows without phantoms on a shape that has no gdT pass by: nothing to take out; rows WITH
+            # phantoms on such a shape were refused by the plan)
+            n_valid = p.n_valid if p.nb != p.n_valid else None
+            keep = keep if (dm and p.gx is None) else None
+            if n_valid is not None or keep is not None:
+                self._take_out_phantoms(self.D, p.nb, p.gxT, p.gdT, p.ll, fw["ent"], n_valid, keep)
+
+    def _mvn_enc_score(self, c, p):
+        """gxT, gdT <- the score-function operands (k_mvn_score.hip); item gradients and loss stand."""
+        be, cfg, fw, nb, W22, b22 = self.be, c.cfg, p.fw, p.nb, p.enc["fc22.weight"], p.enc["fc22.bias"]
+        if p.gx is not None or p.gdT is None:
+            raise NotImplementedError("the score-function estimator of the amortized multivariate guide runs on the "
+                                      "dimension-major backward kernels: hidden_dim 64, x_feature % 4 == 0 (<= 124), "
+                                      "item_size % 4 == 0, batch % 4 == 0")
+        with self._phase("mvn_score"):
+            log_r, base, beta, by_row = self._score_pass("sf_lr", nb, c.stream_id, *c.score)
+            n_sh = be.mvn_score_heads_workspace(cfg) if (self._hip and self.score_mfma) else -1
+            if n_sh > 0:
+                # u = L^-T eps on the fp16 MFMA, the head rows in column order (k_mvn_score_b.hip)
+                be.mvn_score_heads(cfg, nb, c.rows, fw["h"], W22, b22, fw["packws"], fw["eps"], p.ll, fw["ent"], base, beta,
+                                   by_row, log_r, p.gxT, p.gdT, self._buf("score_img", n_sh))
             else:
-                loc, raw, gloc, graw = self._gather_pp(rows, nb)
-            lists = self._sparse_lists(rows)
-            with self._phase("irt1d"):
-                if lists is not None:                      # mostly-missing responses: observed cells only
-                    sp_ws = self._buf("i1d_sp_ws", be.irt1d_sparse_workspace(cfg, lists["n_groups"]))
-                    be.irt1d_sparse_grad(cfg, lists, self.gid0, loc, raw, eps, a, self.view("b"), c_un, d_un,
-                                         gloc, graw, elbo, g1d, sp_ws, loss=lossslot, **sdc, **self._take_fused_tail())
-                else:
-                    be.irt1d_grad(cfg, self.y_lik if self.y_lik is not None else self.y, rows, nb, self.gid0, loc, raw, eps, a,
-                                  self.view("b"), c_un, d_un,
-                                  gloc, graw, elbo, g1d, i1d_ws, loss=lossslot, **sdc, **self._take_fused_tail())
-            if self.estimator == "score":
-                # score-function gradient of the guide in place of the pathwise one (the step kernel's item gradients and
-                # loss stand); the draws are the step's own Philox normals, keyed by the global person id
-                with self._phase("irt1d_score"):
-                    if eps is None:
-                        eps_sf = self._buf("sf_eps", nb)
-                        gids = None if rows is None else (rows + self.gid0)
-                        be.philox_normals(eps_sf, gids, self.gid0, nb, 1, self.seed, self.t, stream_id)
-                    else:
-                        eps_sf = eps
-                    log_r = self._buf("sf_lr%d" % stream_id if not guide_grads else "sf_lr", nb)
-                    base, beta, by_row = self._score_baseline(baseline_buf, guide_grads)
-                    be.irt1d_score_grad(nb, scale, elbo, eps_sf, raw, rows, base, beta, by_row, log_r, gloc, graw)
-                    self.last_log_r = log_r
-            if self.amortized:
-                with self._phase("guide_backward"):
-                    if nb_e != nb:
-                        gloc[nb:nb_e].zero_()
-                        graw[nb:nb_e].zero_()
-                    be.norm_enc_backward(cfg, y_e, rows, nb_e, enc, fw["h"], gloc, graw,
-                                         self.G[self.enc_off0:self.enc_off0 + self.n_enc], nb_ws,
-                                         yT=self._item_major_y(rows))
-                    self._zero_phantom_head_grads()
+                be.mvn_score_operands(cfg, nb, c.rows, 0, fw["h"], W22, b22, None, fw["eps"], p.ll, fw["ent"], base, beta,
+                                      by_row, log_r, None, None, p.gxT, p.gdT)
+
+    def _mvn_enc_backward(self, c, p):
+        """The backward call and the loss = -scale * sum_i (ll_i + ent_i): on the HIP backend from the call's last launch -- a
+        captured step's counter advances there, behind every kernel that read it."""
+        loss = (p.ll, p.fw["ent"], -c.scale, c.lossslot, self.sum_ws)
+        hip = {"opmax_ready": p.opmax is not None, "loss": loss} if self._hip else {}     # (the other backends' calls are narrower)
+        with self._phase("guide_backward"):
+            self.be.mvn_enc_backward(c.cfg, p.y_k, c.rows, p.nb, p.enc, p.fw, p.gx,
+                                     self.G[self.enc_off0:self.enc_off0 + self.n_enc], p.encb_ws, gxT=p.gxT,
+                                     gd_ready=p.gdT is not None, **hip)
+        if not self._hip:
+            self.be.sum2_into(p.ll, p.fw["ent"], p.nb, -c.scale, c.lossslot, self.sum_ws, **c.sdc)
+        self._zero_phantom_head_grads()
+
+    def _pass_1d(self, c):
+        """x_feature == 1, per-person guide (VIRT) or NormEncoder (VaeIRT) in front of the one step kernel.  The flat item
+        layout [a: J | b: J | c: J | d: J] IS the kernel's gradient layout: written in place."""
+        be, cfg, rows, eps, nb = self.be, c.cfg, c.rows, c.eps, c.nb
+        i1d_ws = self._buf("i1d_ws", be.irt1d_workspace(cfg, nb))
+        elbo = self._buf("elbo", nb)
+        if self.amortized:
+            # phantom persons for the ENCODER's kernels only: the step kernel runs over the shard's own, and their entries of
+            # gloc / graw -- all the encoder's backward sees of a person -- are zeroed in front of it
+            nb_e, y_e = nb + self._pad_persons(rows, eps), self.y
+            if nb_e != nb:
+                self._n_pad = nb_e
+                y_e = self._padded_y()
+            ne = self._norm_enc_forward(cfg, y_e, rows, nb_e)
+            loc, raw, gloc, graw = ne.fw["loc"], ne.fw["raw"], ne.gloc, ne.graw
+        else:
+            loc, raw, gloc, graw = self._gather_pp(rows, nb)
+        lists = self._sparse_lists(rows)
+        with self._phase("irt1d"):
+            if lists is not None:                      # mostly-missing responses: observed cells only
+                sp_ws = self._buf("i1d_sp_ws", be.irt1d_sparse_workspace(cfg, lists["n_groups"]))
+                be.irt1d_sparse_grad(cfg, lists, self.gid0, loc, raw, eps, *c.items,
+                                     gloc, graw, elbo, c.gitem, sp_ws, loss=c.lossslot, **c.sdc, **self._take_fused_tail())
             else:
-                self._scatter_pp(rows, nb, gloc, graw)
-            self.last = {"elbo": elbo, "nb": nb}                # the loss itself came out of the kernel's reduction
+                be.irt1d_grad(cfg, self.y_lik if self.y_lik is not None else self.y, rows, nb, self.gid0, loc, raw, eps,
+                              *c.items, gloc, graw, elbo, c.gitem, i1d_ws, loss=c.lossslot, **c.sdc,
+                              **self._take_fused_tail())
+        if self.estimator == "score":
+            # score-function gradient of the guide in place of the pathwise one (the step kernel's item gradients and
+            # loss stand); the draws are the step's own Philox normals, keyed by the global person id
+            with self._phase("irt1d_score"):
+                if eps is None:
+                    eps = self._buf("sf_eps", nb)
+                    be.philox_normals(eps, None if rows is None else (rows + self.gid0), self.gid0, nb, 1, self.seed, self.t,
+                                      c.stream_id)
+                log_r, base, beta, by_row = self._score_pass("sf_lr", nb, c.stream_id, *c.score)
+                be.irt1d_score_grad(nb, c.scale, elbo, eps, raw, rows, base, beta, by_row, log_r, gloc, graw)
+        if self.amortized:
+            with self._phase("guide_backward"):
+                if nb_e != nb:
+                    gloc[nb:nb_e].zero_()
+                    graw[nb:nb_e].zero_()
+                self._norm_enc_backward(ne, self._item_major_y(rows))
+                self._zero_phantom_head_grads()
+        else:
+            self._scatter_pp(rows, nb, gloc, graw)
+        self.last = {"elbo": elbo, "nb": nb}                # the loss itself came out of the kernel's reduction
 
 
 class HoDinaEngine(_EngineBase):
@@ -1886,10 +1928,10 @@ class HoDinaEngine(_EngineBase):
         # items: its full-batch step took 0.81 ms at 200 k persons where 32 items take 0.24, tools/hodina_cliffs.py): the
         # encoder and the HO-DINA kernel are separate calls with separate configurations, so only the ENCODER sees phantom
         # items (J_enc, a copy of the responses with zero columns behind) and phantom hidden units (zero fc1 rows, zero head
-        # columns whose gradients are zeroed behind the backward call: softplus(0) = log 2) -- IrtEngine.__init__ has the
+        # columns whose gradients are zeroed behind the backward call: softplus(0) = log 2) -- IrtEngine._decide_shapes has the
         # argument; the HO-DINA kernel keeps the problem's own items and responses.
         self.H_model, self.J_enc, self.y_enc = self.H, self.J, self.y
-        if self.amortized and isinstance(self.be, HipBackend) and self.pad_encoder:
+        if self.amortized and self._hip and self.pad_encoder:
             if 0 < self.H < 64:
                 self.H = 64
             if self.H == 64 and self.J % 4 != 0:
@@ -1909,18 +1951,8 @@ class HoDinaEngine(_EngineBase):
         # vi.py:901-904: lam0 = 0, lam1 = 1 (positive -> log 1 = 0), g = s = 0.1 (interval(0,1) -> logit)
         self._init_g_s()
         if self.amortized:
-            Hm = self.H_model
-            if encoder_init is None:
-                encoder_init = default_encoder_init(J, 1, Hm, seed)
-            for k in ENC_KEYS:
-                w = torch.as_tensor(encoder_init[k], dtype=torch.float32)
-                if k == "fc1.weight":
-                    w = torch.nn.functional.pad(w.reshape(Hm, J), (0, self.J_enc - J, 0, self.H - Hm))
-                elif k == "fc1.bias":
-                    w = torch.nn.functional.pad(w.reshape(-1), (0, self.H - Hm))
-                elif k.endswith("weight"):
-                    w = torch.nn.functional.pad(w.reshape(1, Hm), (0, self.H - Hm))
-                self.view("encoder$$$" + k).copy_(w.reshape(-1))
+            self._fill_encoder(default_encoder_init(J, 1, self.H_model, seed) if encoder_init is None else encoder_init,
+                               J, self.H_model)
 
     pad_encoder = os.environ.get("VX_PAD_ENCODER", "1") != "0"      # test seam: 0 = the encoder in the problem's own shape
 
@@ -1967,16 +1999,8 @@ class HoDinaEngine(_EngineBase):
         lossslot = self.G[self.n_params:self.n_params + 1]
         if self.amortized:
             icfg = be.cfg("irt_2pl", 1, self.J_enc, self.H, 1.0, scale, self.seed, self.t, stream_id)
-            enc = self._enc()
-            fw = {"h": self._buf("h", nb * self.H), "loc": self._buf("loc", nb), "raw": self._buf("raw", nb)}
-            n_pk = be.norm_enc_pack_floats(icfg) if hasattr(be, "norm_enc_pack_floats") else 0
-            if n_pk > 0:
-                fw["packws"] = self._buf("nenc_packws", n_pk)
-            gloc, graw = self._buf("gloc", nb), self._buf("graw", nb)
-            nb_ws = self._buf("nencb_ws", be.norm_enc_bwd_workspace(icfg, nb))
-            with self._phase("guide_forward"):
-                be.norm_enc_forward(icfg, self.y_enc, rows, nb, enc, fw)
-            loc, raw = fw["loc"], fw["raw"]
+            ne = self._norm_enc_forward(icfg, self.y_enc, rows, nb)
+            loc, raw, gloc, graw = ne.fw["loc"], ne.fw["raw"], ne.gloc, ne.graw
         else:
             loc, raw, gloc, graw = self._gather_pp(rows, nb)
         with self._phase("hodina"):
@@ -1985,12 +2009,9 @@ class HoDinaEngine(_EngineBase):
                            self.G[:self.n_item], ws)
         if self.amortized:
             with self._phase("guide_backward"):
-                be.norm_enc_backward(icfg, self.y_enc, rows, nb, enc, fw["h"], gloc, graw,
-                                     self.G[self.enc_off0:self.enc_off0 + self.n_enc], nb_ws,
-                                     yT=self._item_major_y_enc(rows))
-                if self.H != self.H_model:                         # phantom hidden units: their head columns take no gradient
-                    for k in ("fc21.weight", "fc22.weight"):
-                        self.view("encoder$$$" + k, self.G)[self.H_model:].zero_()
+                self._norm_enc_backward(ne, self._item_major_y_enc(rows))
+                # (the heads have one row here: the helper's columns [:, H_model:] of [1][H] are the elements [H_model:])
+                self._zero_phantom_unit_grads()
         else:
             self._scatter_pp(rows, nb, gloc, graw)
         be.sum_into(elbo, nb, -scale, lossslot, self.sum_ws, **sdc)   # (a captured step's counter advances here)
@@ -2090,10 +2111,8 @@ class VaeCcdmEngine(_EngineBase):
         o = self._encoder_segments({"fc1.weight": (self.H, J), "fc1.bias": (self.H,), "fc2.weight": (C, self.H), "fc2.bias": (C,)})
         self._alloc(o, self.n_local, per_person=False)
         self._init_g_s()                                                     # vi.py:875-876
-        if encoder_init is None:
-            encoder_init = default_bin_encoder_init(J, C, self.H, seed)       # same nn.Linear shapes with C outputs
-        for k in BIN_ENC_KEYS:
-            self.view("encoder$$$" + k).copy_(torch.as_tensor(encoder_init[k], dtype=torch.float32).reshape(-1))
+        # (the BinEncoder's nn.Linear shapes with C outputs)
+        self._fill_encoder(default_bin_encoder_init(J, C, self.H, seed) if encoder_init is None else encoder_init, J, self.H)
 
     def names(self):
         return ["g", "s"] + ["encoder$$$" + k for k in BIN_ENC_KEYS]
@@ -2179,10 +2198,7 @@ class CdmSfEngine(_EngineBase):
         self._alloc(o, self.n_local, per_person=not self.amortized)
         self._init_g_s()                                                     # vi.py:748-749: g = s = 0.1
         if self.amortized:
-            if encoder_init is None:
-                encoder_init = default_bin_encoder_init(J, K, self.H, seed)
-            for k in BIN_ENC_KEYS:
-                self.view("encoder$$$" + k).copy_(torch.as_tensor(encoder_init[k], dtype=torch.float32).reshape(-1))
+            self._fill_encoder(default_bin_encoder_init(J, K, self.H, seed) if encoder_init is None else encoder_init, J, self.H)
         self.base = torch.zeros(max(self.n_local, 1), dtype=torch.float32, device=self.dev) if baseline == "avg" else None
 
     def names(self):
@@ -2204,7 +2220,7 @@ class CdmSfEngine(_EngineBase):
         K = self.K
         cfg = be.hodina_cfg(K, self.J, self.H, scale, self.seed, self.t, stream_id, **sdc)
         ws = self._buf("cs_ws", be.cdm_sf_workspace(cfg, nb))
-        gu, log_r = self._buf("cs_gu", nb * K), self._buf("cs_lr%d" % stream_id if not guide_grads else "cs_lr", nb)
+        gu = self._buf("cs_gu", nb * K)
         if self.amortized:
             enc = self._enc()
             h, u = self._buf("cs_h", nb * self.H), self._buf("cs_u", nb * K)
@@ -2212,7 +2228,7 @@ class CdmSfEngine(_EngineBase):
                 be.bin_enc_forward(cfg, self.y, rows, nb, enc, h, u)
         else:
             u = self.PP if rows is None else self.PP.reshape(self.n_local, K)[rows].contiguous().reshape(-1)
-        base, beta, by_row = self._score_baseline(baseline_buf, guide_grads)
+        log_r, base, beta, by_row = self._score_pass("cs_lr", nb, stream_id, baseline_buf, guide_grads)
         with self._phase("cdm_sf"):
             be.cdm_sf_grad(cfg, self.cdm == "dino", not self.amortized, self.attr_prior, self.y, rows, nb, self.gid0, self.q,
                            self.view("g"), self.view("s"), u, eps, base, beta, by_row, gu, log_r, None,
@@ -2229,7 +2245,6 @@ class CdmSfEngine(_EngineBase):
                 self.GP.zero_()
                 self.GP.reshape(self.n_local, K).index_add_(0, rows, gu[:nb * K].reshape(nb, K))
         be.sum_into(log_r, nb, -1.0, self.G[self.n_params:self.n_params + 1], self.sum_ws, **(sdc if guide_grads else {}))
-        self.last_log_r = log_r
         self.last = {"log_r": log_r, "gu": gu, "nb": nb}
 
     def step(self, lrs, rows=None, b_global=None, eps=None, num_particles=1):
@@ -2277,6 +2292,11 @@ class _Phase(object):
             self.e1.record()
             self.sink.append((self.name, self.e0, self.e1))
         return False
+
+
+def _grown(t, shape):
+    """t with zeros behind it in every dimension, up to `shape` (what a phantom's parameters start as)."""
+    return torch.nn.functional.pad(t, [v for have, want in zip(reversed(t.shape), reversed(shape)) for v in (0, want - have)])
 
 
 def _merge_segments(segs):
