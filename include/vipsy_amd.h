@@ -36,7 +36,7 @@ extern "C" {
 #define VX_OK 0
 #define VX_EINVAL (-1)       /* bad argument / unsupported shape */
 #define VX_EUNIMPL (-2)
-#define VX_ABI_VERSION 6
+#define VX_ABI_VERSION 7
 
 enum vx_model { VX_IRT_1PL = 1, VX_IRT_2PL = 2, VX_IRT_3PL = 3, VX_IRT_4PL = 4 }; /* vi.py:538-543 */
 
@@ -458,6 +458,30 @@ int64_t vx_grid_counts_workspace_floats(int64_t nb, int32_t J, int32_t G);
 int vx_grid_counts(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G,
                    const void* img, const float* logw /*[G]*/, const float* loglik /*[nb]*/, float* n1 /*[J][G]*/,
                    float* n0 /*[J][G]*/, float* mass /*[G]*/, float* workspace, void* hip_stream);
+
+/* ---- The M-step of the Bock-Aitkin EM on those tables (marginal maximum likelihood of the item parameters; with the E-step of
+ * vx_grid_posterior + vx_grid_counts one EM iteration).  Every item is a problem of its own; a and b / g_un and s_un are updated
+ * in place, [D][J] / [J] as the table builders take them, and nothing else is written.
+ *   vx_grid_mstep_irt (cfg: model 1 | 2, D <= 3, J, Dc): item j maximises
+ *         Q_j = sum_g n1[j][g] log P_j(g) + n0[j][g] log(1 - P_j(g)),   z = Dc (theta_g . a_j + b_j)   (1PL: z = Dc (theta_g + b_j))
+ *     through the cell of the tables (z clamped to +-logit(1 - eps32); a clamped node adds nothing to gradient or curvature) by
+ *     `newton` Newton (= Fisher scoring) steps inside the one launch, one wave an item.  a_free[d][j] == 0 takes that loading out
+ *     of the system: it is not written.  A step is accepted when Q does not fall by more than 1e-6 |Q|, else halved, at most 8
+ *     times, else the item stops; a step longer than 4 in its largest component is scaled down to 4 (an item whose observed
+ *     answers are all equal has its maximum at infinity: it ends finite, with every node at the clamp).  An item nobody answered
+ *     (sum_g n = 0) or a pivot that is not positive: the values keep their bits.  A parameter left where the clamp is active
+ *     everywhere has zero gradient in the step kernels afterwards.
+ *   vx_grid_mstep_cdm (cfg: K, J; dino, q as vx_grid_table_cdm): the closed form.  With R0 / W0 = the sums of n1 / n0 over the
+ *     patterns of eta = 0 and R1 / W1 those over eta = 1 (eta as the tables have it, DINO's single-attribute rule included):
+ *         g_un[j] = log R0 - log W0      s_un[j] = log W1 - log R1      clamped to +-logit(1 - eps32);
+ *     a class without mass (R + W = 0) leaves its parameter untouched.
+ * Every sum runs in a fixed order, no atomics: the same call gives the same bits.
+ * Limits: 1 <= J <= 1024, 1 <= G <= 1024, 1 <= D <= 3, model 1 or 2, 1 <= newton <= 64, K <= 10; VX_EINVAL beyond. */
+int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int32_t G, const float* n1 /*[J][G]*/,
+                      const float* n0 /*[J][G]*/, const float* a_free /*[D][J] or NULL = all free*/,
+                      float* a /*[D][J] in/out, NULL for 1PL*/, float* b /*[J] in/out*/, int32_t newton, void* hip_stream);
+int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const float* n1 /*[J][2^K]*/,
+                      const float* n0 /*[J][2^K]*/, float* g_un /*[J] in/out*/, float* s_un /*[J] in/out*/, void* hip_stream);
 
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,

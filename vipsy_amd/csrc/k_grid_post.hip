@@ -79,6 +79,18 @@ __global__ __launch_bounds__(256) void k_grid_table_irt(int D, int J, int G, flo
     }
 }
 
+// The attributes item j needs, as a bit pattern, and eta of a pattern for it (shared with k_grid_mstep.hip): DINA -- every needed
+// attribute held; DINO -- any of them, with the reference's in-place sequencing: single-attribute items always get eta = 0.
+__device__ __forceinline__ int gp_cdm_qpat(const float* __restrict__ q, int K, int J, int j) {
+    int qpat = 0;
+    for (int k = 0; k < K; ++k)
+        if (q[(int64_t)k * J + j] != 0.f) qpat |= (1 << k);
+    return qpat;
+}
+__device__ __forceinline__ bool gp_cdm_eta(int dino, int qpat, int pattern) {
+    return dino ? (__popc(qpat) >= 2 && (pattern & qpat) != 0) : ((pattern & qpat) == qpat);
+}
+
 // DINA / DINO: node c = attribute pattern (bit k = attribute k, the order of all_attrs); eta as k_hodina has it (DINO with the
 // reference's in-place sequencing: single-attribute items always get eta = 0), the Bernoulli clamp of bern_const.
 __global__ __launch_bounds__(256) void k_grid_table_cdm(int K, int J, int dino, const float* __restrict__ q,
@@ -89,10 +101,7 @@ __global__ __launch_bounds__(256) void k_grid_table_cdm(int K, int J, int dino, 
         const int gp = idx / JP, jp = idx - gp * JP;
         float t1 = 0.f, t0 = 0.f;
         if (gp < G && jp < J) {
-            int qpat = 0;
-            for (int k = 0; k < K; ++k)
-                if (q[(int64_t)k * J + jp] != 0.f) qpat |= (1 << k);
-            const bool eta = dino ? (__popc(qpat) >= 2 && (gp & qpat) != 0) : ((gp & qpat) == qpat);
+            const bool eta = gp_cdm_eta(dino, gp_cdm_qpat(q, K, J, jp), gp);
             const float gj = fminf(sigmoidf_(g_un[jp]), 1.0f - VX_EPS32), og = fmaxf(sigmoidf_(-g_un[jp]), VX_EPS32);
             const float sj = fminf(sigmoidf_(s_un[jp]), 1.0f - VX_EPS32), os = fmaxf(sigmoidf_(-s_un[jp]), VX_EPS32);
             const float P = eta ? os : gj, Q = eta ? sj : og;

@@ -32,6 +32,7 @@
 #include "k_vaeccdm.hip"
 #include "k_grid_post.hip"
 #include "k_grid_counts.hip"
+#include "k_grid_mstep.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2243,6 +2244,35 @@ int vx_grid_counts(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J,
                            p.slab_len, lens[k], 1.0f, outs[k]);
         VX_CHECK_LAUNCH();
     }
+    return VX_OK;
+}
+
+// The M-step on the expected-count tables (k_grid_mstep.hip): one wave an item, every Newton step inside the one launch
+int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0, const float* a_free,
+                      float* a, float* b, int32_t newton, void* hs) {
+    if (!cfg || (cfg->model != 1 && cfg->model != 2) || cfg->D < 1 || cfg->D > GM_MAXD || cfg->J < 1 || cfg->J > GP_MAXJ ||
+        G < 1 || G > GP_MAXG || newton < 1 || newton > GM_MAX_NEWTON || !theta || !n1 || !n0 || !b)
+        return VX_EINVAL;
+    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model == 2 && !a)) return VX_EINVAL;
+    const dim3 grid((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES));
+    hipStream_t st = (hipStream_t)hs;
+    if (cfg->model == 1)
+        hipLaunchKernelGGL((k_grid_mstep_irt<1>), grid, dim3(GM_THREADS), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, n1,
+                           n0, a_free, a, b, (int)newton);
+    else
+        hipLaunchKernelGGL((k_grid_mstep_irt<2>), grid, dim3(GM_THREADS), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, n1,
+                           n0, a_free, a, b, (int)newton);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* n1, const float* n0, float* g_un,
+                      float* s_un, void* hs) {
+    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || cfg->J > GP_MAXJ || (dino != 0 && dino != 1) || !q || !n1 || !n0 || !g_un || !s_un)
+        return VX_EINVAL;
+    hipLaunchKernelGGL(k_grid_mstep_cdm, dim3((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES)), dim3(GM_THREADS), 0, (hipStream_t)hs,
+                       (int)cfg->K, (int)cfg->J, (int)dino, q, n1, n0, g_un, s_un);
+    VX_CHECK_LAUNCH();
     return VX_OK;
 }
 

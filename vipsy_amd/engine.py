@@ -249,6 +249,16 @@ class HipBackend(object):
                                    _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(mass), _hip.ptr(ws), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_counts")
 
+    def grid_mstep_irt(self, cfg, theta, G, n1, n0, a_free, a, b, newton):
+        rc = self.L.vx_grid_mstep_irt(ctypes.byref(cfg), _hip.ptr(theta), G, _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(a_free),
+                                      _hip.ptr(a), _hip.ptr(b), int(newton), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_mstep_irt")
+
+    def grid_mstep_cdm(self, cfg, dino, q, n1, n0, g, s_):
+        rc = self.L.vx_grid_mstep_cdm(ctypes.byref(cfg), int(dino), _hip.ptr(q), _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(g),
+                                      _hip.ptr(s_), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_mstep_cdm")
+
     def grid_posterior(self, y, rows, nb, J, G, D, img, logw, coord, loglik, mean, sd, argmax):
         rc = self.L.vx_grid_posterior(_hip.ptr(y), _hip.ptr(rows), nb, J, G, D, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord),
                                       _hip.ptr(loglik), _hip.ptr(mean), _hip.ptr(sd), _hip.ptr(argmax), _hip.stream_ptr())
@@ -378,6 +388,7 @@ class HipBackend(object):
 
 SCORE_MAX_NODES = 1024           # GP_MAXG (vipsy_amd/csrc/k_grid_post.hip)
 SCORE_MAX_DIMS = 3               # IRT: the tensor-product grid stops being a method beyond three dimensions
+EM_MAX_NEWTON = 64               # GM_MAX_NEWTON (vipsy_amd/csrc/k_grid_mstep.hip)
 
 
 def score_grid(D, nodes=61, span=6.0):
@@ -729,6 +740,61 @@ class _EngineBase(object):
         ws = torch.empty(1024, dtype=torch.float32, device=self.dev)            # vx_sum_workspace_floats(); not the step's
         self.be.sum_into(ll, int(ll.numel()), 1.0, out, ws)
         return float(out.item())
+
+    # -- marginal maximum likelihood of the item parameters by EM on the grid posteriors (vx_grid_mstep_*) ---------------
+    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, **kw):
+        self._no_grid()
+
+    def _em_refusals(self, max_iter, newton):
+        """What every fit_em refuses before it looks at the model."""
+        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
+            raise NotImplementedError("fit_em over a process group: the expected counts are the local shard's sums and the "
+                                      "cross-rank sum is not built (one rank refits; the other ranks copy its item parameters)")
+        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+            raise ValueError("max_iter must be an integer >= 1")
+        if isinstance(newton, bool) or not isinstance(newton, (int, np.integer)) or not 1 <= newton <= EM_MAX_NEWTON:
+            raise ValueError("newton must be an integer in 1 .. %d (Newton steps of an item inside one M-step launch)" % EM_MAX_NEWTON)
+
+    def _em_loop(self, y, J, theta, logw, fill_tables, mstep, write_back, max_iter, tol, progress):
+        """The EM iterations shared by IrtEngine.fit_em and CcdmEngine.fit_em, beside _grid_posterior / _grid_counts: tables
+        (fill_tables(img)), vx_grid_posterior, the sum of its loglik (as marginal_loglik sums it), vx_grid_counts, the M-step
+        (mstep(n1, n0), on the caller's compact parameter copies) and write_back() into the leaves.  Every buffer is made once,
+        before the loop, and is the loop's own: nothing a step reads is touched.  The float of an iteration is fetched after
+        its M-step is queued: one host sync an iteration, behind which the device is never idle for long."""
+        be = self.be
+        G, D, n = int(theta.shape[0]), int(theta.shape[1]), int(y.shape[0])
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        img = torch.empty(be.grid_image_bytes(J, G), dtype=torch.uint8, device=self.dev)
+        loglik, mean, sd = torch.empty(n, **f32), torch.empty(n, D, **f32), torch.empty(n, D, **f32)
+        node = torch.empty(n, dtype=torch.int32, device=self.dev)
+        n1, n0, mass = torch.empty(J, G, **f32), torch.empty(J, G, **f32), torch.empty(G, **f32)
+        ws = torch.empty(be.grid_counts_workspace(n, J, G), **f32)
+        total, sum_ws = torch.empty(1, **f32), torch.empty(1024, **f32)      # vx_sum_workspace_floats(); not the step's
+        bar = None
+        if progress:
+            try:
+                from tqdm import trange
+                bar = trange(max_iter)
+            except Exception:  # pragma: no cover
+                bar = None
+        hist, converged = [], False
+        for _ in range(max_iter):
+            fill_tables(img)
+            be.grid_posterior(y, None, n, J, G, D, img, logw, theta, loglik, mean, sd, node)
+            be.sum_into(loglik, n, 1.0, total, sum_ws)
+            be.grid_counts(y, None, n, J, G, img, logw, loglik, n1, n0, mass, ws)
+            mstep(n1, n0)
+            write_back()
+            hist.append(float(total.item()))
+            if bar is not None:
+                bar.update(1)
+                bar.set_postfix(loglik="{0:1.4f}".format(hist[-1]))
+            if len(hist) > 1 and hist[-1] - hist[-2] <= tol * abs(hist[-2]):
+                converged = True
+                break
+        if bar is not None:
+            bar.close()
+        return {"loglik": hist, "iterations": len(hist), "converged": converged}
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1685,6 +1751,47 @@ class IrtEngine(_EngineBase):
         out["theta"], out["logw"] = call[3], call[4]
         return out
 
+    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, nodes=61, span=6.0):
+        """Marginal maximum likelihood of a and b by Bock-Aitkin EM over the grid of score(): each iteration scores the training
+        responses under the item parameters as they stand (the E-step: vx_grid_posterior, vx_grid_counts) and refits every
+        item to its expected counts by `newton` Newton steps (the M-step: vx_grid_mstep_irt), until the marginal log-likelihood
+        rises by no more than tol times its size between two iterations, or for max_iter iterations.  Returns {"loglik":
+        [floats], "iterations", "converged"}; loglik[k] is the marginal log-likelihood under the parameters iteration k
+        STARTED from (it falls out of the E-step), so loglik[0] is what marginal_loglik() gave before the call.
+        No guide is involved and none is changed: the encoder or the per-person rows, Adam's moments and the step count stay as
+        they are, and a later fit() goes on from the refitted items.  The loadings follow the engine's own free mask (a_free, or
+        the triangular default of x_feature > 1); the phantom items and dimensions of a padded engine are neither read nor
+        written.  1PL and 2PL with x_feature <= 3; an item nobody answered keeps its values; an item whose observed answers
+        are all equal has no finite maximiser and ends where the clamp of the response function, +-logit(1 - eps32) on z,
+        holds at every node -- there the step kernels' `inside` test fails, so a later fit() sees a zero gradient for it."""
+        self._em_refusals(max_iter, newton)
+        if self.model not in ("irt_1pl", "irt_2pl"):
+            raise NotImplementedError("fit_em for %s: with a guessing or slipping asymptote the M-step is not concave and wants "
+                                      "priors on the items; only irt_1pl and irt_2pl have it" % self.model)
+        if self.D_model > SCORE_MAX_DIMS:
+            raise NotImplementedError("fit_em needs x_feature <= %d (this model has %d): a tensor-product grid of n nodes a "
+                                      "dimension has n**D points" % (SCORE_MAX_DIMS, self.D_model))
+        be, J, Dm = self.be, self.J_items, self.D_model
+        theta_np, logw_np = score_grid(Dm, nodes, span)
+        y, _ = self._score_inputs(None, None, J)
+        theta, logw = torch.from_numpy(theta_np).to(self.dev), torch.from_numpy(logw_np).to(self.dev)
+        G = int(theta.shape[0])
+        # compact copies ([D_model][J_items], [J_items]) the tables and the M-step work on: the leaves may be strided views
+        two = self.model != "irt_1pl"
+        a = self.unconstrained("a").contiguous().clone() if two else None
+        free = self.unconstrained("a", self.free).contiguous().clone() if two else None
+        b = self.unconstrained("b").reshape(-1).contiguous().clone()
+        cfg = be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
+
+        def write_back():
+            if two:
+                self.unconstrained("a").copy_(a)
+            self.unconstrained("b").copy_(b.reshape(1, J))
+
+        return self._em_loop(y, J, theta, logw, lambda img: be.grid_table_irt(cfg, theta, G, a, b, None, None, img),
+                             lambda n1, n0: be.grid_mstep_irt(cfg, theta, G, n1, n0, free, a, b, newton), write_back,
+                             max_iter, tol, progress)
+
     # -- one ELBO-gradient step ------------------------------------------------------------------
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, guide_grads=True):
         """Fills self.G (flat grads + loss slot) and per-person grads for ONE particle.
@@ -2069,6 +2176,28 @@ class CcdmEngine(_EngineBase):
         out = self._grid_counts(*call)
         out["patterns"] = call[3]
         return out
+
+    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False):
+        """Marginal maximum likelihood of g and s by EM over the 2^K patterns (IrtEngine.fit_em): the E-step of
+        expected_counts(), then the closed-form M-step of vx_grid_mstep_cdm.  The enumerated ELBO of this class with its empty
+        guide IS the marginal likelihood: this is a second optimiser of what fit() descends.  The pattern distribution stays the
+        uniform prior; Adam's moments and the step count stay as they are.  `newton` is accepted for a common signature and
+        unused.  An estimate of exactly 0 or 1 sits at the clamp, +-logit(1 - eps32), where the step kernels give it a zero
+        gradient afterwards."""
+        self._em_refusals(max_iter, newton)
+        be, K, J = self.be, self.K, self.J
+        y, _, _, coord, logw, _ = self._grid_call(None, None)
+        g, s_ = self.view("g").clone(), self.view("s").clone()
+        cfg = be.hodina_cfg(K, J, 0, 1.0, 0, 0, 0)
+        dino = self.cdm == "dino"
+
+        def write_back():
+            self.unconstrained("g").copy_(g.reshape(1, J))
+            self.unconstrained("s").copy_(s_.reshape(1, J))
+
+        return self._em_loop(y, J, coord, logw, lambda img: be.grid_table_cdm(cfg, dino, self.q, g, s_, img),
+                             lambda n1, n0: be.grid_mstep_cdm(cfg, dino, self.q, n1, n0, g, s_), write_back, max_iter, tol,
+                             progress)
 
     def _replayable(self, full):
         # VCCDM (vi.py:819-865; test.py:560,585,624: 100-1500 rows a step): no guide, no random numbers -- the pattern

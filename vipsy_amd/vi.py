@@ -233,6 +233,20 @@ class BasePsy(object):
                                       "cross-rank sum is not built" % self.world)
         return self.engine.marginal_loglik(self._score_data(data), **kw)
 
+    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, **grid_kw):
+        """Refit the item parameters by marginal maximum likelihood: Bock-Aitkin EM on the training data (this object's
+        `data`) over the grid of score() (grid_kw: nodes, span), until the marginal log-likelihood rises by no more than
+        tol times its size between two iterations or max_iter is reached.  VIRT / VaeIRT with irt_1pl / irt_2pl and
+        x_feature <= 3 (IrtEngine.fit_em: `newton` Newton steps an item and iteration), VCCDM (CcdmEngine.fit_em: closed form);
+        the other classes refuse.  Returns {"loglik": [floats], "iterations": int, "converged": bool}, loglik[k] being the
+        marginal log-likelihood under the parameters at the START of iteration k: loglik[0] is marginal_loglik() before the
+        call, marginal_loglik() after it gives the value of the final parameters.  The guide, the optimiser's state and the
+        step count are left alone: a later fit() continues from the refitted items.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("fit_em with a group of %d ranks: the expected counts are the local shard's sums; the "
+                                      "cross-rank sum is not built" % self.world)
+        return self.engine.fit_em(max_iter=max_iter, tol=tol, newton=newton, progress=progress, **grid_kw)
+
 
 class BaseIRT(BasePsy):
     """vi.py:536-656 (constructor kwargs identical: model, x_feature, share_cov, D, a_free, a0, b0)."""
