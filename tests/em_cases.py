@@ -15,7 +15,21 @@ Cases and starts (em_cases()): IRT_CASES[0] (2PL, N = 33, J = 37: ragged everyth
 and COUNT_BIG (N = 2 500) from a = 1, b = 0; case5_2pl_d2_441 and case5_2pl_d3_729 (masked loadings) from a = 0.5 a_free, b = 0;
 a 1PL case of its own (ONEPL: N = 300, J = 50, thresholds in +-1.5 -- case3 of the score tests draws them over +-4 and has
 constant items, whose maximiser is at infinity, where no two arithmetics agree) from b = 0; the three CDM cases from the engine's
-g = s = 0.1."""
+g = s = 0.1.
+
+On all of these the oracle's Newton takes full steps only.  STEP_CASES are the inputs that leave that path: synthetic tables
+(step_tables: closed form, no seed, no training) from starts far from the maximiser -- capped steps, halved steps, both, two
+halvings in a step, halvings in two steps, nodes clamped at the start, masked loadings in two and three dimensions, constant
+items that walk to the clamp and stop on the zero pivot -- and ordinary items on grids either side of the kernel's lane
+boundaries.  A converged result hides a wrong path, so every launch is compared at every Newton budget of step_budgets().
+newton_mstep's trace records what was decided and by what margin, and its keywords build the wrong variants the cases must
+tell apart (tests/test_em_host.py).
+
+"All nine trials rejected" was searched for and not found: in 9 000 random starts (2PL, D = 1 .. 3, Dc = 1 and 1.702, a in
+[-6, 15], b in [-20, 20], truths with a in [-1, 6] and b in [-6, 6], constant items among them) the oracle and its float32 run
+halve at most twice in a step -- Q is concave and the Newton direction ascends.  (With log P formed as z - softplus(z), as
+_item_eval and the kernel had it before gm_cell, the float32 run did reject all nine, on items with Dc |b| >= 7 at the
+maximiser: rounding, not step control.  The launch step_2pl_easy_items keeps those inputs; docs/NOTEBOOK.md.)"""
 import numpy as np
 
 from oracle import vi_oracle as vo
@@ -95,21 +109,53 @@ def cdm_estep(cs, params, y=None):
 
 
 # ---- the M-step ----------------------------------------------------------------------------------------------------------
-def _item_eval(U, c1, c0, p, Dc, zl):
+def _item_eval(U, c1, c0, p, Dc, zl, leak=False, info=None):
     z = Dc * (U @ p)
     zc = np.clip(z, -zl, zl)
     inside = zc == z
-    e = np.exp(-np.abs(zc))
-    sp = np.maximum(zc, 0) + np.log1p(e)
+    if info is not None:                                                # (the trace: clamped nodes, nearest approach to +-ZL)
+        info["clamped"].append(int((~inside).sum()))
+        info["edge"] = min(info["edge"], float(np.abs(np.abs(z.astype(np.float64)) - ZL).min()))
+    if leak:                                                            # a wrong variant: clamped nodes enter gradient and curvature
+        inside = np.ones_like(inside)
+    e = np.exp(-np.abs(zc))                                             # log P, log(1 - P), P and 1 - P from positive terms:
+    lse = np.log1p(e)                                                   # no z - softplus(z), no 1 - P (gm_cell of the kernel)
     sg = np.where(zc >= 0, 1 / (1 + e), e / (1 + e)).astype(U.dtype)
-    q = (c1 * (zc - sp) - c0 * sp).sum(dtype=U.dtype)
-    r = np.where(inside, c1 * (1 - sg) - c0 * sg, 0).astype(U.dtype)
-    w = np.where(inside, (c1 + c0) * sg * (1 - sg), 0).astype(U.dtype)
+    sn = np.where(zc >= 0, e / (1 + e), 1 / (1 + e)).astype(U.dtype)
+    q = (c1 * (np.minimum(zc, 0) - lse) + c0 * (np.minimum(-zc, 0) - lse)).sum(dtype=U.dtype)
+    r = np.where(inside, c1 * sn - c0 * sg, 0).astype(U.dtype)
+    w = np.where(inside, (c1 + c0) * sg * sn, 0).astype(U.dtype)
     return q, Dc * (U.T @ r), Dc * Dc * ((U * w[:, None]).T @ U)
 
 
-def newton_mstep(model, theta, Dc, n1, n0, a, b, free, newton, dtype=np.float64, stats=None):
-    """New (a [D][J] or None, b [1][J]) in `dtype`; stats (a dict, optional) counts halvings, capped steps, stopped items."""
+def _pivots(A):
+    """The pivots of the Cholesky factorisation of A in A's dtype, up to and including the first that is not positive."""
+    n = A.shape[0]
+    L = np.zeros_like(A)
+    out = []
+    for i in range(n):
+        for l in range(i + 1):
+            v = A[i, l] - (L[i, :l] * L[l, :l]).sum(dtype=A.dtype)
+            if l == i:
+                out.append(float(v))
+                if not v > 0:
+                    return out
+                L[i, i] = np.sqrt(v)
+            else:
+                L[i, l] = v / L[l, l]
+    return out
+
+
+def newton_mstep(model, theta, Dc, n1, n0, a, b, free, newton, dtype=np.float64, stats=None, trace=None, halving=0.5,
+                 cap=STEP_CAP, halvings=HALVINGS, qtol=QTOL, leak=False, cap_rescales=True):
+    """New (a [D][J] or None, b [1][J]) in `dtype`; stats (a dict, optional) counts halvings, capped steps, stopped items.
+    trace (a list, optional) receives one record for every item that somebody answered: {"item", "steps": [{"capped",
+    "m_over_cap", "margins": (qt - (q - qtol |q|)) / |q| of every trial, the last one the accepted, "rises": qt - q of the same,
+    "pivots", "p": the unknowns after the step}], "stop": None / "pivot" / "nonfinite" / "halvings", "stop_step": the step it
+    happened in, "clamped": the number of clamped nodes of every evaluation, "edge": the smallest | |z| - ZL | of any node in
+    any evaluation}.
+    The keywords after it are the constants of the kernel; other values build the wrong variants of test_em_host.py (leak: the
+    clamped nodes enter gradient and curvature; cap_rescales = False: every component is clipped to the cap on its own)."""
     dt = np.dtype(dtype).type
     theta = np.asarray(theta, dtype)
     G, D = theta.shape
@@ -118,7 +164,7 @@ def newton_mstep(model, theta, Dc, n1, n0, a, b, free, newton, dtype=np.float64,
     U = np.concatenate([np.ones((G, 1), dtype), theta], axis=1)
     b = np.array(b, dtype).reshape(1, J)
     a = None if model == "irt_1pl" else np.array(a, dtype).reshape(D, J)
-    Dc, zl, qtol, cap = dt(Dc), dt(ZL), dt(QTOL), dt(STEP_CAP)
+    Dc, zl, qtol, cap, halving = dt(Dc), dt(ZL), dt(qtol), dt(cap), dt(halving)
     st = {"halvings": 0, "capped": 0, "stopped": 0} if stats is None else stats
     for k in ("halvings", "capped", "stopped"):
         st.setdefault(k, 0)
@@ -130,34 +176,59 @@ def newton_mstep(model, theta, Dc, n1, n0, a, b, free, newton, dtype=np.float64,
             p, fr = np.array([b[0, j], 1], dtype), np.array([True, False])
         else:
             p, fr = np.concatenate([b[:, j], a[:, j]]).astype(dtype), np.concatenate([[True], np.asarray(free)[:, j] != 0])
-        q, g, H = _item_eval(U, c1, c0, p, Dc, zl)
-        for _ in range(newton):
+        rec = None
+        if trace is not None:
+            rec = {"item": j, "steps": [], "stop": None, "stop_step": None, "clamped": [], "edge": np.inf}
+            trace.append(rec)
+        q, g, H = _item_eval(U, c1, c0, p, Dc, zl, leak, rec)
+        for it in range(newton):
+            A = H[np.ix_(fr, fr)]
+            step = None
+            if rec is not None:
+                step = {"capped": False, "m_over_cap": 0.0, "margins": [], "rises": [], "pivots": _pivots(A), "p": None}
             try:
-                L = np.linalg.cholesky(H[np.ix_(fr, fr)])
+                L = np.linalg.cholesky(A)
             except np.linalg.LinAlgError:
                 st["stopped"] += 1
+                if rec is not None:
+                    rec["stop"], rec["stop_step"], rec["stop_pivots"] = "pivot", it, step["pivots"]
                 break
             d = np.zeros_like(p)
             d[fr] = np.linalg.solve(L.T, np.linalg.solve(L, g[fr])).astype(dtype)
             m = np.abs(d).max()
             if not np.isfinite(m):
                 st["stopped"] += 1
+                if rec is not None:
+                    rec["stop"], rec["stop_step"] = "nonfinite", it
                 break
             t = dt(1)
             if m > cap:
-                t = cap / m
+                if cap_rescales:
+                    t = cap / m
+                else:
+                    d = np.clip(d, -cap, cap)
                 st["capped"] += 1
+            if step is not None:
+                step["capped"], step["m_over_cap"] = bool(m > cap), float(m / cap)
+                rec["steps"].append(step)
             moved = False
-            for _h in range(HALVINGS + 1):
+            for _h in range(halvings + 1):
                 pt = (p + t * d).astype(dtype)
-                qt, gt, Ht = _item_eval(U, c1, c0, pt, Dc, zl)
+                qt, gt, Ht = _item_eval(U, c1, c0, pt, Dc, zl, leak, rec)
+                if step is not None:
+                    step["margins"].append(float((qt - (q - qtol * abs(q))) / abs(q)))  # (q < 0: log1p(eps32) a node at the clamp)
+                    step["rises"].append(float(qt - q))
                 if qt >= q - qtol * abs(q):
                     p, q, g, H, moved = pt, qt, gt, Ht, True
                     break
                 st["halvings"] += 1
-                t = t * dt(0.5)
+                t = t * halving
+            if step is not None:
+                step["p"] = p.copy()
             if not moved:
                 st["stopped"] += 1
+                if rec is not None:
+                    rec["stop"], rec["stop_step"] = "halvings", it
                 break
         b[0, j] = p[0]
         if a is not None:
@@ -226,3 +297,199 @@ def design_case():
 
 
 DESIGN_UNANSWERED, DESIGN_CONSTANT = 4, 9
+
+
+# ---- the M-step's step control: synthetic tables -----------------------------------------------------------------------------
+def step_tables(theta, logw, Dc, N, truth):
+    """The tables of one synthetic item in float64: n1 = N w sigma(z), n0 = N w sigma(-z) with z = Dc (theta . a + b) of
+    truth = (a, b), or everything in n1 / n0 for truth = "correct" / "wrong".  w is the grid's prior weight times
+    1 + 0.25 sin(1.7 sum(theta) + 0.4), normalised: no table is symmetric about theta = 0, and so none about b = 0."""
+    theta = np.asarray(theta, np.float64)
+    w = np.exp(np.asarray(logw, np.float64)) * (1 + 0.25 * np.sin(1.7 * theta.sum(1) + 0.4))
+    w = N * w / w.sum()
+    if truth == "correct":
+        return w, np.zeros_like(w)
+    if truth == "wrong":
+        return np.zeros_like(w), w
+    a, b = truth
+    z = Dc * (theta @ np.asarray(a, np.float64).reshape(-1) + b)
+    return w * vo.sigmoid(z), w * vo.sigmoid(-z)
+
+
+def _it(name, truth, a0, b0, free=None, kind="finite", path=()):
+    return {"name": name, "truth": truth, "a0": a0, "b0": b0, "free": free, "kind": kind, "path": list(path)}
+
+
+# One entry = one launch: the items share model, D, Dc and grid.  kind: "finite" (a finite maximiser: a and b compared
+# absolutely), "clamp" (a constant 1PL item: walks until every node is clamped and the pivot is zero; b compared relative to
+# its size), "contract" (a constant 2PL item: near-singular on the way, no two arithmetics agree; the documented contract is
+# asserted instead of values).  J is never a multiple of 4: waves that stop early share a workgroup with waves that go on.
+# path: (capped, halvings) of the item's first Newton steps in the float64 oracle, the path its name stands for; every later
+# step is a full Newton step accepted at once (tests/test_em_host.py::test_step_case_conditions asserts both).
+STEP_CASES = [
+    {"name": "step_2pl_dc1", "model": "irt_2pl", "D": 1, "Dc": 1.0, "nodes": 41, "span": 6.0, "items": [
+        _it("ordinary", ([1.2], 0.3), [1.0], 0.0),
+        _it("cap", ([1.2], 0.3), [0.2], -3.0, path=[(1, 0)]),
+        _it("halve", ([1.2], 0.3), [3.0], 0.0, path=[(0, 1)]),
+        _it("cap_and_halve_clamped_start", ([2.0], 1.0), [4.0], 0.0, path=[(1, 1)]),      # a = 4 on [-6, 6]: clamped nodes at the start
+        _it("cap_then_halve", ([1.2], 0.3), [6.0], -4.0, path=[(1, 0), (0, 1)]),
+        _it("cap3", ([1.2], 0.3), [12.0], -8.0, path=[(1, 0), (1, 0), (1, 0)]),
+        _it("all_correct", "correct", [1.0], 0.0, kind="contract"),
+        _it("all_wrong_cap", "wrong", [2.0], 2.0, kind="contract", path=[(1, 0)]),
+        _it("cap_b", ([0.8], -0.7), [0.1], 4.0, path=[(1, 0)]),
+    ]},
+    {"name": "step_2pl_dc1702", "model": "irt_2pl", "D": 1, "Dc": 1.702, "nodes": 41, "span": 6.0, "items": [
+        _it("ordinary", ([1.0], 0.9), [1.0], 0.0),
+        _it("cap_halve2", ([1.7], -2.2), [-0.8], -1.9, path=[(1, 2)]),
+        _it("cap_then_halve2", ([1.0], -2.1), [-2.4], -6.3, path=[(1, 0), (0, 2)]),
+        _it("halve_in_two_steps", ([1.2], -1.0), [-0.3], -1.8, path=[(1, 1), (0, 1)]),
+        _it("cap_halve_twice", ([1.4], -3.3), [-0.3], -6.6, path=[(1, 1), (1, 1)]),
+        _it("halve2", ([0.9], -3.9), [-0.1], -4.0, path=[(0, 2)]),
+    ]},
+    # very easy and very hard items: Dc |b| of 8 to 10 at the maximiser, P > 0.9997 or < 0.0003 at theta = 0.  With log P formed as
+    # z - softplus(z) the float32 Q of such an item is rounded at 1e-4 of its size, every trial near the maximiser looks like a
+    # fall, and the item stopped on its halvings up to 1.5e-2 short (the first item: a 6.9e-3, b 1.5e-2 on an MI355X)
+    {"name": "step_2pl_easy_items", "model": "irt_2pl", "D": 1, "Dc": 1.702, "nodes": 41, "span": 6.0, "items": [
+        _it("easy_from_far", ([0.64], 5.88), [-2.78], -7.18, path=[(1, 0), (1, 0)]),
+        _it("easy_negative_a", ([-0.33], 5.56), [7.31], -8.11, path=[(1, 0), (1, 0)]),
+        _it("easy_from_one", ([1.0], 5.5), [1.0], 0.0),
+        _it("hard_from_one", ([0.8], -5.0), [1.0], 0.0),
+        _it("easy_steep", ([1.06], 4.77), [-5.69], 5.34, path=[(1, 0)]),
+    ]},
+    {"name": "step_1pl_dc1702", "model": "irt_1pl", "D": 1, "Dc": 1.702, "nodes": 41, "span": 6.0, "items": [
+        _it("ordinary", ([1.0], 0.4), None, 0.0),
+        _it("cap", ([1.0], 0.4), None, -4.0, path=[(1, 0)]),
+        _it("cap3", ([1.0], 0.4), None, 12.0, path=[(1, 0), (1, 0), (1, 0)]),
+        _it("all_correct", "correct", None, 0.0, kind="clamp"),
+        _it("all_correct_cap3", "correct", None, -12.0, kind="clamp", path=[(1, 0), (1, 0), (1, 0)]),       # stops past step 25
+        _it("all_wrong_cap", "wrong", None, 5.0, kind="clamp", path=[(1, 0)]),
+        _it("all_wrong_clamped_start", "wrong", None, -4.0, kind="clamp"),
+        _it("all_correct_clamped_start", "correct", None, 12.0, kind="clamp"),
+        _it("cap2", ([1.0], 0.4), None, 8.0, path=[(1, 0), (1, 0)]),
+    ]},
+    {"name": "step_1pl_dc1", "model": "irt_1pl", "D": 1, "Dc": 1.0, "nodes": 41, "span": 6.0, "items": [
+        _it("ordinary", ([1.0], 0.4), None, 0.0),
+        _it("all_correct", "correct", None, 0.0, kind="clamp"),
+        _it("cap", ([1.0], 0.4), None, 5.0, path=[(1, 0)]),
+        _it("all_wrong_cap2", "wrong", None, 8.0, kind="clamp", path=[(1, 0), (1, 0)]),
+        _it("cap3", ([1.0], 0.4), None, -12.0, path=[(1, 0), (1, 0), (1, 0)]),
+    ]},
+    {"name": "step_2pl_d2_masked", "model": "irt_2pl", "D": 2, "Dc": 1.0, "nodes": 11, "span": 4.0, "items": [
+        _it("ordinary", ([1.0, 0.6], 0.2), [0.5, 0.5], 0.0, [1, 1]),
+        _it("cap_halve_fixed_0.7", ([1.4, 0.7], 1.1), [3.3, 0.7], 3.2, [1, 0], path=[(1, 1)]),
+        _it("halve_fixed_0.7", ([0.7, 1.7], 1.9), [0.7, 0.0], 2.9, [0, 1], path=[(0, 1)]),
+        _it("cap_halve_fixed_0", ([0.0, 1.7], 1.5), [0.0, 3.4], 4.1, [0, 1], path=[(1, 1)]),
+        _it("cap_fixed_0.7", ([0.7, 1.9], -0.2), [0.7, -0.7], 3.7, [0, 1], path=[(1, 0)]),
+        _it("halve_fixed_0", ([1.6, 0.0], -1.2), [0.5, 0.0], -2.9, [1, 0], path=[(0, 1)]),
+    ]},
+    {"name": "step_2pl_d3_masked", "model": "irt_2pl", "D": 3, "Dc": 1.0, "nodes": 5, "span": 4.0, "items": [
+        _it("ordinary", ([1.0, 0.6, 0.8], 0.2), [0.5, 0.5, 0.5], 0.0, [1, 1, 1]),
+        _it("cap_halve_one_fixed", ([1.9, 0.7, 1.3], 0.9), [3.8, 0.7, 3.6], 2.6, [1, 0, 1], path=[(1, 1)]),
+        _it("halve_one_fixed", ([0.7, 1.8, 1.5], 1.9), [0.7, 0.8, 2.8], 2.3, [0, 1, 1], path=[(0, 1)]),
+        _it("cap_halve_two_fixed", ([1.9, 0.7, 0.7], 1.5), [3.9, 0.7, 0.7], 1.1, [1, 0, 0], path=[(1, 1)]),
+        _it("cap_one_fixed_0", ([1.4, 1.7, 0.0], -1.2), [3.7, 3.9, 0.0], 1.9, [1, 1, 0], path=[(1, 0)]),
+    ]},
+]
+# Ordinary converging items on grids either side of the lane boundaries of the kernel (64 lanes, at most GM_NK = 16 nodes a lane)
+for _D, _nodes, _span in ((1, 64, 6.0), (1, 65, 6.0), (2, 31, 5.0), (3, 10, 4.0), (2, 32, 5.0)):
+    STEP_CASES.append({"name": "lanes_d%d_g%d" % (_D, _nodes ** _D), "model": "irt_2pl", "D": _D, "Dc": 1.0, "nodes": _nodes,
+                       "span": _span, "items": [
+        _it("ordinary_a", ([1.2, 0.6, 0.9][:_D], 0.3), [0.5] * _D, 0.0, [1] * _D),
+        _it("ordinary_b", ([0.7, 1.1, 0.5][:_D], -0.8), [0.5] * _D, 0.0, [1] * _D),
+        _it("ordinary_c", ([1.5, 0.4, 0.8][:_D], 1.0), [1.0] * _D, 0.5, [1] * _D),
+    ]})
+STEP_LATE = 25                      # the budget at which a finite item has converged
+STEP_MAX = 64                       # GM_MAX_NEWTON: run where an item stops later than step 25
+
+_STEP = {}
+
+
+def step_case(spec):
+    """The launch of a STEP_CASES entry, built once: theta, the float32 tables [J][G] (what the kernel is fed, and the oracle),
+    the float32 start a0 [D][J] (None for 1PL) and b0 [1][J], free [D][J] bool (None for 1PL), the items' kinds."""
+    key = spec["name"]
+    if key not in _STEP:
+        from vipsy_amd.engine import score_grid
+        theta, logw = score_grid(spec["D"], spec["nodes"], spec["span"])
+        tabs = [step_tables(theta, logw, spec["Dc"], 2000.0, it["truth"]) for it in spec["items"]]
+        one = spec["model"] == "irt_1pl"
+        D = spec["D"]
+        _STEP[key] = {
+            "theta": theta, "J": len(tabs), "G": theta.shape[0],
+            "n1": np.stack([t[0] for t in tabs]).astype(np.float32), "n0": np.stack([t[1] for t in tabs]).astype(np.float32),
+            "a0": None if one else np.array([it["a0"] for it in spec["items"]], np.float32).T.reshape(D, -1).copy(),
+            "b0": np.array([[it["b0"] for it in spec["items"]]], np.float32),
+            "free": None if one else np.array([[1] * D if it["free"] is None else it["free"] for it in spec["items"]], bool).T.copy(),
+            "kinds": [it["kind"] for it in spec["items"]], "names": [it["name"] for it in spec["items"]]}
+    return _STEP[key]
+
+
+_STEP_RUN = {}
+
+
+def step_run(spec, newton, dtype=np.float64, cache=True, **knobs):
+    """(a, b, trace) of newton_mstep on the launch; the unmutated runs are computed once and shared (never modified), unless
+    cache = False; a run with knobs is never kept."""
+    key = (spec["name"], newton, np.dtype(dtype).name)
+    keep = cache and not knobs
+    if keep and key in _STEP_RUN:
+        return _STEP_RUN[key]
+    c = step_case(spec)
+    tr = []
+    a, b = newton_mstep(spec["model"], c["theta"], spec["Dc"], c["n1"], c["n0"], c["a0"], c["b0"], c["free"], newton,
+                        dtype=dtype, trace=tr, **knobs)
+    if keep:
+        _STEP_RUN[key] = (a, b, tr)
+    return a, b, tr
+
+
+def step_decisions(rec, upto=None):
+    """What the step control decided for one item: ((capped, halvings) of each Newton step, stop, the step it stopped in)."""
+    steps = rec["steps"] if upto is None else rec["steps"][:upto]
+    return [(s["capped"], len(s["margins"]) - 1) for s in steps], rec["stop"], rec["stop_step"]
+
+
+def step_last_special(rec):
+    """The number of Newton steps up to and including the item's last capped or halved one (0: none)."""
+    return max([i + 1 for i, (c, h) in enumerate(step_decisions(rec)[0]) if c or h] or [0])
+
+
+def step_budgets(spec):
+    """The `newton` of the launches of an entry: every budget from 1 to one past the last capped or halved step of any of its
+    items, then 25 -- and 64 where an item of the oracle stops later than that."""
+    _, _, tr = step_run(spec, STEP_MAX)
+    last = max(step_last_special(r) for r in tr)
+    out = list(range(1, last + 2)) + [STEP_LATE]
+    if any(r["stop_step"] is not None and r["stop_step"] >= STEP_LATE for r in tr):
+        out.append(STEP_MAX)
+    return sorted(set(out))
+
+
+def step_errors(spec, a, b, a64, b64, tol):
+    """The rule of the comparisons of a launch, as error / tolerance an item (> 1 fails): `tol` absolutely on a and b of a
+    finite item, tol * max(1, |b|) on a clamp item; None for a contract item (no values compared)."""
+    out = []
+    for j, kind in enumerate(step_case(spec)["kinds"]):
+        if kind == "contract":
+            out.append(None)
+            continue
+        e = abs(float(b[0, j]) - b64[0, j])
+        if a64 is not None:
+            e = max(e, float(np.abs(np.asarray(a, np.float64)[:, j] - a64[:, j]).max()))
+        out.append(e / (tol * (max(1.0, abs(b64[0, j])) if kind == "clamp" else 1.0)))
+    return out
+
+
+# ---- fit_em's stopping rule ----------------------------------------------------------------------------------------------------
+# (case, tol): tol lies between two consecutive relative rises of the oracle's trajectory that differ by a factor >= 4, each at
+# least 5 ROW_TOL from it (tests/test_em_host.py::test_converged_cases_are_decided checks it): the loglik the GPU returns is
+# held to ROW_TOL relatively, so its rises cannot fall on the other side of tol.
+CONVERGED = [(IRT_EM[0], 3e-2), (CDM_EM[0], 3e-4)]
+
+
+def stop_iteration(lks, tol):
+    """The number of iterations after which fit_em's rule stops on the log-likelihoods lks (None: not within them)."""
+    for k in range(1, len(lks)):
+        if lks[k] - lks[k - 1] <= tol * abs(lks[k - 1]):
+            return k + 1
+    return None

@@ -104,6 +104,154 @@ def test_cdm_closed_form_is_the_maximiser():
     assert abs(grid[Q.argmax()] - vo.sigmoid(g[0, j])) <= 1e-3
 
 
+# ---- the M-step's step control: conditions of the synthetic cases, and what they tell apart ----------------------------------
+STEP_IDS = [c["name"] for c in ec.STEP_CASES]
+
+
+@pytest.mark.parametrize("spec", ec.STEP_CASES, ids=STEP_IDS)
+def test_step_case_conditions(spec):
+    """The conditions under which the float64 oracle is a fair yardstick for a launch of STEP_CASES, on the oracle alone.
+    Each item takes the path it is named for and full Newton steps after it.  No node comes within 1e-3 of +-ZL in any
+    evaluation.  The float32 run takes the same decisions in all 64 steps and stays within an eighth of the GPU test's rule at
+    every budget.
+
+    |margin| >= 1e-4 = 100 QTOL is asserted for the finite items only, and for the steps the budgets tell apart (up to one
+    past the item's last capped or halved step): it cannot hold for every decision.  A converged finite item (budget 25) and
+    the last steps of a constant item to the clamp leave Q unchanged, so their margin is QTOL itself (1.0e-6 in float64,
+    9.8e-7 in float32).  A constant item is held to this instead: Q never falls on the way to the clamp (each node's term
+    rises), in float32 as in float64, so every step is accepted at once in both, and the item stops on a pivot of exactly
+    zero with every node clamped."""
+    c = ec.step_case(spec)
+    assert c["J"] % 4 != 0, c["J"]
+    _, _, tr = ec.step_run(spec, ec.STEP_MAX)
+    _, _, tr32 = ec.step_run(spec, ec.STEP_MAX, np.float32)
+    assert [r["item"] for r in tr] == list(range(c["J"]))
+    smallest, edge = np.inf, np.inf
+    for r, r32, it in zip(tr, tr32, spec["items"]):
+        tag = (spec["name"], it["name"])
+        dec, stop, at = ec.step_decisions(r)
+        assert dec == [tuple(map(bool, p[:1])) + (p[1],) for p in it["path"]] + [(False, 0)] * (len(dec) - len(it["path"])), (tag, dec)
+        assert ec.step_decisions(r32) == (dec, stop, at), (tag, ec.step_decisions(r32))
+        if it["kind"] == "finite":
+            assert stop is None and len(dec) == ec.STEP_MAX, tag
+            margins = [abs(m) for s_ in r["steps"][:ec.step_last_special(r) + 1] for m in s_["margins"]]
+            assert min(margins) >= 1e-4, (tag, min(margins))
+            smallest = min(smallest, min(margins))
+        else:
+            assert stop == "pivot" and at < ec.STEP_LATE + (ec.STEP_MAX - ec.STEP_LATE) * (ec.STEP_MAX in ec.step_budgets(spec)), (tag, stop, at)
+            assert r["stop_pivots"] == [0.0] and r32["stop_pivots"] == [0.0], (tag, r["stop_pivots"])
+            assert r["clamped"][-1] == c["G"] and r32["clamped"][-1] == c["G"], tag
+            for rr in (r, r32):
+                for s_ in rr["steps"]:
+                    assert len(s_["rises"]) == 1 and s_["rises"][0] >= 0, (tag, s_["rises"])
+                    assert s_["m_over_cap"] <= 1.0 or s_["capped"]
+        if "clamped_start" in it["name"]:
+            assert r["clamped"][0] >= 1 and len(set(r["clamped"])) > 1, (tag, r["clamped"])
+        assert min(r["edge"], r32["edge"]) >= 1e-3, (tag, r["edge"], r32["edge"])
+        edge = min(edge, r["edge"], r32["edge"])
+    worst = 0.0
+    for n in ec.step_budgets(spec):
+        a64, b64, _ = ec.step_run(spec, n)
+        a32, b32, _ = ec.step_run(spec, n, np.float32)
+        e = [x for x in ec.step_errors(spec, a32, b32, a64, b64, ROW_TOL / 8) if x is not None]
+        assert max(e) <= 1.0, (spec["name"], n, e)
+        worst = max(worst, max(e))
+        if a64 is not None:                                              # masked loadings keep their bits in both
+            assert np.array_equal(a64[~c["free"]], c["a0"][~c["free"]].astype(np.float64))
+            assert np.array_equal(a32[~c["free"]], c["a0"][~c["free"]])
+    print("%s budgets %s: smallest |margin| %.1e, nearest approach to the clamp %.1e, float32 at most %.3f of ROW_TOL / 8"
+          % (spec["name"], ec.step_budgets(spec), smallest, edge, worst))
+
+
+def test_step_cases_cover_the_paths():
+    """Every path of the kernel's step control that an input can reach is taken by some item (all halvings exhausted is not:
+    see the docstring of test_step_mutants)."""
+    have = set()
+    for spec in ec.STEP_CASES:
+        c = ec.step_case(spec)
+        _, _, tr = ec.step_run(spec, ec.STEP_MAX)
+        have.add("G%d" % c["G"])
+        for r, it in zip(tr, spec["items"]):
+            dec, stop, at = ec.step_decisions(r)
+            one, D = spec["model"] == "irt_1pl", spec["D"]
+            masked = it["free"] is not None and 0 in it["free"]
+            if (True, 0) in dec and it["kind"] == "finite":
+                have.add("cap accepted 1pl" if one else "cap accepted 2pl")
+            if any(cp and h for cp, h in dec):
+                have.add("capped and halved")
+            if max(h for _, h in dec) >= 2:
+                have.add("two halvings in a step")
+            if sum(h > 0 for _, h in dec) >= 2:
+                have.add("halvings in two steps")
+            if r["clamped"][0] >= 1 and len(set(r["clamped"])) > 1 and it["kind"] == "finite":
+                have.add("clamped at the start")
+            if masked and (dec[0][0] or dec[0][1]):
+                have.add("masked D%d" % D)
+            if it["kind"] == "clamp":
+                have.add("1pl %s%s" % (it["truth"], " capped first" if dec[0][0] else ""))
+            if it["kind"] == "contract":
+                have.add("2pl %s" % it["truth"])
+            assert max(h for _, h in dec) < ec.HALVINGS and stop != "halvings"
+    want = {"cap accepted 1pl", "cap accepted 2pl", "capped and halved", "two halvings in a step", "halvings in two steps",
+            "clamped at the start", "masked D2", "masked D3", "1pl correct", "1pl wrong", "1pl correct capped first",
+            "1pl wrong capped first", "2pl correct", "2pl wrong", "G64", "G65", "G961", "G1000", "G1024"}
+    assert want <= have, want - have
+
+
+STEP_MUTANTS = {"halving factor 0.25": dict(halving=0.25), "cap 2": dict(cap=2.0), "cap clips each component": dict(cap_rescales=False),
+                "clamped nodes in the gradient": dict(leak=True), "one Newton step more": 1, "one Newton step fewer": -1}
+
+
+def _step_failures(kn, tol):
+    """(launch, budget, item) of every comparison of the float32 stand-in, changed by `kn`, that breaks the GPU test's rule."""
+    out = []
+    for spec in ec.STEP_CASES:
+        for n in ec.step_budgets(spec):
+            a64, b64, _ = ec.step_run(spec, n)
+            if isinstance(kn, int):                                      # (n + kn is not always a budget: not kept)
+                a32, b32, _ = ec.step_run(spec, n + kn, np.float32, cache=False)
+            else:
+                a32, b32, _ = ec.step_run(spec, n, np.float32, **kn)
+            e = ec.step_errors(spec, a32, b32, a64, b64, tol)
+            out += [(spec["name"], n, ec.step_case(spec)["names"][j]) for j, x in enumerate(e) if x is not None and x > 1]
+    return out
+
+
+def test_step_stand_in_passes_everywhere():
+    """The kernel's own method, said in float32 numpy, breaks the rule of the GPU test on no launch, budget or item."""
+    assert _step_failures({}, ROW_TOL) == []
+
+
+@pytest.mark.parametrize("mutant", list(STEP_MUTANTS), ids=[m.replace(" ", "_") for m in STEP_MUTANTS])
+def test_step_mutants(mutant):
+    """A wrong kernel, said in float32 numpy, breaks the rule of tests/test_gpu_em.py::test_step_control on some launch and
+    budget (the kernel's own method breaks it nowhere: test_step_stand_in_passes_everywhere).
+
+    Two wrong variants no reachable input exposes, and none is asserted for them.  One halving fewer (hv < GM_HALVINGS)
+    differs only where the eighth halving is tried: in 9 000 random starts (2PL, D = 1 .. 3, Dc = 1 and 1.702, a from -6 to
+    15, b from -20 to 20, constant items among them) the float64 oracle and the float32 run halve at most twice in a step and
+    never reject all nine trials -- Q is concave and the Newton direction ascends.  qtol = 0 differs only where a trial's Q
+    falls by less than 1e-6 |Q|: a decision the conditions above exclude, since the two precisions need not agree on it; at
+    convergence, where such trials do occur, the outcome moves the result by less than the rule."""
+    bad =_step_failures(STEP_MUTANTS[mutant], ROW_TOL)
+    print(mutant, "breaks", len(bad), "comparisons, first", bad[:3])
+    assert bad, mutant
+
+
+@pytest.mark.parametrize("case,tol", ec.CONVERGED, ids=[c[0][0] for c in ec.CONVERGED])
+def test_converged_cases_are_decided(case, tol):
+    """The tol of tests/test_gpu_em.py::test_converged separates two consecutive relative rises of the oracle that differ by a
+    factor >= 4, every rise up to the stop at least 5 ROW_TOL away from it."""
+    cs, kind, ps, lks, _ = ec.trajectory(case, 8)
+    n = ec.stop_iteration(lks, tol)
+    assert n is not None and n >= 3, n
+    rises = [(lks[k + 1] - lks[k]) / abs(lks[k]) for k in range(n - 1)]
+    print(cs["name"], "tol %.0e stops after %d iterations; rises %s" % (tol, n, ["%.2e" % r for r in rises]))
+    assert rises[-2] >= 4 * rises[-1] > 0
+    assert all(r - tol >= 5 * ROW_TOL for r in rises[:-1]) and tol - rises[-1] >= 5 * ROW_TOL
+    assert ec.stop_iteration(lks, 1e30) == 2
+
+
 # ---- declarations ------------------------------------------------------------------------------------------------------------
 def test_header_and_binding_declare_the_entry_points():
     from vipsy_amd import _hip

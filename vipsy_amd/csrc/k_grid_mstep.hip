@@ -6,8 +6,9 @@
 //
 //     Q_j(a_j, b_j) = sum_g n1[j][g] log P_j(g) + n0[j][g] log(1 - P_j(g)),      z = Dc (theta_g . a_j + b_j)
 //
-// through the cell of the tables (irt_cell<2>: z clamped to +-logit(1 - eps32); a node where the clamp is active adds its
-// clamped term to Q and nothing to the gradient or the curvature).  Newton steps, which for the logistic link are Fisher
+// with the clamp of the tables' cell (irt_cell<2>: z clamped to +-logit(1 - eps32); a node where the clamp is active adds its
+// clamped term to Q and nothing to the gradient or the curvature) in a cell of its own, gm_cell, which keeps the digits of log P
+// and 1 - P where P is near 1.  Newton steps, which for the logistic link are Fisher
 // scoring: with u_g = (1, theta_g), r = n1 (1 - p) - n0 p and w = (n1 + n0) p (1 - p),
 //
 //     gradient = Dc sum_g r u_g        -Hessian = Dc^2 sum_g w u_g u_g^T        (positive semi-definite always).
@@ -56,6 +57,26 @@ struct GmSums {
     float h[GM_NP * (GM_NP + 1) / 2];
 };
 
+// One node: log P, log(1 - P) at z clamped to +-GM_ZL, and 1 - P, P (0 where the clamp is active), every one from positive terms.
+// irt_cell<2> has log P = y z - softplus(z) and 1 - P = 1 - sigmoid(z): at z = 10 differences of numbers near 10 and near 1 that
+// leave 5e-5 -- good for a likelihood, but Q of an item nearly everybody answers alike is then rounded at 1e-4 of its size, a
+// hundred times what the acceptance rule allows for: near the maximiser every trial looked like a fall and the item stopped on
+// its halvings up to 1.5e-2 short.  Here log P = min(z, 0) - log1p(e), log(1 - P) = min(-z, 0) - log1p(e) with e = exp(-|z|), and
+// log1p(e) = log(t) e / (t - 1) for t = 1 + e rounded: t - 1 is exact, and the quotient takes back what the rounding of t took.
+__device__ __forceinline__ void gm_cell(float z, float& lp1, float& lp0, float& om, float& pr) {
+    const float zc = __builtin_amdgcn_fmed3f(z, -GM_ZL, GM_ZL);
+    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(zc));   // exp(-|zc|) in (1e-7, 1]
+    const float t = 1.0f + e;                                                   // in (1, 2]
+    const float tm1 = t - 1.0f;
+    const float lse = tm1 > 0.f ? 0.6931471805599453f * __builtin_amdgcn_logf(t) * (e * fast_rcp(tm1)) : e;
+    const float big = fast_rcp(t), small = e * big;                             // sigmoid(|zc|), sigmoid(-|zc|)
+    const bool pos = zc >= 0.f, inside = zc == z;
+    lp1 = fminf(zc, 0.f) - lse;
+    lp0 = fminf(-zc, 0.f) - lse;
+    om = inside ? (pos ? small : big) : 0.f;
+    pr = inside ? (pos ? big : small) : 0.f;
+}
+
 __device__ __forceinline__ void gm_eval(const float* __restrict__ th, int D, int G, int NK, int lane, float Dc,
                                         const float (&r1)[GM_NK], const float (&r0)[GM_NK], const float (&p)[GM_NP], GmSums& s) {
     float q = 0.f, g[GM_NP], h[GM_NP * (GM_NP + 1) / 2];
@@ -77,13 +98,12 @@ __device__ __forceinline__ void gm_eval(const float* __restrict__ th, int D, int
             for (int d = 0; d < GM_MAXD; ++d)
                 if (d < D) sz = fmaf(u[1 + d], p[1 + d], sz);
             const float z = Dc * sz;
-            float lp1, lp0, dz1, dz0, dc, dd;
-            irt_cell<2>(z, 1u, 0.f, 1.f, 0.f, lp1, dz1, dc, dd);    // dz1 = 1 - p, dz0 = -p; both 0 where the clamp is active
-            irt_cell<2>(z, 0u, 0.f, 1.f, 0.f, lp0, dz0, dc, dd);
+            float lp1, lp0, om, pr;
+            gm_cell(z, lp1, lp0, om, pr);                           // om = 1 - P, pr = P; both 0 where the clamp is active
             const float c1 = r1[k], c0 = r0[k];
             q = fmaf(c1, lp1, fmaf(c0, lp0, q));
-            const float r = fmaf(c1, dz1, c0 * dz0);
-            const float w = (c1 + c0) * (dz1 * -dz0);
+            const float r = fmaf(c1, om, -(c0 * pr));
+            const float w = (c1 + c0) * (om * pr);
             int t = 0;
 #pragma unroll
             for (int i = 0; i < GM_NP; ++i) {
