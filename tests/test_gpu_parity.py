@@ -256,35 +256,13 @@ def test_mvn_amortized_step_vs_oracle(N, J, D, H, model, miss, B):
 
 
 def _oracle_headline_chunked(eng, y, eps, model="irt_2pl", chunk=2048):
-    """The oracle on a full batch too large for one call ((B, D, D) temporaries): a full-batch loss and every gradient
-    are sums over the persons (plate scale N / B = 1), so person chunks are evaluated with spec N = chunk size and added.
-    Also returns the per-person forward values x, h and ent = 0.5 |eps|^2 + sum_k M_kk of the guide (vi.py:448-455)."""
-    N, J = y.shape
-    D, H = eng.D, eng.H
+    """The oracle on a full batch too large for one call ((B, D, D) temporaries), in person chunks, at the engine's parameters:
+    loss, every gradient, and the per-person forward values x, h and ent = 0.5 |eps|^2 + sum_k M_kk of the guide
+    (vi.py:448-455).  tests/magnitude_cases.py::oracle_chunked holds the sums."""
+    from tests.magnitude_cases import oracle_chunked
     params = {n: eng.unconstrained(n).cpu().numpy().astype(np.float64) for n in eng.names()}
-    W = {k: params["encoder$$$" + k] for k in vo.ENC_KEYS}
-    r_, c_ = vo.tril_rows_cols(D)
-    dsel = np.flatnonzero(r_ == c_)
-    loss, grads = 0.0, None
-    x_o, h_o, ent_o = np.empty((N, D)), np.empty((N, H)), np.empty(N)
-    for lo in range(0, N, chunk):
-        hi = min(N, lo + chunk)
-        yc, ec = y[lo:hi], eps[lo:hi].astype(np.float64)
-        spec = {"family": "irt", "model": model, "D": D, "Dc": 1.0, "N": hi - lo, "amortized": True, "share_cov": False,
-                "a_free": vo.default_a_free(D, J)}
-        l, g = vo.loss_and_grads(spec, params, yc, [np.arange(hi - lo)], [ec])
-        loss += l
-        grads = g if grads is None else {k: grads[k] + g[k] for k in g}
-        loc, raw, cache = vo.enc_forward(W, vo.enc_input(yc, np.float64))
-        h_o[lo:hi] = cache[2]
-        xc = loc.copy()
-        col0 = 0
-        for k in range(D):                             # row k of L: raw[(k, 0..k-1)] off the diagonal, exp on it (vi.py:452-454)
-            xc[:, k] += (raw[:, col0:col0 + k] * ec[:, :k]).sum(1) + np.exp(raw[:, col0 + k]) * ec[:, k]
-            col0 += k + 1
-        x_o[lo:hi] = xc
-        ent_o[lo:hi] = 0.5 * (ec ** 2).sum(1) + raw[:, dsel].sum(1)
-    return loss, grads, x_o, h_o, ent_o
+    assert params["encoder$$$fc21.weight"].shape[0] == eng.D and params["encoder$$$fc1.weight"].shape[0] == eng.H
+    return oracle_chunked(params, y, eps, model=model, Dc=1.0, chunk=chunk)
 
 
 Z_CLAMP = float(np.log((1.0 - vo.EPS32) / vo.EPS32))       # 15.9424: where torch's clamp_probs cuts the Bernoulli logit

@@ -117,8 +117,11 @@ __device__ __forceinline__ void enc_scales_from_max(float mw, float mb, float m1
     const int sw1 = f16_scale_exp(m1), sh = f16_scale_exp(hbound);
     int sw = f16_scale_exp(mw), sb = f16_scale_exp(mb), eb = sw + sh - sb;
     // the bias enters the accumulator chain as one more product, (b 2^sb) x 2^eb: the constant must be an fp16 normal
-    if (eb > 15) { sw -= eb - 15; eb = 15; }                // a bias far above |W| |h|: the weights give up headroom
-    if (eb < -14) { sb = sw + sh + 14; eb = -14; }          // a bias far below: it sits lower in the fp16 range
+    if (!(mb > 0.f)) {                                      // no bias term (every bias zero; f16_scale_exp(0) = 0 says nothing of
+        eb = eb > 15 ? 15 : eb < -14 ? -14 : eb;            // |W| |h|): the weights keep their headroom, the bias fragment is all
+        sb = sw + sh - eb;                                  // zeros whatever its power of two -- any sb that keeps the constant normal
+    } else if (eb > 15) { sw -= eb - 15; eb = 15; }         // a bias far above |W| |h|: the weights give up headroom
+    else if (eb < -14) { sb = sw + sh + 14; eb = -14; }     // a bias far below: it sits lower in the fp16 range
     sc[0] = ldexpf(1.f, sw1); sc[1] = ldexpf(1.f, -sw1);
     sc[2] = ldexpf(1.f, sw); sc[3] = ldexpf(1.f, sh); sc[4] = ldexpf(1.f, -(sw + sh));
     sc[5] = ldexpf(1.f, sb); sc[6] = ldexpf(1.f, eb);
