@@ -36,7 +36,7 @@ extern "C" {
 #define VX_OK 0
 #define VX_EINVAL (-1)       /* bad argument / unsupported shape */
 #define VX_EUNIMPL (-2)
-#define VX_ABI_VERSION 7
+#define VX_ABI_VERSION 8
 
 enum vx_model { VX_IRT_1PL = 1, VX_IRT_2PL = 2, VX_IRT_3PL = 3, VX_IRT_4PL = 4 }; /* vi.py:538-543 */
 
@@ -443,6 +443,20 @@ int vx_grid_posterior(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[
                       int32_t D, const void* img, const float* logw /*[G]*/, const float* coord /*[G][D]*/,
                       float* loglik /*[nb]*/, float* mean /*[nb][D]*/, float* sd /*[nb][D]*/, int32_t* argmax /*[nb]*/,
                       void* hip_stream);
+
+/* ---- Plausible values: draws of a person's node from the grid posterior p_i(g) ~ exp(logw[g] + ll[i][g]) of vx_grid_posterior
+ * (same y, rows, nb, img, logw), by the Gumbel-max rule: node[i][m] = argmax_g (logw[g] + ll[i][g] + noise(r, g, m)), ties to the
+ * lowest g.  No normalisation, no second pass, nothing of size [nb][G] touches memory, no workspace, no atomics.  The noise is
+ * counter-based: with r = row_offset + row (row = rows[i] where rows is given, else i) and m the absolute draw index,
+ *     w = philox4x32_10(lo32(r), hi32(r), g, (PV_STREAM << 16) | (m >> 2); key lo32(seed), hi32(seed)),   x = word m & 3 of w,
+ *     u = ((x >> 9) + 0.5) 2^-23  (exact in float32, 2^-24 <= u <= 1 - 2^-24),   noise = -log(-log(u)),
+ * so a draw depends on (seed, r, g, m) alone: not on the batch, on `rows`, or on how the draws are cut into launches (16 a
+ * launch, k_grid_draw.hip).  Writes node[i * stride + m] for draw0 <= m < draw0 + ndraws and nothing else.
+ * Limits: those of vx_grid_posterior (1 <= J <= 1024, 1 <= G <= 1024, nb >= 1), 1 <= ndraws, draw0 >= 0,
+ * draw0 + ndraws <= stride, draw0 + ndraws <= 1024; VX_EINVAL beyond them. */
+int vx_grid_draw(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G,
+                 const void* img, const float* logw /*[G]*/, uint64_t seed, int64_t row_offset, int32_t draw0, int32_t ndraws,
+                 int64_t stride, int32_t* node /*[nb][stride]*/, void* hip_stream);
 
 /* ---- Expected counts from the grid posteriors (the Bock-Aitkin E-step; the per-item half of what vx_grid_posterior gives per
  * person).  With p_i(g) = exp(logw[g] + ll[i][g] - loglik[i]), loglik being vx_grid_posterior's output for the same y, rows, nb,

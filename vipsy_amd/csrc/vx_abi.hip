@@ -32,6 +32,7 @@
 #include "k_vaeccdm.hip"
 #include "k_grid_post.hip"
 #include "k_grid_counts.hip"
+#include "k_grid_draw.hip"
 #include "k_grid_mstep.hip"
 
 #include <unordered_map>
@@ -2208,6 +2209,28 @@ int vx_grid_posterior(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t
     else if (D == 4) { LAUNCH_GP(4); } else if (D <= 6) { LAUNCH_GP(6); } else if (D <= 8) { LAUNCH_GP(8); } else { LAUNCH_GP(10); }
 #undef LAUNCH_GP
     VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+// Plausible values (k_grid_draw.hip): the draws go to launches of PV_CAP slots that start at multiples of 4, so that a Philox
+// call (four draws) never straddles two launches; what a draw is does not depend on the cut
+int vx_grid_draw(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, const void* img, const float* logw,
+                 uint64_t seed, int64_t row_offset, int32_t draw0, int32_t ndraws, int64_t stride, int32_t* node, void* hs) {
+    if (!y || !img || !aligned16(img) || !logw || !node) return VX_EINVAL;
+    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    if (draw0 < 0 || draw0 > PV_MAXDRAWS || ndraws < 1 || ndraws > PV_MAXDRAWS || draw0 + ndraws > PV_MAXDRAWS ||
+        (int64_t)draw0 + ndraws > stride)
+        return VX_EINVAL;
+    const int64_t units = (nb + 32 * GP_MT - 1) / (32 * GP_MT);
+    int64_t blocks = (units + GP_WAVES - 1) / GP_WAVES;
+    const int64_t cap = (int64_t)num_cu() * 2;                 // two waves a SIMD, as vx_grid_posterior
+    if (blocks > cap) blocks = cap;
+    const int hi = draw0 + ndraws;
+    for (int base = draw0 & ~3; base < hi; base += PV_CAP) {
+        hipLaunchKernelGGL(k_grid_draw, dim3((int)blocks), dim3(GP_THREADS), pv_lds_bytes(G), (hipStream_t)hs, y, rows, nb, (int)J,
+                           (int)G, (const uint4*)img, logw, seed, row_offset, base, (int)draw0, hi, stride, node);
+        VX_CHECK_LAUNCH();
+    }
     return VX_OK;
 }
 

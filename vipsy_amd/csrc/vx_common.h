@@ -155,6 +155,10 @@ __host__ __device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1
     return u32x4{c0, c1, c2, c3};
 }
 
+// Philox stream tag (counter word 3, bits 16..31) of the plausible-value draws (k_grid_draw.hip; vipsy_amd.engine.PV_STREAM).  The
+// step kernels put the particle index there, the generators SY_X / SY_Y / SY_M / SY_A (k_synth.hip: 0xE0, 0xD1, 0xD2, 0xE1).
+#define PV_STREAM 0xC7u
+
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-08f; }
 
 // four standard normals for (person gid, block) -- dims 4*block .. 4*block+3

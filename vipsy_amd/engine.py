@@ -264,6 +264,11 @@ class HipBackend(object):
                                       _hip.ptr(loglik), _hip.ptr(mean), _hip.ptr(sd), _hip.ptr(argmax), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_posterior")
 
+    def grid_draw(self, y, rows, nb, J, G, img, logw, seed, row_offset, draw0, ndraws, stride, node):
+        rc = self.L.vx_grid_draw(_hip.ptr(y), _hip.ptr(rows), nb, J, G, _hip.ptr(img), _hip.ptr(logw), int(seed), int(row_offset),
+                                 int(draw0), int(ndraws), int(stride), _hip.ptr(node), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_draw")
+
     def cdm_sf_workspace(self, cfg, nb):
         return self._size("vx_cdm_sf_workspace_floats", ctypes.byref(cfg), nb)
 
@@ -389,6 +394,8 @@ class HipBackend(object):
 SCORE_MAX_NODES = 1024           # GP_MAXG (vipsy_amd/csrc/k_grid_post.hip)
 SCORE_MAX_DIMS = 3               # IRT: the tensor-product grid stops being a method beyond three dimensions
 EM_MAX_NEWTON = 64               # GM_MAX_NEWTON (vipsy_amd/csrc/k_grid_mstep.hip)
+PV_MAX_DRAWS = 1024              # PV_MAXDRAWS (vipsy_amd/csrc/k_grid_draw.hip)
+PV_STREAM = 0xC7                 # PV_STREAM (vipsy_amd/csrc/vx_common.h): the Philox stream tag of the plausible-value draws
 
 
 def score_grid(D, nodes=61, span=6.0):
@@ -670,6 +677,9 @@ class _EngineBase(object):
     def expected_counts(self, y_u8=None, rows=None, **kw):
         self._no_grid()
 
+    def plausible_values(self, y_u8=None, rows=None, **kw):
+        self._no_grid()
+
     def item_fit(self, y_u8=None, rows=None, **kw):
         """Per-item fit statistics of the scored rows (item_fit_stats over expected_counts): `n_obs`, `md`, `rmsd` [J] and
         `observed` [J][G] as float64 device tensors, beside the `prob` [J][G] they are measured against.  One rank only."""
@@ -715,6 +725,28 @@ class _EngineBase(object):
         be.grid_posterior(y, rows, n, J, G, D, img, logw, theta, out["loglik"], out["mean"], out["sd"], out["node"])
         out["img"] = img
         return out
+
+    @staticmethod
+    def _draw_args(draws, seed):
+        """What every plausible_values refuses before it looks at the data."""
+        if isinstance(draws, bool) or not isinstance(draws, (int, np.integer)) or not 1 <= draws <= PV_MAX_DRAWS:
+            raise ValueError("draws must be an integer in 1 .. %d" % PV_MAX_DRAWS)
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be an integer in 0 .. 2**64 - 1")
+        return int(draws), int(seed)
+
+    def _grid_draws(self, y, rows, J, theta, logw, fill_tables, draws, seed, row_offset):
+        """Tables (fill_tables(img)) and the draw kernel (vx_grid_draw: Gumbel-max over the nodes, Philox noise keyed by
+        (seed, row_offset + row, node, draw)), beside _grid_posterior and like it in buffers of their own: nothing a step
+        reads is touched.  Returns (node int32 [n, draws], coord float32 [n, draws, D] = theta[node], gathered on the device)."""
+        be = self.be
+        G = int(theta.shape[0])
+        n = int(y.shape[0]) if rows is None else int(rows.numel())
+        img = torch.empty(be.grid_image_bytes(J, G), dtype=torch.uint8, device=self.dev)
+        fill_tables(img)
+        node = torch.empty(n, draws, dtype=torch.int32, device=self.dev)
+        be.grid_draw(y, rows, n, J, G, img, logw, seed, row_offset, 0, draws, draws, node)
+        return node, theta[node.long()]
 
     def _grid_counts(self, y, rows, J, theta, logw, fill_tables):
         """The posterior kernel for loglik, then the counts kernel over the same image, in per-call buffers: n1, n0 [J][G],
@@ -1741,6 +1773,20 @@ class IrtEngine(_EngineBase):
         return (y, rows, J, theta, logw,
                 lambda img: self.be.grid_table_irt(cfg, theta, int(theta.shape[0]), a, flat("b"), c, d, img))
 
+    def plausible_values(self, y_u8=None, rows=None, draws=5, seed=0, nodes=61, span=6.0):
+        """Plausible values: `draws` independent draws of each scored row's latent from its posterior on the grid of score()
+        (the N(0, I) prior times the likelihood under the item parameters as they stand): `theta` float32 (n, draws, D), the
+        coordinates of the drawn nodes, and `node` int32 (n, draws).  Inputs, grid and refusals as score().  draws: 1 .. 1024;
+        seed: 0 .. 2**64 - 1.  A draw is a function of (seed, row, node, draw index) alone -- the training rows are keyed by
+        their global person id, rows of `y_u8` by their index in it -- so more draws extend fewer, `rows` picks the full
+        call's rows, and the shards of a process group draw independently.
+        The draws sit ON grid nodes: their resolution is the node spacing (2 span / (nodes - 1) a dimension); ask for more
+        nodes for finer draws.  They are taken under the item parameters as they stand, as fixed: the uncertainty of the item
+        parameters is not in them."""
+        draws, seed = self._draw_args(draws, seed)
+        node, theta = self._grid_draws(*self._grid_call(y_u8, rows, nodes, span), draws, seed, self.gid0 if y_u8 is None else 0)
+        return {"theta": theta, "node": node}
+
     def expected_counts(self, y_u8=None, rows=None, nodes=61, span=6.0):
         """The expected-count tables of the scored rows over the grid of score() (the Bock-Aitkin E-step): `n1`, `n0` [J][G] =
         the posterior mass at node g of the persons who answered item j correctly / wrongly, `mass` [G] = the posterior mass
@@ -2168,6 +2214,16 @@ class CcdmEngine(_EngineBase):
         cfg = self.be.hodina_cfg(K, J, 0, 1.0, 0, 0, 0)
         return (y, rows, J, coord, logw,
                 lambda img: self.be.grid_table_cdm(cfg, self.cdm == "dino", self.q, self.view("g"), self.view("s"), img))
+
+    def plausible_values(self, y_u8=None, rows=None, draws=5, seed=0):
+        """Plausible values: `draws` independent draws of each scored row's attribute pattern from its posterior over the 2^K
+        patterns (the uniform prior of score() times the likelihood under the item parameters as they stand): `attr` float32
+        (n, draws, K), the attribute bits of the drawn patterns, and `pattern` int32 (n, draws).  y_u8 / rows, draws, seed and
+        the keying of the noise as IrtEngine.plausible_values.  The nodes here ARE the patterns: nothing is discretised.  The
+        draws are taken under the item parameters as they stand, as fixed: their uncertainty is not in them."""
+        draws, seed = self._draw_args(draws, seed)
+        node, attr = self._grid_draws(*self._grid_call(y_u8, rows), draws, seed, self.gid0 if y_u8 is None else 0)
+        return {"attr": attr, "pattern": node}
 
     def expected_counts(self, y_u8=None, rows=None):
         """The expected-count tables of the scored rows over the 2^K patterns (IrtEngine.expected_counts): `n1`, `n0` [J][2^K],

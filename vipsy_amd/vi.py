@@ -210,6 +210,15 @@ class BasePsy(object):
         VCCDM: attr_prob, pattern, loglik (CcdmEngine.score).  The other classes refuse."""
         return self.engine.score(self._score_data(data), **kw)
 
+    def plausible_values(self, data=None, **kw):
+        """Plausible values: draws of each person's latent from the exact grid posterior of score() (`data` None: the training
+        data; with a `group` this rank's shard, keyed by global person id) -- VIRT / VaeIRT with x_feature <= 3: theta
+        [persons, draws, x_feature] and node [persons, draws] (IrtEngine.plausible_values: draws=5, seed=0, nodes=61,
+        span=6.0); VCCDM: attr [persons, draws, K] and pattern [persons, draws] (CcdmEngine.plausible_values: draws=5, seed=0).
+        The draws sit on grid nodes, so their resolution is the node spacing: use more nodes for finer draws.  They are taken
+        under the item parameters as they stand, without item-parameter uncertainty.  The other classes refuse."""
+        return self.engine.plausible_values(self._score_data(data), **kw)
+
     def expected_counts(self, data=None, **kw):
         """The expected-count tables of the persons in `data` (None: the training data) over the grid of score(): device
         tensors n1, n0 [items][nodes], mass [nodes], prob [items][nodes], and theta / logw (IRT) or patterns (VCCDM); see
