@@ -103,6 +103,32 @@ def cdm_case(case):
     return {"name": name, "N": N, "J": J, "cdm": cdm, "K": K, "q": q, "y": y, "params": p}
 
 
+SECOND_UNIT_TAIL = 97
+_SECOND = {}
+
+
+def second_unit_case(cus):
+    """The case in which a wave of the person-on-lane kernels takes a SECOND unit (k_grid_post, k_grid_draw: a launch stops at
+    2 blocks a CU, 4 waves a block, 64 persons a unit): 2 * cus * 256 + 97 persons, 9 items (rows start at every byte alignment;
+    one item chunk), 2PL, 5 nodes (one node tile).  The first 2 * cus * 256 rows -- every wave's first unit -- are coin flips with
+    about 70 % of the cells missing; the last 97, the second units of two waves, are drawn as irt_case draws them, except
+    eight of them with no answer at all, whose loglik is of the order of 1e-6: one missing cell carried over from the first
+    unit changes its bits.  What a unit leaves behind must not reach the next; the oracle is that of the last 97 rows alone.
+    (irt_condition does not hold on five nodes and is not asked: it is about what the quadrature means, not what the kernel
+    computes.)  Computed once for a device; callers must not modify it."""
+    if cus not in _SECOND:
+        T = SECOND_UNIT_TAIL
+        cs = irt_case(("second_unit_2pl_j9", T, 9, "irt_2pl", 1, 1.0, 5, 0.20, (0.5, 1.5), 17))
+        y_tail = cs["y"]
+        y_tail[[3, 17, 31, 32, 47, 63, 64, 96]] = 255               # both person tiles of the first unit, and the second unit
+        rng = np.random.RandomState(18)
+        head = (rng.uniform(size=(2 * cus * 256, cs["J"])) < 0.5).astype(np.uint8)
+        head[rng.uniform(size=head.shape) < 0.70] = 255
+        cs.update(N=len(head) + T, y=np.concatenate([head, y_tail]), y_tail=y_tail, tail=np.arange(len(head), len(head) + T))
+        _SECOND[cus] = (cs, irt_oracle(cs, y=y_tail))
+    return _SECOND[cus]
+
+
 # ---- the oracle ----------------------------------------------------------------------------------------------------------
 def irt_grid_loglik(model, theta, params, Dc, y):
     """ll[i][g] = log p(y_i | x = theta_g): vo.irt_loglik at every node.  params: unconstrained leaves (any float dtype)."""

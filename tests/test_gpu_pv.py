@@ -87,6 +87,27 @@ def test_rows_are_keyed_by_their_index_and_seeds_differ():
     assert changed >= 0.5
 
 
+def test_a_waves_second_unit_starts_clean():
+    """sc.second_unit_case: two waves take a second unit.  The draws of the last 97 rows behind the others are the bits of the
+    call that takes those rows alone (`rows`: keyed by the same row index), and both are the oracle's draws."""
+    from vipsy_amd.engine import score_grid
+    cs, _ = sc.second_unit_case(torch.cuda.get_device_properties(_dev()).multi_processor_count)
+    eng = _irt_engine(cs)
+    kw = dict(draws=5, seed=pv.SEED, nodes=cs["nodes"], span=cs["span"])
+    full = eng.plausible_values(**kw)
+    tail = torch.from_numpy(cs["tail"]).to(_dev())
+    alone = eng.plausible_values(rows=tail, **kw)
+    torch.cuda.synchronize()
+    assert full["node"].shape == (cs["N"], 5) and alone["node"].shape == (sc.SECOND_UNIT_TAIL, 5)
+    for key in ("theta", "node"):
+        assert torch.equal(full[key][tail], alone[key]), key
+    theta, logw = score_grid(cs["D"], cs["nodes"], cs["span"])
+    f = sc.irt_grid_loglik(cs["model"], theta, cs["params"], cs["Dc"], cs["y_tail"]) + logw.astype(np.float64)[None, :]
+    want_node, gap = pv.draw(f, pv.gumbel(pv.SEED, cs["tail"], len(logw), 5))
+    _hold_draws(cs["name"], _np(alone["node"]), want_node, gap)
+    assert np.array_equal(_np(alone["theta"])[:, :, 0], theta[:, 0][_np(alone["node"])])
+
+
 def test_pure_noise_on_1024_equal_nodes():
     """65 rows without a response over 1 024 equally weighted nodes: f is one constant, every draw is the argmax of the noise
     alone -- the counter layout over all 32 node tiles and both tails of the noise."""

@@ -159,6 +159,24 @@ def test_repeated_calls_and_row_subsets_give_the_same_bits():
         eng.score(rows=np.array([0, 100]), nodes=cs["nodes"])
 
 
+def test_a_waves_second_unit_starts_clean():
+    """sc.second_unit_case: more persons than one launch has lanes for, so that two waves take a second unit.  The last 97 rows
+    scored behind the others give the bits they give alone, and both hold to their oracle."""
+    cs, want = sc.second_unit_case(torch.cuda.get_device_properties(_dev()).multi_processor_count)
+    eng = _irt_engine(cs)
+    full = eng.score(nodes=cs["nodes"], span=cs["span"])
+    alone = eng.score(torch.from_numpy(cs["y_tail"]), nodes=cs["nodes"], span=cs["span"])
+    torch.cuda.synchronize()
+    assert full["loglik"].shape == (cs["N"],) and alone["loglik"].shape == (sc.SECOND_UNIT_TAIL,)
+    tail = torch.from_numpy(cs["tail"]).to(_dev())
+    behind = {k: v[tail] for k, v in full.items()}
+    for k in ("eap", "psd", "loglik", "node"):
+        assert torch.equal(behind[k], alone[k]), k
+    _hold(cs["name"], behind, want, IRT_NAMES)
+    empty = np.flatnonzero((cs["y_tail"] == 255).all(1))
+    assert len(empty) == 8 and (np.abs(want["loglik"][empty]) < 1e-5).all() and (_np(behind["node"])[empty] == 2).all()
+
+
 @pytest.mark.parametrize("cls,D", [("VIRT", 1), ("VaeIRT", 2)])
 def test_score_between_two_fits_changes_nothing(cls, D):
     """fit(8), score(), fit(8) leaves the parameter bits of sixteen uninterrupted iterations from the same seed."""

@@ -6,7 +6,7 @@
 // Two chained MFMA products on v_mfma_f32_32x32x16_f16, p never leaving the chip:
 //
 //   1. ll, TRANSPOSED against k_grid_post: the indicator is the A operand (lane = person l & 31, 8 items) and the table image's
-//      fragment the B operand (lane = node l & 31, the same 8 items) -- the image and gp_load8 serve as they are.  The accumulator
+//      fragment the B operand (lane = node l & 31, the same 8 items) -- the image and GP_INDICATORS serve as they are.  The accumulator
 //      has the NODE on the lane and 16 persons in the lane's registers (rows crow32(r, half)).  p = exp(f - loglik_i) with
 //      f = acc 2^-10 + miss_i + logw_g as the posterior kernel forms it: the normaliser is known, so there is no running
 //      maximum and no cross-lane traffic.
@@ -113,17 +113,8 @@ __global__ __launch_bounds__(GC_THREADS) void k_grid_counts(const uint8_t* __res
             int nmiss = 0;
             for (int kc = 0; kc < KC; ++kc) {
                 const int j0 = kc * 16 + 8 * half;
-                uint32_t yw[2];
-                gp_load8(yr + j0, yr + J, yw[0], yw[1]);
-                const int nv = J - j0;
                 f16x8 f1, f0;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const unsigned yy = (e < nv) ? ((yw[e >> 2] >> (8 * (e & 3))) & 0xffu) : 254u;
-                    f1[e] = (yy == 1u) ? (_Float16)1.0f : (_Float16)0.0f;
-                    f0[e] = (yy == 0u) ? (_Float16)1.0f : (_Float16)0.0f;
-                    nmiss += (yy == 255u) ? 1 : 0;
-                }
+                GP_INDICATORS(yr, J, j0, f1, f0, nmiss +=)
 #pragma unroll
                 for (int t = 0; t < NTG; ++t) {
                     if (nt0 + t < NT) {

@@ -3,12 +3,13 @@
 // normalisation, no second pass over the nodes and no cumulative sum across lanes: one more running maximum of the kind
 // k_grid_post keeps for the MAP node, one a draw.  Nothing of size [n][G] leaves the chip, no atomics, no workspace.
 //
-// Operand phase: that of k_grid_post (the image of vx_grid_table_*, indicator fragments by gp_load8, four
-// v_mfma_f32_32x32x16_f16 an item chunk, the person on the lane, GP_MT person tiles a wave, GP_NTG node tiles a pass), and
-// f is formed by the same expression, fmaf(acc, GP_UNSCALE, miss) + lw[g]: the same bits as the posterior kernel sees.
+// Operand phase: GP_UNIT_* / GP_PASS of k_grid_post.hip, what the posterior kernel runs (the image of vx_grid_table_*, indicator
+// fragments by GP_INDICATORS, four v_mfma_f32_32x32x16_f16 an item chunk, the person on the lane, GP_MT person tiles a wave, GP_NTG node
+// tiles a pass), and f is formed by the same expression, fmaf(acc, GP_UNSCALE, miss) + lw[g]: the bits the posterior kernel
+// sees.  What is here is what differs: the LDS staging of f, the noise, the fold and the keys.
 //
-// Noise (restated in numpy by tests/pv_cases.py): with r = row_offset + row (row = the index into y: rows[pid] where rows is
-// given, never the place in the batch), m the ABSOLUTE draw index and g the node,
+// Noise (restated in numpy by tests/pv_cases.py): with r = row_offset + row (row = the index into y, GP_UNIT_PERSON's: rows[pid] where
+// rows is given, never the place in the batch), m the ABSOLUTE draw index and g the node,
 //     w = philox4x32_10(lo32(r), hi32(r), g, (PV_STREAM << 16) | (m >> 2); key lo32(seed), hi32(seed)),   x = word m & 3 of w,
 //     u = ((x >> 9) + 0.5) 2^-23 = (2 (x >> 9) + 1) 2^-24,        noise = -log(-log(u)).
 // The odd numerator is below 2^24, so u is exact in float32 and lies in [2^-24, 1 - 2^-24]: noise in about [-2.82, 16.7],
@@ -68,70 +69,22 @@ __global__ __launch_bounds__(GP_THREADS, 2) void k_grid_draw(const uint8_t* __re
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     const int64_t n_units = (nb + 32 * GP_MT - 1) / (32 * GP_MT);
     for (int64_t unit = (int64_t)blockIdx.x * GP_WAVES + wave; unit < n_units; unit += (int64_t)gridDim.x * GP_WAVES) {
-        const uint8_t* yr[GP_MT];
-        int64_t pid[GP_MT];
-        uint32_t r_lo[GP_MT], r_hi[GP_MT];
+        GP_UNIT_ROWS;                        // GP_UNIT_STATE in two halves around the kernel's own: register assignment follows
+        uint32_t r_lo[GP_MT], r_hi[GP_MT];   // the order of declaration, and in this order the kernel compiles to what it was
         float bv[GP_MT][PV_CAP];
         int bi[GP_MT][PV_CAP];
-        int nmiss[GP_MT];
-        float miss[GP_MT];
+        GP_UNIT_MISSING;
 #pragma unroll
         for (int mt = 0; mt < GP_MT; ++mt) {
-            pid[mt] = unit * (32 * GP_MT) + mt * 32 + l31;
-            const int64_t row = (pid[mt] < nb) ? (rows ? rows[pid[mt]] : pid[mt]) : (rows ? rows[0] : 0);   // past the end: a valid row, not stored
-            yr[mt] = y + row * J;
-            const uint64_t r = (uint64_t)row_offset + (uint64_t)row;
+            GP_UNIT_PERSON(mt);
+            const uint64_t r = (uint64_t)row_offset + (uint64_t)row;                // the noise's key, formed here: row is dead in the passes
             r_lo[mt] = (uint32_t)r; r_hi[mt] = (uint32_t)(r >> 32);
 #pragma unroll
             for (int s = 0; s < PV_CAP; ++s) { bv[mt][s] = GP_NEG; bi[mt][s] = 0x7fffffff; }
-            nmiss[mt] = 0; miss[mt] = 0.f;
         }
         for (int ng = 0; ng < NT; ng += GP_NTG) {
             f32x16 acc[GP_MT][GP_NTG];
-#pragma unroll
-            for (int mt = 0; mt < GP_MT; ++mt)
-#pragma unroll
-                for (int t = 0; t < GP_NTG; ++t) acc[mt][t] = zero16();
-            for (int kc = 0; kc < KC; ++kc) {
-                // the indicator fragments: items 16 kc + 8 half + e of the lane's person
-                f16x8 f1[GP_MT], f0[GP_MT];
-                const int j0 = kc * 16 + 8 * half;
-#pragma unroll
-                for (int mt = 0; mt < GP_MT; ++mt) {
-                    uint32_t yw[2];
-                    gp_load8(yr[mt] + j0, yr[mt] + J, yw[0], yw[1]);
-                    const int nv = J - j0;                                    // items of the row from j0 on (<= 0: none)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const unsigned yy = (e < nv) ? ((yw[e >> 2] >> (8 * (e & 3))) & 0xffu) : 254u;
-                        f1[mt][e] = (yy == 1u) ? (_Float16)1.0f : (_Float16)0.0f;
-                        f0[mt][e] = (yy == 0u) ? (_Float16)1.0f : (_Float16)0.0f;
-                        if (ng == 0) nmiss[mt] += (yy == 255u) ? 1 : 0;
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < GP_NTG; ++t) {
-                    if (ng + t < NT) {
-                        const uint4* p = img + (((int64_t)(ng + t) * KC + kc) * 4) * 64 + lane;
-                        const f16x8 a1h = __builtin_bit_cast(f16x8, p[0]), a1l = __builtin_bit_cast(f16x8, p[64]);
-                        const f16x8 a0h = __builtin_bit_cast(f16x8, p[128]), a0l = __builtin_bit_cast(f16x8, p[192]);
-#pragma unroll
-                        for (int mt = 0; mt < GP_MT; ++mt) {
-                            acc[mt][t] = mfma_f16(a1h, f1[mt], acc[mt][t]);
-                            acc[mt][t] = mfma_f16(a1l, f1[mt], acc[mt][t]);
-                            acc[mt][t] = mfma_f16(a0h, f0[mt], acc[mt][t]);
-                            acc[mt][t] = mfma_f16(a0l, f0[mt], acc[mt][t]);
-                        }
-                    }
-                }
-            }
-            if (ng == 0) {
-#pragma unroll
-                for (int mt = 0; mt < GP_MT; ++mt) {
-                    const int tot = nmiss[mt] + __shfl_xor(nmiss[mt], 32, 64);      // the other half of the items
-                    miss[mt] = (float)tot * VX_LOGP_MISSING;
-                }
-            }
+            GP_PASS(acc)
             // the nodes of this pass, tile by tile: f through the lane's column of the staging, then node by node
 #pragma unroll
             for (int t = 0; t < GP_NTG; ++t) {

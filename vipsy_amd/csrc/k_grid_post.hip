@@ -19,6 +19,9 @@
 // fragment.  Nodes >= G and items >= J are ZERO rows (and carry log-weight -inf in the main kernel): ragged edges live in
 // the tables, not in the loops.
 //
+// Shared with k_grid_draw.hip and k_grid_counts.hip, which include this file: the byte-to-indicator decoding (GP_INDICATORS, all
+// three) and the operand phase of the person-on-lane kernels (GP_UNIT_STATE / GP_UNIT_PERSON / GP_PASS; posterior and draw).
+//
 // Limits (vx_grid_*: VX_EINVAL beyond): J <= 1024, G <= 1024, D <= 10, nb >= 1.
 #pragma once
 #include "vx_common.h"
@@ -126,6 +129,75 @@ __device__ __forceinline__ void gp_load8(const uint8_t* p, const uint8_t* end, u
     hi = __builtin_amdgcn_alignbyte(w2, w1, sh);
 }
 
+// The operand phase of the grid kernels, written once.  These are macros, not inline functions: a helper is simplified on its
+// own before it is inlined, the loops then reach the back end in another shape, and k_grid_draw, which sits at the edge of its
+// register budget, pays for it (measured: docs/NOTEBOOK.md).  Expanded in place the kernels compile to what they were.
+//
+// GP_INDICATORS: the indicator fragments of one response row at items j0 .. j0 + 7 (a lane's eight of item chunk kc: j0 = 16 kc +
+// 8 half): f1[e] = [y == 1], f0[e] = [y == 0], exact in fp16; COUNT, a statement prefix such as `nmiss +=`, takes 1 for every
+// cell of the eight that is 255 (missing).  Bytes at or past J are 254 -- outside the problem: in neither fragment and not missing.
+#define GP_INDICATORS(yr, J, j0, f1, f0, COUNT)                                                                        \
+    {                                                                                                                  \
+        uint32_t yw[2];                                                                                                \
+        gp_load8((yr) + (j0), (yr) + (J), yw[0], yw[1]);                                                               \
+        const int nv = (J) - (j0);                                    /* items of the row from j0 on (<= 0: none) */   \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                                \
+            const unsigned yy = (e < nv) ? ((yw[e >> 2] >> (8 * (e & 3))) & 0xffu) : 254u;                             \
+            (f1)[e] = (yy == 1u) ? (_Float16)1.0f : (_Float16)0.0f;                                                    \
+            (f0)[e] = (yy == 0u) ? (_Float16)1.0f : (_Float16)0.0f;                                                    \
+            COUNT (yy == 255u) ? 1 : 0;                                                                                \
+        }                                                                                                              \
+    }
+
+// The person-on-lane kernels (k_grid_post, k_grid_draw): a wave's unit is GP_MT tiles of 32 persons.  GP_UNIT_STATE declares what
+// the operand phase keeps of them (its two halves apart for k_grid_draw, see there); GP_UNIT_PERSON(mt), inside the kernel's own loop over the tiles, sets it up: person pid[mt] =
+// 32 GP_MT unit + 32 mt + (lane & 31), `row` = that person's index into y (in scope behind the macro) -- a person past the end
+// reads a valid row, the first of the call, and is not stored -- and the missing count at zero.  Reads y, rows, nb, J, unit, l31.
+#define GP_UNIT_ROWS                                                                                                   \
+    const uint8_t* yr[GP_MT];                                                                                          \
+    int64_t pid[GP_MT]
+#define GP_UNIT_MISSING                                                                                                \
+    int nmiss[GP_MT];                                                                                                  \
+    float miss[GP_MT]
+#define GP_UNIT_STATE GP_UNIT_ROWS; GP_UNIT_MISSING
+#define GP_UNIT_PERSON(mt)                                                                                             \
+    pid[mt] = unit * (32 * GP_MT) + mt * 32 + l31;                                                                     \
+    const int64_t row = (pid[mt] < nb) ? (rows ? rows[pid[mt]] : pid[mt]) : (rows ? rows[0] : 0);                      \
+    yr[mt] = y + row * J;                                                                                              \
+    nmiss[mt] = 0; miss[mt] = 0.f
+
+// GP_PASS(acc): the scaled ll of the unit at the node tiles ng .. ng + GP_NTG - 1 into f32x16 acc[GP_MT][GP_NTG] -- every sum
+// over a fixed order of items that depends on neither the person's place in the batch nor the launch -- and, on the first pass
+// (ng == 0), miss = (#missing) VX_LOGP_MISSING.  Reads img, J, KC, NT, ng, lane, half.
+#define GP_PASS(acc)                                                                                                   \
+    _Pragma("unroll") for (int mt = 0; mt < GP_MT; ++mt)                                                               \
+        _Pragma("unroll") for (int t = 0; t < GP_NTG; ++t) acc[mt][t] = zero16();                                      \
+    for (int kc = 0; kc < KC; ++kc) {                                                                                  \
+        f16x8 f1[GP_MT], f0[GP_MT];                                                                                    \
+        const int j0 = kc * 16 + 8 * half;                                                                             \
+        _Pragma("unroll") for (int mt = 0; mt < GP_MT; ++mt)                                                           \
+            GP_INDICATORS(yr[mt], J, j0, f1[mt], f0[mt], if (ng == 0) nmiss[mt] +=)                                    \
+        _Pragma("unroll") for (int t = 0; t < GP_NTG; ++t) {                                                           \
+            if (ng + t < NT) {                                                                                         \
+                const uint4* p = img + (((int64_t)(ng + t) * KC + kc) * 4) * 64 + lane;                                \
+                const f16x8 a1h = __builtin_bit_cast(f16x8, p[0]), a1l = __builtin_bit_cast(f16x8, p[64]);             \
+                const f16x8 a0h = __builtin_bit_cast(f16x8, p[128]), a0l = __builtin_bit_cast(f16x8, p[192]);          \
+                _Pragma("unroll") for (int mt = 0; mt < GP_MT; ++mt) {                                                 \
+                    acc[mt][t] = mfma_f16(a1h, f1[mt], acc[mt][t]);                                                    \
+                    acc[mt][t] = mfma_f16(a1l, f1[mt], acc[mt][t]);                                                    \
+                    acc[mt][t] = mfma_f16(a0h, f0[mt], acc[mt][t]);                                                    \
+                    acc[mt][t] = mfma_f16(a0l, f0[mt], acc[mt][t]);                                                    \
+                }                                                                                                      \
+            }                                                                                                          \
+        }                                                                                                              \
+    }                                                                                                                  \
+    if (ng == 0) {                                                                                                     \
+        _Pragma("unroll") for (int mt = 0; mt < GP_MT; ++mt) {                                                         \
+            const int tot = nmiss[mt] + __shfl_xor(nmiss[mt], 32, 64);      /* the other half of the items */          \
+            miss[mt] = (float)tot * VX_LOGP_MISSING;                                                                   \
+        }                                                                                                              \
+    }
+
 // What a lane knows of its person over the nodes it has seen: the largest f = logw + ll and its node, and, with weights
 // w = exp(f - m), the sums S0 = sum w, S1 = sum w (theta - ref), S2 = sum w (theta - ref)^2 about ref = the coordinates of
 // THAT node.  The posterior's mass sits around its mode, so the moments about it are of the size of the variance itself:
@@ -177,67 +249,18 @@ __global__ __launch_bounds__(GP_THREADS) void k_grid_post(const uint8_t* __restr
     __syncthreads();
     const int64_t n_units = (nb + 32 * GP_MT - 1) / (32 * GP_MT);
     for (int64_t unit = (int64_t)blockIdx.x * GP_WAVES + wave; unit < n_units; unit += (int64_t)gridDim.x * GP_WAVES) {
-        const uint8_t* yr[GP_MT];
-        int64_t pid[GP_MT];
+        GP_UNIT_STATE;
         GpState<DP> st[GP_MT];
-        int nmiss[GP_MT];
-        float miss[GP_MT];
 #pragma unroll
         for (int mt = 0; mt < GP_MT; ++mt) {
-            pid[mt] = unit * (32 * GP_MT) + mt * 32 + l31;
-            const int64_t row = (pid[mt] < nb) ? (rows ? rows[pid[mt]] : pid[mt]) : (rows ? rows[0] : 0);   // past the end: a valid row, not stored
-            yr[mt] = y + row * J;
+            GP_UNIT_PERSON(mt);
             st[mt].m = GP_NEG; st[mt].s0 = 0.f; st[mt].idx = 0x7fffffff;
 #pragma unroll
             for (int d = 0; d < DP; ++d) { st[mt].ref[d] = 0.f; st[mt].s1[d] = 0.f; st[mt].s2[d] = 0.f; }
-            nmiss[mt] = 0; miss[mt] = 0.f;
         }
         for (int ng = 0; ng < NT; ng += GP_NTG) {
             f32x16 acc[GP_MT][GP_NTG];
-#pragma unroll
-            for (int mt = 0; mt < GP_MT; ++mt)
-#pragma unroll
-                for (int t = 0; t < GP_NTG; ++t) acc[mt][t] = zero16();
-            for (int kc = 0; kc < KC; ++kc) {
-                // the indicator fragments: items 16 kc + 8 half + e of the lane's person
-                f16x8 f1[GP_MT], f0[GP_MT];
-                const int j0 = kc * 16 + 8 * half;
-#pragma unroll
-                for (int mt = 0; mt < GP_MT; ++mt) {
-                    uint32_t yw[2];
-                    gp_load8(yr[mt] + j0, yr[mt] + J, yw[0], yw[1]);
-                    const int nv = J - j0;                                    // items of the row from j0 on (<= 0: none)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const unsigned yy = (e < nv) ? ((yw[e >> 2] >> (8 * (e & 3))) & 0xffu) : 254u;
-                        f1[mt][e] = (yy == 1u) ? (_Float16)1.0f : (_Float16)0.0f;
-                        f0[mt][e] = (yy == 0u) ? (_Float16)1.0f : (_Float16)0.0f;
-                        if (ng == 0) nmiss[mt] += (yy == 255u) ? 1 : 0;
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < GP_NTG; ++t) {
-                    if (ng + t < NT) {
-                        const uint4* p = img + (((int64_t)(ng + t) * KC + kc) * 4) * 64 + lane;
-                        const f16x8 a1h = __builtin_bit_cast(f16x8, p[0]), a1l = __builtin_bit_cast(f16x8, p[64]);
-                        const f16x8 a0h = __builtin_bit_cast(f16x8, p[128]), a0l = __builtin_bit_cast(f16x8, p[192]);
-#pragma unroll
-                        for (int mt = 0; mt < GP_MT; ++mt) {
-                            acc[mt][t] = mfma_f16(a1h, f1[mt], acc[mt][t]);
-                            acc[mt][t] = mfma_f16(a1l, f1[mt], acc[mt][t]);
-                            acc[mt][t] = mfma_f16(a0h, f0[mt], acc[mt][t]);
-                            acc[mt][t] = mfma_f16(a0l, f0[mt], acc[mt][t]);
-                        }
-                    }
-                }
-            }
-            if (ng == 0) {
-#pragma unroll
-                for (int mt = 0; mt < GP_MT; ++mt) {
-                    const int tot = nmiss[mt] + __shfl_xor(nmiss[mt], 32, 64);      // the other half of the items
-                    miss[mt] = (float)tot * VX_LOGP_MISSING;
-                }
-            }
+            GP_PASS(acc)
             // the nodes of this pass, into the lane's running state
 #pragma unroll
             for (int t = 0; t < GP_NTG; ++t) {

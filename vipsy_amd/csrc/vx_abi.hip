@@ -2155,20 +2155,34 @@ int vx_ccdm_grad(const vx_hodina_cfg* cfg, int32_t dino, const uint8_t* y, const
 
 // ------------------------------------------------------------------------------------------------
 // Person scores on a grid of latent nodes (k_grid_post.hip): two table builders and one kernel
+
+// the shape limits every vx_grid_* entry shares (entries without persons pass nb = 1)
+static bool grid_shape_ok(int64_t J, int64_t G, int64_t nb) {
+    return J >= 1 && J <= GP_MAXJ && G >= 1 && G <= GP_MAXG && nb >= 1 && nb <= ((int64_t)1 << 48);
+}
+// cells of the operand image, its zero padding included: what a table builder fills
+static int64_t grid_image_cells(int J, int G) { return (int64_t)gp_nt(G) * 32 * gp_kc(J) * 16; }
+// blocks of a person-on-lane launch (k_grid_post, k_grid_draw): a wave takes units of 32 * GP_MT persons, and the launch stops
+// at two blocks a CU -- two waves a SIMD; a block's first act is to fill its LDS
+static int grid_unit_blocks(int64_t nb) {
+    const int64_t units = (nb + 32 * GP_MT - 1) / (32 * GP_MT);
+    const int64_t blocks = (units + GP_WAVES - 1) / GP_WAVES, cap = (int64_t)num_cu() * 2;
+    return (int)(blocks < cap ? blocks : cap);
+}
+
 int64_t vx_grid_image_bytes(int32_t J, int32_t G) {
-    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG) return VX_EINVAL;
+    if (!grid_shape_ok(J, G, 1)) return VX_EINVAL;
     return gp_image_bytes(J, G);
 }
 
 int vx_grid_table_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* a, const float* b, const float* c_un,
                       const float* d_un, void* img, void* hs) {
-    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GP_MAXD || cfg->J < 1 || cfg->J > GP_MAXJ ||
-        G < 1 || G > GP_MAXG || !theta || !b || !img || !aligned16(img))
+    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GP_MAXD || !grid_shape_ok(cfg->J, G, 1) || !theta || !b ||
+        !img || !aligned16(img))
         return VX_EINVAL;
     if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
         return VX_EINVAL;
-    const int64_t cells = (int64_t)gp_nt(G) * 32 * gp_kc(cfg->J) * 16;
-    const int blocks = grid_1d(cells, 256);
+    const int blocks = grid_1d(grid_image_cells((int)cfg->J, (int)G), 256);
     hipStream_t st = (hipStream_t)hs;
 #define LAUNCH_GT(M)                                                                                                  \
     hipLaunchKernelGGL((k_grid_table_irt<M>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, \
@@ -2185,9 +2199,8 @@ int vx_grid_table_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, co
     if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || cfg->J > GP_MAXJ || (dino != 0 && dino != 1) || !q || !g_un || !s_un || !img ||
         !aligned16(img))
         return VX_EINVAL;
-    const int64_t cells = (int64_t)gp_nt(1 << cfg->K) * 32 * gp_kc(cfg->J) * 16;
-    hipLaunchKernelGGL(k_grid_table_cdm, dim3(grid_1d(cells, 256)), dim3(256), 0, (hipStream_t)hs, (int)cfg->K, (int)cfg->J,
-                       (int)dino, q, g_un, s_un, (uint16_t*)img);
+    hipLaunchKernelGGL(k_grid_table_cdm, dim3(grid_1d(grid_image_cells((int)cfg->J, 1 << cfg->K), 256)), dim3(256), 0, (hipStream_t)hs,
+                       (int)cfg->K, (int)cfg->J, (int)dino, q, g_un, s_un, (uint16_t*)img);
     VX_CHECK_LAUNCH();
     return VX_OK;
 }
@@ -2195,15 +2208,12 @@ int vx_grid_table_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, co
 int vx_grid_posterior(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, int32_t D, const void* img,
                       const float* logw, const float* coord, float* loglik, float* mean, float* sd, int32_t* argmax, void* hs) {
     if (!y || !img || !aligned16(img) || !logw || !coord || !loglik || !mean || !sd || !argmax) return VX_EINVAL;
-    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || D < 1 || D > GP_MAXD || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
-    const int64_t units = (nb + 32 * GP_MT - 1) / (32 * GP_MT);
-    int64_t blocks = (units + GP_WAVES - 1) / GP_WAVES;
-    const int64_t cap = (int64_t)num_cu() * 2;                 // two waves a SIMD; a block's first act is to fill its LDS
-    if (blocks > cap) blocks = cap;
+    if (!grid_shape_ok(J, G, nb) || D < 1 || D > GP_MAXD) return VX_EINVAL;
+    const int blocks = grid_unit_blocks(nb);
     hipStream_t st = (hipStream_t)hs;
     const uint4* im = (const uint4*)img;
 #define LAUNCH_GP(DPV)                                                                                                \
-    hipLaunchKernelGGL((k_grid_post<DPV>), dim3((int)blocks), dim3(GP_THREADS), (size_t)gp_nt(G) * 32 * (DPV + 1) * sizeof(float), \
+    hipLaunchKernelGGL((k_grid_post<DPV>), dim3(blocks), dim3(GP_THREADS), (size_t)gp_nt(G) * 32 * (DPV + 1) * sizeof(float), \
                        st, y, rows, nb, (int)J, (int)G, (int)D, im, logw, coord, loglik, mean, sd, argmax)
     if (D == 1) { LAUNCH_GP(1); } else if (D == 2) { LAUNCH_GP(2); } else if (D == 3) { LAUNCH_GP(3); }
     else if (D == 4) { LAUNCH_GP(4); } else if (D <= 6) { LAUNCH_GP(6); } else if (D <= 8) { LAUNCH_GP(8); } else { LAUNCH_GP(10); }
@@ -2217,17 +2227,14 @@ int vx_grid_posterior(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t
 int vx_grid_draw(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, const void* img, const float* logw,
                  uint64_t seed, int64_t row_offset, int32_t draw0, int32_t ndraws, int64_t stride, int32_t* node, void* hs) {
     if (!y || !img || !aligned16(img) || !logw || !node) return VX_EINVAL;
-    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb)) return VX_EINVAL;
     if (draw0 < 0 || draw0 > PV_MAXDRAWS || ndraws < 1 || ndraws > PV_MAXDRAWS || draw0 + ndraws > PV_MAXDRAWS ||
         (int64_t)draw0 + ndraws > stride)
         return VX_EINVAL;
-    const int64_t units = (nb + 32 * GP_MT - 1) / (32 * GP_MT);
-    int64_t blocks = (units + GP_WAVES - 1) / GP_WAVES;
-    const int64_t cap = (int64_t)num_cu() * 2;                 // two waves a SIMD, as vx_grid_posterior
-    if (blocks > cap) blocks = cap;
+    const int blocks = grid_unit_blocks(nb);
     const int hi = draw0 + ndraws;
     for (int base = draw0 & ~3; base < hi; base += PV_CAP) {
-        hipLaunchKernelGGL(k_grid_draw, dim3((int)blocks), dim3(GP_THREADS), pv_lds_bytes(G), (hipStream_t)hs, y, rows, nb, (int)J,
+        hipLaunchKernelGGL(k_grid_draw, dim3(blocks), dim3(GP_THREADS), pv_lds_bytes(G), (hipStream_t)hs, y, rows, nb, (int)J,
                            (int)G, (const uint4*)img, logw, seed, row_offset, base, (int)draw0, hi, stride, node);
         VX_CHECK_LAUNCH();
     }
@@ -2237,7 +2244,7 @@ int vx_grid_draw(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, i
 // Expected counts from the grid posteriors (k_grid_counts.hip): one kernel over (node groups x person chunks), then the chunks'
 // slabs added in ascending order
 int64_t vx_grid_counts_workspace_floats(int64_t nb, int32_t J, int32_t G) {
-    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb)) return VX_EINVAL;
     const GcPlan p = gc_plan(nb, J, G);
     return p.n_chunks * p.slab_len;
 }
@@ -2245,7 +2252,7 @@ int64_t vx_grid_counts_workspace_floats(int64_t nb, int32_t J, int32_t G) {
 int vx_grid_counts(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, const void* img, const float* logw,
                    const float* loglik, float* n1, float* n0, float* mass, float* workspace, void* hs) {
     if (!y || !img || !aligned16(img) || !logw || !loglik || !n1 || !n0 || !mass || !workspace) return VX_EINVAL;
-    if (J < 1 || J > GP_MAXJ || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb)) return VX_EINVAL;
     const GcPlan p = gc_plan(nb, J, G);
     hipStream_t st = (hipStream_t)hs;
     const uint4* im = (const uint4*)img;
@@ -2273,8 +2280,8 @@ int vx_grid_counts(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J,
 // The M-step on the expected-count tables (k_grid_mstep.hip): one wave an item, every Newton step inside the one launch
 int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0, const float* a_free,
                       float* a, float* b, int32_t newton, void* hs) {
-    if (!cfg || (cfg->model != 1 && cfg->model != 2) || cfg->D < 1 || cfg->D > GM_MAXD || cfg->J < 1 || cfg->J > GP_MAXJ ||
-        G < 1 || G > GP_MAXG || newton < 1 || newton > GM_MAX_NEWTON || !theta || !n1 || !n0 || !b)
+    if (!cfg || (cfg->model != 1 && cfg->model != 2) || cfg->D < 1 || cfg->D > GM_MAXD || !grid_shape_ok(cfg->J, G, 1) ||
+        newton < 1 || newton > GM_MAX_NEWTON || !theta || !n1 || !n0 || !b)
         return VX_EINVAL;
     if ((cfg->model == 1 && cfg->D != 1) || (cfg->model == 2 && !a)) return VX_EINVAL;
     const dim3 grid((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES));

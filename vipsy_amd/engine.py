@@ -15,6 +15,8 @@ import numpy as np
 import torch
 
 from . import _hip
+from .grid import (EM_MAX_NEWTON, PV_MAX_DRAWS, PV_STREAM, SCORE_MAX_DIMS, SCORE_MAX_NODES, GridCall, GridMixin,  # noqa: F401
+                   grid_image_prob, item_fit_stats, score_grid)     # (re-exported: the grid family lives in grid.py)
 
 MODEL_CODE = {"irt_1pl": 1, "irt_2pl": 2, "irt_3pl": 3, "irt_4pl": 4}       # vi.py:538-543
 LOSS_RING = 64                                                               # VX_LOSS_RING (include/vipsy_amd.h)
@@ -391,79 +393,6 @@ class HipBackend(object):
         _hip.check(rc, "vx_philox_normals")
 
 
-SCORE_MAX_NODES = 1024           # GP_MAXG (vipsy_amd/csrc/k_grid_post.hip)
-SCORE_MAX_DIMS = 3               # IRT: the tensor-product grid stops being a method beyond three dimensions
-EM_MAX_NEWTON = 64               # GM_MAX_NEWTON (vipsy_amd/csrc/k_grid_mstep.hip)
-PV_MAX_DRAWS = 1024              # PV_MAXDRAWS (vipsy_amd/csrc/k_grid_draw.hip)
-PV_STREAM = 0xC7                 # PV_STREAM (vipsy_amd/csrc/vx_common.h): the Philox stream tag of the plausible-value draws
-
-
-def score_grid(D, nodes=61, span=6.0):
-    """The quadrature grid of IrtEngine.score: `nodes` equally spaced points on [-span, span] in each of the D dimensions
-    (tensor product, dimension 0 slowest: node g = (i_0 * nodes + i_1) * nodes + i_2 sits at (p[i_0], p[i_1], p[i_2])), weights
-    proportional to exp(-|theta|^2 / 2) -- the N(0, I) prior of the model (vi.py:590) -- normalised to sum 1.
-    Returns (theta float32 [G, D], logw float32 [G]); `nodes` may also be an explicit pair (theta [G, D], logw [G])."""
-    D = int(D)
-    if not 1 <= D <= SCORE_MAX_DIMS:
-        raise ValueError("grid scores need 1 <= x_feature <= %d (got %d): a tensor-product grid of n nodes a dimension has "
-                         "n**D points, and the kernel takes at most %d" % (SCORE_MAX_DIMS, D, SCORE_MAX_NODES))
-    if isinstance(nodes, (tuple, list)):
-        if len(nodes) != 2:
-            raise ValueError("explicit nodes are a pair (theta [G, D], logw [G])")
-        theta = np.asarray(nodes[0], dtype=np.float64)
-        logw = np.asarray(nodes[1], dtype=np.float64).reshape(-1)
-        if theta.ndim == 1 and D == 1:
-            theta = theta[:, None]
-        if theta.ndim != 2 or theta.shape[1] != D or theta.shape[0] != logw.shape[0]:
-            raise ValueError("explicit nodes: theta must be [G, %d] and logw [G]" % D)
-        if not 1 <= theta.shape[0] <= SCORE_MAX_NODES:
-            raise ValueError("explicit nodes: 1 <= G <= %d" % SCORE_MAX_NODES)
-        if not (np.isfinite(theta).all() and np.isfinite(logw).all()):
-            raise ValueError("explicit nodes: theta and logw must be finite")
-        return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(logw, dtype=np.float32)
-    if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or nodes < 2:
-        raise ValueError("nodes must be an integer >= 2 (points per dimension) or a pair (theta, logw)")
-    if not (isinstance(span, (int, float, np.floating, np.integer)) and np.isfinite(span) and span > 0):
-        raise ValueError("span must be a positive finite number")
-    n = int(nodes)
-    if n ** D > SCORE_MAX_NODES:
-        raise ValueError("%d nodes in each of %d dimensions are %d grid points; the kernel takes at most %d" %
-                         (n, D, n ** D, SCORE_MAX_NODES))
-    p = np.linspace(-float(span), float(span), n)
-    theta = np.stack([m.reshape(-1) for m in np.meshgrid(*([p] * D), indexing="ij")], axis=1)
-    lw = -0.5 * (theta ** 2).sum(axis=1)
-    lw = lw - (lw.max() + np.log(np.exp(lw - lw.max()).sum()))
-    return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
-
-
-def grid_image_prob(img, J, G):
-    """P(y_j = 1 | node g), float32 [J][G], read back from the operand image of vx_grid_table_* (k_grid_post.hip: [node tile][item
-    chunk][T1 head, T1 low, T0 head, T0 low][64 lanes][8 fp16], lane = node % 32 + 32 * (item % 16 // 8), values T * 2^10): the
-    exponential of the very T1 the kernels multiply with, not a second evaluation of the response function."""
-    KC, NT = (J + 15) // 16, (G + 31) // 32
-    t = img.view(torch.float16).view(NT, KC, 4, 2, 32, 8)[:, :, 0:2].to(torch.float64)
-    t1 = (t[:, :, 0] + t[:, :, 1]) / 1024.0                                   # [node tile][item chunk][item half][node][item]
-    t1 = t1.permute(1, 2, 4, 0, 3).reshape(KC * 16, NT * 32)[:J, :G]
-    return torch.exp(t1).to(torch.float32).contiguous()
-
-
-def item_fit_stats(n1, n0, prob):
-    """Per-item fit from the expected counts, in float64 on the tables' device.  With n = n1 + n0, N_j = sum_g n[j][g] and every
-    sum over the nodes with n[j][g] > 0: n_obs = N_j (the persons who answered j), md = sum (n1 - n prob) / N_j, rmsd =
-    sqrt(sum (n1 - n prob)^2 / n / N_j), observed = n1 / n (NaN where n = 0).  An item nobody answered: NaN, NaN, n_obs 0."""
-    n1, n0, prob = n1.to(torch.float64), n0.to(torch.float64), prob.to(torch.float64)
-    n = n1 + n0
-    pos = n > 0
-    zero = torch.zeros_like(n)
-    n_obs = torch.where(pos, n, zero).sum(1)
-    safe = torch.where(pos, n, torch.ones_like(n))
-    resid = torch.where(pos, n1 - n * prob, zero)
-    md = resid.sum(1) / n_obs                                                 # 0 / 0 = NaN: nobody answered
-    rmsd = torch.sqrt((resid * resid / safe).sum(1) / n_obs)
-    observed = torch.where(pos, n1 / safe, torch.full_like(n, float("nan")))
-    return {"n_obs": n_obs, "md": md, "rmsd": rmsd, "observed": observed}
-
-
 _ADAM_NOOP = {"weight_decay": 0, "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
               "differentiable": False, "fused": None}
 
@@ -665,168 +594,13 @@ class _EngineBase(object):
     def _phase(self, name):
         return _Phase(self.events, name)
 
-    # -- person scores on a grid of latent nodes (vx_grid_*; no reference counterpart) -------------
-    def _no_grid(self):
+    # -- the grid family (grid.py: GridMixin): the classes without it refuse ----------------------
+    def _no_grid(self, *args, **kw):
         raise NotImplementedError("%s has no grid scores: its pattern prior depends on a continuous latent, on the other "
                                   "persons of the batch, or it has no enumerated likelihood (IrtEngine with x_feature <= 3 and "
                                   "CcdmEngine have them)" % type(self).__name__)
 
-    def score(self, y_u8=None, rows=None, **kw):
-        self._no_grid()
-
-    def expected_counts(self, y_u8=None, rows=None, **kw):
-        self._no_grid()
-
-    def plausible_values(self, y_u8=None, rows=None, **kw):
-        self._no_grid()
-
-    def item_fit(self, y_u8=None, rows=None, **kw):
-        """Per-item fit statistics of the scored rows (item_fit_stats over expected_counts): `n_obs`, `md`, `rmsd` [J] and
-        `observed` [J][G] as float64 device tensors, beside the `prob` [J][G] they are measured against.  One rank only."""
-        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
-            raise NotImplementedError("item_fit over a process group: expected_counts() gives the local shard's sums; the "
-                                      "cross-rank sum is not built")
-        c = self.expected_counts(y_u8, rows, **kw)
-        out = item_fit_stats(c["n1"], c["n0"], c["prob"])
-        out["prob"] = c["prob"]
-        return out
-
-    def _score_inputs(self, y_u8, rows, J):
-        """The responses a score call reads ([n][J] u8 on the device, the training responses by default) and its rows."""
-        if y_u8 is None:
-            y = self.y if self.y.shape[1] == J else self.y[:, :J].contiguous()      # (without the phantom items)
-        else:
-            y = torch.as_tensor(y_u8)
-            if y.dtype != torch.uint8 or y.dim() != 2:
-                raise ValueError("responses must be a uint8 matrix (0 / 1 / 255 = missing)")
-            if y.shape[1] != J:
-                raise ValueError("responses have %d items, the model has %d" % (y.shape[1], J))
-            y = y.to(self.dev).contiguous()
-        if y.shape[0] < 1:
-            raise ValueError("no persons to score")
-        if rows is not None:
-            rows = torch.as_tensor(rows).to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
-            if rows.numel() < 1:
-                raise ValueError("no persons to score")
-            if int(rows.min()) < 0 or int(rows.max()) >= y.shape[0]:
-                raise IndexError("rows must index the %d response rows" % y.shape[0])
-        return y, rows
-
-    def _grid_posterior(self, y, rows, J, theta, logw, fill_tables):
-        """Tables (fill_tables(img)) and the posterior kernel, in buffers of their own: nothing a step reads is touched."""
-        be = self.be
-        G, D = int(theta.shape[0]), int(theta.shape[1])
-        n = int(y.shape[0]) if rows is None else int(rows.numel())
-        img = torch.empty(be.grid_image_bytes(J, G), dtype=torch.uint8, device=self.dev)
-        fill_tables(img)
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        out = {"loglik": torch.empty(n, **f32), "mean": torch.empty(n, D, **f32), "sd": torch.empty(n, D, **f32),
-               "node": torch.empty(n, dtype=torch.int32, device=self.dev)}
-        be.grid_posterior(y, rows, n, J, G, D, img, logw, theta, out["loglik"], out["mean"], out["sd"], out["node"])
-        out["img"] = img
-        return out
-
-    @staticmethod
-    def _draw_args(draws, seed):
-        """What every plausible_values refuses before it looks at the data."""
-        if isinstance(draws, bool) or not isinstance(draws, (int, np.integer)) or not 1 <= draws <= PV_MAX_DRAWS:
-            raise ValueError("draws must be an integer in 1 .. %d" % PV_MAX_DRAWS)
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be an integer in 0 .. 2**64 - 1")
-        return int(draws), int(seed)
-
-    def _grid_draws(self, y, rows, J, theta, logw, fill_tables, draws, seed, row_offset):
-        """Tables (fill_tables(img)) and the draw kernel (vx_grid_draw: Gumbel-max over the nodes, Philox noise keyed by
-        (seed, row_offset + row, node, draw)), beside _grid_posterior and like it in buffers of their own: nothing a step
-        reads is touched.  Returns (node int32 [n, draws], coord float32 [n, draws, D] = theta[node], gathered on the device)."""
-        be = self.be
-        G = int(theta.shape[0])
-        n = int(y.shape[0]) if rows is None else int(rows.numel())
-        img = torch.empty(be.grid_image_bytes(J, G), dtype=torch.uint8, device=self.dev)
-        fill_tables(img)
-        node = torch.empty(n, draws, dtype=torch.int32, device=self.dev)
-        be.grid_draw(y, rows, n, J, G, img, logw, seed, row_offset, 0, draws, draws, node)
-        return node, theta[node.long()]
-
-    def _grid_counts(self, y, rows, J, theta, logw, fill_tables):
-        """The posterior kernel for loglik, then the counts kernel over the same image, in per-call buffers: n1, n0 [J][G],
-        mass [G] and prob [J][G] = P(y_j = 1 | node g) out of the image."""
-        be = self.be
-        post = self._grid_posterior(y, rows, J, theta, logw, fill_tables)
-        G = int(theta.shape[0])
-        n = int(post["loglik"].numel())
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        out = {"n1": torch.empty(J, G, **f32), "n0": torch.empty(J, G, **f32), "mass": torch.empty(G, **f32)}
-        ws = torch.empty(be.grid_counts_workspace(n, J, G), **f32)
-        be.grid_counts(y, rows, n, J, G, post["img"], logw, post["loglik"], out["n1"], out["n0"], out["mass"], ws)
-        out["prob"] = grid_image_prob(post["img"], J, G)
-        return out
-
-    def marginal_loglik(self, y_u8=None, rows=None, **kw):
-        """sum_i log p(y_i) under the item parameters as they stand, summed on the device in a fixed order."""
-        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
-            raise NotImplementedError("marginal_loglik over a process group: score() gives the local shard's rows; the "
-                                      "cross-rank sum is not built")
-        ll = self.score(y_u8, rows, **kw)["loglik"]
-        out = torch.empty(1, dtype=torch.float32, device=self.dev)
-        ws = torch.empty(1024, dtype=torch.float32, device=self.dev)            # vx_sum_workspace_floats(); not the step's
-        self.be.sum_into(ll, int(ll.numel()), 1.0, out, ws)
-        return float(out.item())
-
-    # -- marginal maximum likelihood of the item parameters by EM on the grid posteriors (vx_grid_mstep_*) ---------------
-    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, **kw):
-        self._no_grid()
-
-    def _em_refusals(self, max_iter, newton):
-        """What every fit_em refuses before it looks at the model."""
-        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
-            raise NotImplementedError("fit_em over a process group: the expected counts are the local shard's sums and the "
-                                      "cross-rank sum is not built (one rank refits; the other ranks copy its item parameters)")
-        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
-            raise ValueError("max_iter must be an integer >= 1")
-        if isinstance(newton, bool) or not isinstance(newton, (int, np.integer)) or not 1 <= newton <= EM_MAX_NEWTON:
-            raise ValueError("newton must be an integer in 1 .. %d (Newton steps of an item inside one M-step launch)" % EM_MAX_NEWTON)
-
-    def _em_loop(self, y, J, theta, logw, fill_tables, mstep, write_back, max_iter, tol, progress):
-        """The EM iterations shared by IrtEngine.fit_em and CcdmEngine.fit_em, beside _grid_posterior / _grid_counts: tables
-        (fill_tables(img)), vx_grid_posterior, the sum of its loglik (as marginal_loglik sums it), vx_grid_counts, the M-step
-        (mstep(n1, n0), on the caller's compact parameter copies) and write_back() into the leaves.  Every buffer is made once,
-        before the loop, and is the loop's own: nothing a step reads is touched.  The float of an iteration is fetched after
-        its M-step is queued: one host sync an iteration, behind which the device is never idle for long."""
-        be = self.be
-        G, D, n = int(theta.shape[0]), int(theta.shape[1]), int(y.shape[0])
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        img = torch.empty(be.grid_image_bytes(J, G), dtype=torch.uint8, device=self.dev)
-        loglik, mean, sd = torch.empty(n, **f32), torch.empty(n, D, **f32), torch.empty(n, D, **f32)
-        node = torch.empty(n, dtype=torch.int32, device=self.dev)
-        n1, n0, mass = torch.empty(J, G, **f32), torch.empty(J, G, **f32), torch.empty(G, **f32)
-        ws = torch.empty(be.grid_counts_workspace(n, J, G), **f32)
-        total, sum_ws = torch.empty(1, **f32), torch.empty(1024, **f32)      # vx_sum_workspace_floats(); not the step's
-        bar = None
-        if progress:
-            try:
-                from tqdm import trange
-                bar = trange(max_iter)
-            except Exception:  # pragma: no cover
-                bar = None
-        hist, converged = [], False
-        for _ in range(max_iter):
-            fill_tables(img)
-            be.grid_posterior(y, None, n, J, G, D, img, logw, theta, loglik, mean, sd, node)
-            be.sum_into(loglik, n, 1.0, total, sum_ws)
-            be.grid_counts(y, None, n, J, G, img, logw, loglik, n1, n0, mass, ws)
-            mstep(n1, n0)
-            write_back()
-            hist.append(float(total.item()))
-            if bar is not None:
-                bar.update(1)
-                bar.set_postfix(loglik="{0:1.4f}".format(hist[-1]))
-            if len(hist) > 1 and hist[-1] - hist[-2] <= tol * abs(hist[-2]):
-                converged = True
-                break
-        if bar is not None:
-            bar.close()
-        return {"loglik": hist, "iterations": len(hist), "converged": converged}
+    score = expected_counts = plausible_values = item_fit = marginal_loglik = fit_em = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1407,7 +1181,7 @@ class _GraphCaptureFailed(RuntimeError):
     """Capture of a sharded step (no collective inside) failed; _EngineBase.step() falls back to the eager step."""
 
 
-class IrtEngine(_EngineBase):
+class IrtEngine(GridMixin, _EngineBase):
     """IRT ELBO-gradient step (VIRT / VaeIRT of the reference, vi.py:536-723) on one rank.
 
     Flat parameter buffer: [a: D*J | b: J | c_un: J | d_un: J | encoder (nn.Linear order, amortized only)]."""
@@ -1753,11 +1527,12 @@ class IrtEngine(_EngineBase):
         uint8, 255 = missing), by default the training responses; rows: indices into them.  Exact and deterministic, needs
         no guide: new respondents are scored like training ones.  The model's own items and dimensions only -- phantom
         items / dimensions of a padded engine are not in the tables.  x_feature <= 3 and nodes ** x_feature <= 1024."""
-        out = self._grid_posterior(*self._grid_call(y_u8, rows, nodes, span))
+        out = self._grid_posterior(self._grid_call(y_u8, rows, nodes, span))
         return {"eap": out["mean"], "psd": out["sd"], "loglik": out["loglik"], "node": out["node"]}
 
-    def _grid_call(self, y_u8, rows, nodes, span):
-        """What score() and expected_counts() hand to the grid kernels: (y, rows, J, theta, logw, fill_tables)."""
+    def _grid_call(self, y_u8, rows, nodes, span, params=None):
+        """The GridCall of score() and its kin.  params: the tensors to tabulate, compact (a [D_model][J_items] or None, b, c_un,
+        d_un [J_items] or None) -- by default the leaves as they stand, the problem's own items."""
         if self.D_model > SCORE_MAX_DIMS:
             raise NotImplementedError("grid scores need x_feature <= %d (this model has %d): a tensor-product grid of n nodes "
                                       "a dimension has n**D points" % (SCORE_MAX_DIMS, self.D_model))
@@ -1765,13 +1540,13 @@ class IrtEngine(_EngineBase):
         J, Dm = self.J_items, self.D_model
         y, rows = self._score_inputs(y_u8, rows, J)
         theta, logw = torch.from_numpy(theta_np).to(self.dev), torch.from_numpy(logw_np).to(self.dev)
-        flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()          # noqa: E731  (the problem's own items)
-        a = self.unconstrained("a").contiguous() if self.model != "irt_1pl" else None
-        c = flat("c") if self.model in ("irt_3pl", "irt_4pl") else None
-        d = flat("d") if self.model == "irt_4pl" else None
+        if params is None:
+            flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()      # noqa: E731
+            params = (self.unconstrained("a").contiguous() if self.model != "irt_1pl" else None, flat("b"),
+                      flat("c") if self.model in ("irt_3pl", "irt_4pl") else None, flat("d") if self.model == "irt_4pl" else None)
         cfg = self.be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
-        return (y, rows, J, theta, logw,
-                lambda img: self.be.grid_table_irt(cfg, theta, int(theta.shape[0]), a, flat("b"), c, d, img))
+        return GridCall(y, rows, J, theta, logw,
+                        lambda img: self.be.grid_table_irt(cfg, theta, int(theta.shape[0]), *params, img), cfg)
 
     def plausible_values(self, y_u8=None, rows=None, draws=5, seed=0, nodes=61, span=6.0):
         """Plausible values: `draws` independent draws of each scored row's latent from its posterior on the grid of score()
@@ -1784,7 +1559,7 @@ class IrtEngine(_EngineBase):
         nodes for finer draws.  They are taken under the item parameters as they stand, as fixed: the uncertainty of the item
         parameters is not in them."""
         draws, seed = self._draw_args(draws, seed)
-        node, theta = self._grid_draws(*self._grid_call(y_u8, rows, nodes, span), draws, seed, self.gid0 if y_u8 is None else 0)
+        node, theta = self._grid_draws(self._grid_call(y_u8, rows, nodes, span), draws, seed, self.gid0 if y_u8 is None else 0)
         return {"theta": theta, "node": node}
 
     def expected_counts(self, y_u8=None, rows=None, nodes=61, span=6.0):
@@ -1793,8 +1568,8 @@ class IrtEngine(_EngineBase):
         of all scored persons, `prob` [J][G] = P(y_j = 1 | node g) as the tables hold it, `theta` [G][D] and `logw` [G].
         Inputs and refusals as score(); the model's own items only.  Deterministic: the same call gives the same bits."""
         call = self._grid_call(y_u8, rows, nodes, span)
-        out = self._grid_counts(*call)
-        out["theta"], out["logw"] = call[3], call[4]
+        out = self._grid_counts(call)
+        out["theta"], out["logw"] = call.theta, call.logw
         return out
 
     def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, nodes=61, span=6.0):
@@ -1817,26 +1592,14 @@ class IrtEngine(_EngineBase):
         if self.D_model > SCORE_MAX_DIMS:
             raise NotImplementedError("fit_em needs x_feature <= %d (this model has %d): a tensor-product grid of n nodes a "
                                       "dimension has n**D points" % (SCORE_MAX_DIMS, self.D_model))
-        be, J, Dm = self.be, self.J_items, self.D_model
-        theta_np, logw_np = score_grid(Dm, nodes, span)
-        y, _ = self._score_inputs(None, None, J)
-        theta, logw = torch.from_numpy(theta_np).to(self.dev), torch.from_numpy(logw_np).to(self.dev)
-        G = int(theta.shape[0])
         # compact copies ([D_model][J_items], [J_items]) the tables and the M-step work on: the leaves may be strided views
         two = self.model != "irt_1pl"
         a = self.unconstrained("a").contiguous().clone() if two else None
         free = self.unconstrained("a", self.free).contiguous().clone() if two else None
         b = self.unconstrained("b").reshape(-1).contiguous().clone()
-        cfg = be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
-
-        def write_back():
-            if two:
-                self.unconstrained("a").copy_(a)
-            self.unconstrained("b").copy_(b.reshape(1, J))
-
-        return self._em_loop(y, J, theta, logw, lambda img: be.grid_table_irt(cfg, theta, G, a, b, None, None, img),
-                             lambda n1, n0: be.grid_mstep_irt(cfg, theta, G, n1, n0, free, a, b, newton), write_back,
-                             max_iter, tol, progress)
+        call = self._grid_call(None, None, nodes, span, params=(a, b, None, None))
+        return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_irt(call.cfg, call.theta, call.G, n1, n0, free, a, b, newton),
+                             {"a": a, "b": b} if two else {"b": b}, max_iter, tol, progress)
 
     # -- one ELBO-gradient step ------------------------------------------------------------------
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, guide_grads=True):
@@ -2171,7 +1934,7 @@ class HoDinaEngine(_EngineBase):
         self.last = {"elbo": elbo, "nb": nb}
 
 
-class CcdmEngine(_EngineBase):
+class CcdmEngine(GridMixin, _EngineBase):
     """Pattern-enumerated DINA / DINO with the uniform pattern prior and an empty guide (VCCDM, vi.py:819-865).
     Flat parameter buffer: [g_un: J | s_un: J]; no per-person state, no random numbers."""
 
@@ -2200,11 +1963,12 @@ class CcdmEngine(_EngineBase):
         """Classification of each scored row under the uniform pattern prior (the clamped Categorical of the step) and the
         item parameters as they stand: `attr_prob` (n, K) posterior mastery probabilities, `pattern` (n,) the most probable
         pattern (bit k = attribute k), `loglik` (n,) the marginal log-likelihood.  y_u8 / rows as IrtEngine.score."""
-        out = self._grid_posterior(*self._grid_call(y_u8, rows))
+        out = self._grid_posterior(self._grid_call(y_u8, rows))
         return {"attr_prob": out["mean"], "pattern": out["node"], "loglik": out["loglik"]}
 
-    def _grid_call(self, y_u8, rows):
-        """What score() and expected_counts() hand to the grid kernels: (y, rows, J, patterns, logw, fill_tables)."""
+    def _grid_call(self, y_u8, rows, params=None):
+        """The GridCall of score() and its kin: the nodes are the 2^K patterns.  params: the (g_un, s_un) [J] to tabulate, by
+        default the leaves as they stand."""
         K, J, C = self.K, self.J, 1 << self.K
         y, rows = self._score_inputs(y_u8, rows, J)
         bits = ((torch.arange(C, device=self.dev)[:, None] >> torch.arange(K, device=self.dev)[None, :]) & 1)
@@ -2212,8 +1976,9 @@ class CcdmEngine(_EngineBase):
         eps32 = float(np.finfo(np.float32).eps)
         logw = torch.full((C,), 1.0 / C, dtype=torch.float32, device=self.dev).clamp(eps32, 1.0 - eps32).log()
         cfg = self.be.hodina_cfg(K, J, 0, 1.0, 0, 0, 0)
-        return (y, rows, J, coord, logw,
-                lambda img: self.be.grid_table_cdm(cfg, self.cdm == "dino", self.q, self.view("g"), self.view("s"), img))
+        g, s_ = params if params is not None else (self.view("g"), self.view("s"))
+        return GridCall(y, rows, J, coord, logw,
+                        lambda img: self.be.grid_table_cdm(cfg, self.cdm == "dino", self.q, g, s_, img), cfg)
 
     def plausible_values(self, y_u8=None, rows=None, draws=5, seed=0):
         """Plausible values: `draws` independent draws of each scored row's attribute pattern from its posterior over the 2^K
@@ -2222,15 +1987,15 @@ class CcdmEngine(_EngineBase):
         the keying of the noise as IrtEngine.plausible_values.  The nodes here ARE the patterns: nothing is discretised.  The
         draws are taken under the item parameters as they stand, as fixed: their uncertainty is not in them."""
         draws, seed = self._draw_args(draws, seed)
-        node, attr = self._grid_draws(*self._grid_call(y_u8, rows), draws, seed, self.gid0 if y_u8 is None else 0)
+        node, attr = self._grid_draws(self._grid_call(y_u8, rows), draws, seed, self.gid0 if y_u8 is None else 0)
         return {"attr": attr, "pattern": node}
 
     def expected_counts(self, y_u8=None, rows=None):
         """The expected-count tables of the scored rows over the 2^K patterns (IrtEngine.expected_counts): `n1`, `n0` [J][2^K],
         `mass` [2^K], `prob` [J][2^K] = P(y_j = 1 | pattern) and `patterns` [2^K][K], the attribute bits of every node."""
         call = self._grid_call(y_u8, rows)
-        out = self._grid_counts(*call)
-        out["patterns"] = call[3]
+        out = self._grid_counts(call)
+        out["patterns"] = call.theta
         return out
 
     def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False):
@@ -2241,19 +2006,11 @@ class CcdmEngine(_EngineBase):
         unused.  An estimate of exactly 0 or 1 sits at the clamp, +-logit(1 - eps32), where the step kernels give it a zero
         gradient afterwards."""
         self._em_refusals(max_iter, newton)
-        be, K, J = self.be, self.K, self.J
-        y, _, _, coord, logw, _ = self._grid_call(None, None)
-        g, s_ = self.view("g").clone(), self.view("s").clone()
-        cfg = be.hodina_cfg(K, J, 0, 1.0, 0, 0, 0)
         dino = self.cdm == "dino"
-
-        def write_back():
-            self.unconstrained("g").copy_(g.reshape(1, J))
-            self.unconstrained("s").copy_(s_.reshape(1, J))
-
-        return self._em_loop(y, J, coord, logw, lambda img: be.grid_table_cdm(cfg, dino, self.q, g, s_, img),
-                             lambda n1, n0: be.grid_mstep_cdm(cfg, dino, self.q, n1, n0, g, s_), write_back, max_iter, tol,
-                             progress)
+        g, s_ = self.view("g").clone(), self.view("s").clone()
+        call = self._grid_call(None, None, params=(g, s_))
+        return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_cdm(call.cfg, dino, self.q, n1, n0, g, s_), {"g": g, "s": s_},
+                             max_iter, tol, progress)
 
     def _replayable(self, full):
         # VCCDM (vi.py:819-865; test.py:560,585,624: 100-1500 rows a step): no guide, no random numbers -- the pattern

@@ -1,0 +1,240 @@
+"""The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide -- score(), expected_counts() /
+item_fit(), fit_em(), plausible_values() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
+entries of the C ABI (k_grid_*.hip; no reference counterpart).  All of it works in buffers of its own: nothing a step reads is
+touched."""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+SCORE_MAX_NODES = 1024           # GP_MAXG (vipsy_amd/csrc/k_grid_post.hip)
+SCORE_MAX_DIMS = 3               # IRT: the tensor-product grid stops being a method beyond three dimensions
+EM_MAX_NEWTON = 64               # GM_MAX_NEWTON (vipsy_amd/csrc/k_grid_mstep.hip)
+PV_MAX_DRAWS = 1024              # PV_MAXDRAWS (vipsy_amd/csrc/k_grid_draw.hip)
+PV_STREAM = 0xC7                 # PV_STREAM (vipsy_amd/csrc/vx_common.h): the Philox stream tag of the plausible-value draws
+
+
+def score_grid(D, nodes=61, span=6.0):
+    """The quadrature grid of IrtEngine.score: `nodes` equally spaced points on [-span, span] in each of the D dimensions
+    (tensor product, dimension 0 slowest: node g = (i_0 * nodes + i_1) * nodes + i_2 sits at (p[i_0], p[i_1], p[i_2])), weights
+    proportional to exp(-|theta|^2 / 2) -- the N(0, I) prior of the model (vi.py:590) -- normalised to sum 1.
+    Returns (theta float32 [G, D], logw float32 [G]); `nodes` may also be an explicit pair (theta [G, D], logw [G])."""
+    D = int(D)
+    if not 1 <= D <= SCORE_MAX_DIMS:
+        raise ValueError("grid scores need 1 <= x_feature <= %d (got %d): a tensor-product grid of n nodes a dimension has "
+                         "n**D points, and the kernel takes at most %d" % (SCORE_MAX_DIMS, D, SCORE_MAX_NODES))
+    if isinstance(nodes, (tuple, list)):
+        if len(nodes) != 2:
+            raise ValueError("explicit nodes are a pair (theta [G, D], logw [G])")
+        theta = np.asarray(nodes[0], dtype=np.float64)
+        logw = np.asarray(nodes[1], dtype=np.float64).reshape(-1)
+        if theta.ndim == 1 and D == 1:
+            theta = theta[:, None]
+        if theta.ndim != 2 or theta.shape[1] != D or theta.shape[0] != logw.shape[0]:
+            raise ValueError("explicit nodes: theta must be [G, %d] and logw [G]" % D)
+        if not 1 <= theta.shape[0] <= SCORE_MAX_NODES:
+            raise ValueError("explicit nodes: 1 <= G <= %d" % SCORE_MAX_NODES)
+        if not (np.isfinite(theta).all() and np.isfinite(logw).all()):
+            raise ValueError("explicit nodes: theta and logw must be finite")
+        return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(logw, dtype=np.float32)
+    if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or nodes < 2:
+        raise ValueError("nodes must be an integer >= 2 (points per dimension) or a pair (theta, logw)")
+    if not (isinstance(span, (int, float, np.floating, np.integer)) and np.isfinite(span) and span > 0):
+        raise ValueError("span must be a positive finite number")
+    n = int(nodes)
+    if n ** D > SCORE_MAX_NODES:
+        raise ValueError("%d nodes in each of %d dimensions are %d grid points; the kernel takes at most %d" %
+                         (n, D, n ** D, SCORE_MAX_NODES))
+    p = np.linspace(-float(span), float(span), n)
+    theta = np.stack([m.reshape(-1) for m in np.meshgrid(*([p] * D), indexing="ij")], axis=1)
+    lw = -0.5 * (theta ** 2).sum(axis=1)
+    lw = lw - (lw.max() + np.log(np.exp(lw - lw.max()).sum()))
+    return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
+
+
+def grid_image_prob(img, J, G):
+    """P(y_j = 1 | node g), float32 [J][G], read back from the operand image of vx_grid_table_* (k_grid_post.hip: [node tile][item
+    chunk][T1 head, T1 low, T0 head, T0 low][64 lanes][8 fp16], lane = node % 32 + 32 * (item % 16 // 8), values T * 2^10): the
+    exponential of the very T1 the kernels multiply with, not a second evaluation of the response function."""
+    KC, NT = (J + 15) // 16, (G + 31) // 32
+    t = img.view(torch.float16).view(NT, KC, 4, 2, 32, 8)[:, :, 0:2].to(torch.float64)
+    t1 = (t[:, :, 0] + t[:, :, 1]) / 1024.0                                   # [node tile][item chunk][item half][node][item]
+    t1 = t1.permute(1, 2, 4, 0, 3).reshape(KC * 16, NT * 32)[:J, :G]
+    return torch.exp(t1).to(torch.float32).contiguous()
+
+
+def item_fit_stats(n1, n0, prob):
+    """Per-item fit from the expected counts, in float64 on the tables' device.  With n = n1 + n0, N_j = sum_g n[j][g] and every
+    sum over the nodes with n[j][g] > 0: n_obs = N_j (the persons who answered j), md = sum (n1 - n prob) / N_j, rmsd =
+    sqrt(sum (n1 - n prob)^2 / n / N_j), observed = n1 / n (NaN where n = 0).  An item nobody answered: NaN, NaN, n_obs 0."""
+    n1, n0, prob = n1.to(torch.float64), n0.to(torch.float64), prob.to(torch.float64)
+    n = n1 + n0
+    pos = n > 0
+    zero = torch.zeros_like(n)
+    n_obs = torch.where(pos, n, zero).sum(1)
+    safe = torch.where(pos, n, torch.ones_like(n))
+    resid = torch.where(pos, n1 - n * prob, zero)
+    md = resid.sum(1) / n_obs                                                 # 0 / 0 = NaN: nobody answered
+    rmsd = torch.sqrt((resid * resid / safe).sum(1) / n_obs)
+    observed = torch.where(pos, n1 / safe, torch.full_like(n, float("nan")))
+    return {"n_obs": n_obs, "md": md, "rmsd": rmsd, "observed": observed}
+
+
+class GridCall(namedtuple("GridCall", "y rows J theta logw fill_tables cfg")):
+    """What an engine's `_grid_call` hands to the grid kernels: the responses y ([n][J] u8 on the device) and the rows of them to
+    score (int64 on the device, or None: all), the nodes theta [G][D] with their log-weights logw [G], fill_tables(img), which
+    tabulates the item parameters into an operand image, and the cfg those tables are built from, which the M-step of the same
+    engine takes: a vx_irt_cfg from IrtEngine, a vx_hodina_cfg from CcdmEngine."""
+    n = property(lambda c: int(c.y.shape[0]) if c.rows is None else int(c.rows.numel()))
+    G = property(lambda c: int(c.theta.shape[0]))
+    D = property(lambda c: int(c.theta.shape[1]))
+
+
+class GridMixin(object):
+    """The grid methods of an engine class that brings `_grid_call(y_u8, rows, ..., params=None)` -> GridCall: its nodes and how
+    its item parameters become tables (IrtEngine, CcdmEngine)."""
+
+    @staticmethod
+    def _int_in(name, value, lo, hi=None, says=None):
+        """value as an int, refused unless it is an integer (no bool) in lo .. hi (hi None: no upper end); says: the range in words."""
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < lo or (hi is not None and value > hi):
+            raise ValueError("%s must be an integer %s" % (name, says or (">= %d" % lo if hi is None else "in %d .. %d" % (lo, hi))))
+        return int(value)
+
+    def _one_rank_only(self, message):
+        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
+            raise NotImplementedError(message)
+
+    def _em_refusals(self, max_iter, newton):
+        """What every fit_em refuses before it looks at the model."""
+        self._one_rank_only("fit_em over a process group: the expected counts are the local shard's sums and the cross-rank sum "
+                            "is not built (one rank refits; the other ranks copy its item parameters)")
+        self._int_in("max_iter", max_iter, 1)
+        self._int_in("newton", newton, 1, EM_MAX_NEWTON,
+                     "in 1 .. %d (Newton steps of an item inside one M-step launch)" % EM_MAX_NEWTON)
+
+    def _score_inputs(self, y_u8, rows, J):
+        """The responses a score call reads ([n][J] u8 on the device, the training responses by default) and its rows."""
+        if y_u8 is None:
+            y = self.y if self.y.shape[1] == J else self.y[:, :J].contiguous()      # (without the phantom items)
+        else:
+            y = torch.as_tensor(y_u8)
+            if y.dtype != torch.uint8 or y.dim() != 2:
+                raise ValueError("responses must be a uint8 matrix (0 / 1 / 255 = missing)")
+            if y.shape[1] != J:
+                raise ValueError("responses have %d items, the model has %d" % (y.shape[1], J))
+            y = y.to(self.dev).contiguous()
+        if y.shape[0] < 1:
+            raise ValueError("no persons to score")
+        if rows is not None:
+            rows = torch.as_tensor(rows).to(device=self.dev, dtype=torch.int64).reshape(-1).contiguous()
+            if rows.numel() < 1:
+                raise ValueError("no persons to score")
+            if int(rows.min()) < 0 or int(rows.max()) >= y.shape[0]:
+                raise IndexError("rows must index the %d response rows" % y.shape[0])
+        return y, rows
+
+    def _grid_image(self, call):
+        """The operand image of a call, with its tables in it."""
+        img = torch.empty(self.be.grid_image_bytes(call.J, call.G), dtype=torch.uint8, device=self.dev)
+        call.fill_tables(img)
+        return img
+
+    def _grid_posterior(self, call):
+        """Tables and the posterior kernel: loglik [n], mean, sd [n][D], node [n], and the image they came from."""
+        n, D = call.n, call.D
+        img = self._grid_image(call)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = {"loglik": torch.empty(n, **f32), "mean": torch.empty(n, D, **f32), "sd": torch.empty(n, D, **f32),
+               "node": torch.empty(n, dtype=torch.int32, device=self.dev)}
+        self.be.grid_posterior(call.y, call.rows, n, call.J, call.G, D, img, call.logw, call.theta, out["loglik"], out["mean"],
+                               out["sd"], out["node"])
+        out["img"] = img
+        return out
+
+    def _draw_args(self, draws, seed):
+        """What every plausible_values refuses before it looks at the data."""
+        return self._int_in("draws", draws, 1, PV_MAX_DRAWS), self._int_in("seed", seed, 0, 2 ** 64 - 1, "in 0 .. 2**64 - 1")
+
+    def _grid_draws(self, call, draws, seed, row_offset):
+        """Tables and the draw kernel (vx_grid_draw: Gumbel-max over the nodes, Philox noise keyed by (seed, row_offset + row,
+        node, draw)).  Returns (node int32 [n, draws], coord float32 [n, draws, D] = theta[node], gathered on the device)."""
+        img = self._grid_image(call)
+        node = torch.empty(call.n, draws, dtype=torch.int32, device=self.dev)
+        self.be.grid_draw(call.y, call.rows, call.n, call.J, call.G, img, call.logw, seed, row_offset, 0, draws, draws, node)
+        return node, call.theta[node.long()]
+
+    def _grid_counts(self, call):
+        """The posterior kernel for loglik, then the counts kernel over the same image: n1, n0 [J][G], mass [G] and prob [J][G] =
+        P(y_j = 1 | node g) out of the image."""
+        be, J, G = self.be, call.J, call.G
+        post = self._grid_posterior(call)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = {"n1": torch.empty(J, G, **f32), "n0": torch.empty(J, G, **f32), "mass": torch.empty(G, **f32)}
+        ws = torch.empty(be.grid_counts_workspace(call.n, J, G), **f32)
+        be.grid_counts(call.y, call.rows, call.n, J, G, post["img"], call.logw, post["loglik"], out["n1"], out["n0"], out["mass"], ws)
+        out["prob"] = grid_image_prob(post["img"], J, G)
+        return out
+
+    def _em_loop(self, call, mstep, leaves, max_iter, tol, progress):
+        """The EM iterations of IrtEngine.fit_em and CcdmEngine.fit_em over a call on the caller's compact parameter copies:
+        tables, vx_grid_posterior, the sum of its loglik (as marginal_loglik sums it), vx_grid_counts, the M-step (mstep(n1, n0),
+        on those copies) and the write-back of the copies into the leaves ({name: copy}).  Every buffer is made once, before the
+        loop.  The float of an iteration is fetched after its M-step is queued: one host sync an iteration, behind which the
+        device is never idle for long."""
+        be = self.be
+        y, J, theta, logw, G, D, n = call.y, call.J, call.theta, call.logw, call.G, call.D, call.n
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        img = torch.empty(be.grid_image_bytes(J, G), dtype=torch.uint8, device=self.dev)     # (filled anew every iteration)
+        loglik, mean, sd = torch.empty(n, **f32), torch.empty(n, D, **f32), torch.empty(n, D, **f32)
+        node = torch.empty(n, dtype=torch.int32, device=self.dev)
+        n1, n0, mass = torch.empty(J, G, **f32), torch.empty(J, G, **f32), torch.empty(G, **f32)
+        ws = torch.empty(be.grid_counts_workspace(n, J, G), **f32)
+        total, sum_ws = torch.empty(1, **f32), torch.empty(1024, **f32)      # vx_sum_workspace_floats(); not the step's
+        bar = None
+        if progress:
+            try:
+                from tqdm import trange
+                bar = trange(max_iter)
+            except Exception:  # pragma: no cover
+                bar = None
+        hist, converged = [], False
+        for _ in range(max_iter):
+            call.fill_tables(img)
+            be.grid_posterior(y, None, n, J, G, D, img, logw, theta, loglik, mean, sd, node)
+            be.sum_into(loglik, n, 1.0, total, sum_ws)
+            be.grid_counts(y, None, n, J, G, img, logw, loglik, n1, n0, mass, ws)
+            mstep(n1, n0)
+            for name, t in leaves.items():
+                leaf = self.unconstrained(name)
+                leaf.copy_(t.reshape(leaf.shape))
+            hist.append(float(total.item()))
+            if bar is not None:
+                bar.update(1)
+                bar.set_postfix(loglik="{0:1.4f}".format(hist[-1]))
+            if len(hist) > 1 and hist[-1] - hist[-2] <= tol * abs(hist[-2]):
+                converged = True
+                break
+        if bar is not None:
+            bar.close()
+        return {"loglik": hist, "iterations": len(hist), "converged": converged}
+
+    def item_fit(self, y_u8=None, rows=None, **kw):
+        """Per-item fit statistics of the scored rows (item_fit_stats over expected_counts): `n_obs`, `md`, `rmsd` [J] and
+        `observed` [J][G] as float64 device tensors, beside the `prob` [J][G] they are measured against.  One rank only."""
+        self._one_rank_only("item_fit over a process group: expected_counts() gives the local shard's sums; the cross-rank sum "
+                            "is not built")
+        c = self.expected_counts(y_u8, rows, **kw)
+        out = item_fit_stats(c["n1"], c["n0"], c["prob"])
+        out["prob"] = c["prob"]
+        return out
+
+    def marginal_loglik(self, y_u8=None, rows=None, **kw):
+        """sum_i log p(y_i) under the item parameters as they stand, summed on the device in a fixed order."""
+        self._one_rank_only("marginal_loglik over a process group: score() gives the local shard's rows; the cross-rank sum is "
+                            "not built")
+        ll = self.score(y_u8, rows, **kw)["loglik"]
+        out = torch.empty(1, dtype=torch.float32, device=self.dev)
+        ws = torch.empty(1024, dtype=torch.float32, device=self.dev)            # vx_sum_workspace_floats(); not the step's
+        self.be.sum_into(ll, int(ll.numel()), 1.0, out, ws)
+        return float(out.item())
