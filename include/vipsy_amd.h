@@ -36,7 +36,7 @@ extern "C" {
 #define VX_OK 0
 #define VX_EINVAL (-1)       /* bad argument / unsupported shape */
 #define VX_EUNIMPL (-2)
-#define VX_ABI_VERSION 8
+#define VX_ABI_VERSION 9
 
 enum vx_model { VX_IRT_1PL = 1, VX_IRT_2PL = 2, VX_IRT_3PL = 3, VX_IRT_4PL = 4 }; /* vi.py:538-543 */
 
@@ -496,6 +496,36 @@ int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int3
                       float* a /*[D][J] in/out, NULL for 1PL*/, float* b /*[J] in/out*/, int32_t newton, void* hip_stream);
 int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const float* n1 /*[J][2^K]*/,
                       const float* n0 /*[J][2^K]*/, float* g_un /*[J] in/out*/, float* s_un /*[J] in/out*/, void* hip_stream);
+
+/* ---- The cross-product (BHHH) information of the item parameters from the grid posteriors: with Fisher's identity the marginal
+ * score of person i for parameter k of item j is
+ *     s_i[(j,k)] = sum_g p_i(g) ( [y_ij == 1] W1[g][(j,k)] - [y_ij == 0] W0[g][(j,k)] ),   W1 = (1 - P_j(g)) u_jgk,  W0 = P_j(g) u_jgk,
+ * p_i(g) as vx_grid_counts forms it, u_g = Dc (1, theta_g) for the IRT links, ([eta = 0], -[eta = 1]) for DINA / DINO on the
+ * unconstrained g / s scale.  info = sum_i s_i s_i^T [P][P], symmetric bit for bit, over the DENSE parameter layout: column
+ * c = j K + k with K = D + 1 (k = 0: b, k = 1 + d: a_d) for 2PL, 1 for 1PL, 2 (g_un, s_un) for DINA / DINO, P = J K <= 4096;
+ * gradient = sum_i s_i [P], the gradient of the marginal log-likelihood -- by construction what the M-step of vx_grid_mstep_irt
+ * forms from n1 / n0: P, 1 - P and the clamp come from its cell (a node where the z clamp is active contributes 0).  Both are taken
+ * AT THE PARAMETERS AS THEY STAND; the inverse of info is a covariance only at the marginal maximum.
+ *   1. vx_grid_wtable_irt (cfg: model 1 | 2, D <= 3, J, Dc) / vx_grid_wtable_cdm (cfg: K, J) fill `wimg` (vx_grid_wimage_bytes(P, G)
+ *      bytes, 16-byte aligned) with W1 / W0 as fp16-pair operand images, scaled by a power of two that the image carries.
+ *   2. vx_grid_info: y, rows, nb, img, logw as vx_grid_posterior took them and loglik as it returned it.  Three chained products on
+ *      v_mfma_f32_32x32x16_f16 (fp16 pairs, fp32 accumulation): the log-likelihoods, p W (over nodes) and S^T S (over persons).
+ *      Nothing of size [nb][G] touches memory; S [persons][P] lives in `workspace` as fp16 pairs, a slab of persons (a multiple of
+ *      256) at a time -- as many as ws_floats allow --, and the slabs' matrices are added in person order.  No atomics: the same
+ *      call with the same ws_floats gives the same bits.  vx_grid_info_workspace_floats(nb, P, G): the preferred size (one slab
+ *      where 512 MB allow it); vx_grid_info_workspace_min_floats(P, G): the smallest accepted.  workspace is 16-byte aligned.
+ * Persons' 254 / 255 cells contribute nothing.  Limits: 1 <= J <= 1024, 1 <= G <= 1024, 1 <= K <= 4, nb >= 1, ws_floats at least the
+ * minimum; VX_EINVAL beyond. */
+int64_t vx_grid_wimage_bytes(int32_t P, int32_t G);
+int vx_grid_wtable_irt(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int32_t G, const float* a /*[D][J] or NULL (1PL)*/,
+                       const float* b /*[J]*/, void* wimg, void* hip_stream);
+int vx_grid_wtable_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const float* g_un, const float* s_un,
+                       void* wimg, void* hip_stream);
+int64_t vx_grid_info_workspace_floats(int64_t nb, int32_t P, int32_t G);
+int64_t vx_grid_info_workspace_min_floats(int32_t P, int32_t G);
+int vx_grid_info(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G, int32_t K,
+                 const void* img, const void* wimg, const float* logw /*[G]*/, const float* loglik /*[nb]*/, float* info /*[P][P]*/,
+                 float* gradient /*[P]*/, float* workspace, int64_t ws_floats, void* hip_stream);
 
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,

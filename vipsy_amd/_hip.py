@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VX_LIB names another build of the same sources (tests/test_gpu_schedules.py runs the oracle comparisons against a library
 # compiled with a different instruction schedule: a hazard that only one schedule hides must show in the other)
 LIB_PATH = os.environ.get("VX_LIB") or os.path.join(_HERE, "_lib", "libvipsy_hip.so")
-ABI_VERSION = 8         # include/vipsy_amd.h: VX_ABI_VERSION (struct layouts and argument lists this binding was written for)
+ABI_VERSION = 9         # include/vipsy_amd.h: VX_ABI_VERSION (struct layouts and argument lists this binding was written for)
 
 
 class VxError(RuntimeError):
@@ -133,6 +133,12 @@ SIGNATURES = {
     "vx_grid_counts": (ctypes.c_int, [_P, _P, _I64, _I32, _I32] + [_P] * 3 + [_P] * 3 + [_P, _P]),
     "vx_grid_mstep_irt": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 3 + [_P, _P, _I32, _P]),
     "vx_grid_mstep_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32] + [_P] * 3 + [_P, _P, _P]),
+    "vx_grid_wimage_bytes": (_I64, [_I32, _I32]),
+    "vx_grid_wtable_irt": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 2 + [_P, _P]),
+    "vx_grid_wtable_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32] + [_P] * 3 + [_P, _P]),
+    "vx_grid_info_workspace_floats": (_I64, [_I64, _I32, _I32]),
+    "vx_grid_info_workspace_min_floats": (_I64, [_I32, _I32]),
+    "vx_grid_info": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 4 + [_P, _P] + [_P, _I64, _P]),
     "vx_reduce_slabs": (ctypes.c_int, [_P, _I64, _I64, _F, _P, _P]),
     "vx_sum_workspace_floats": (_I64, []),
     "vx_sum": (ctypes.c_int, [_P, _I64, _F, _P, _P, _P, _P]),

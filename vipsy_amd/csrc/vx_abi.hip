@@ -34,6 +34,7 @@
 #include "k_grid_counts.hip"
 #include "k_grid_draw.hip"
 #include "k_grid_mstep.hip"
+#include "k_grid_info.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2302,6 +2303,100 @@ int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, co
         return VX_EINVAL;
     hipLaunchKernelGGL(k_grid_mstep_cdm, dim3((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES)), dim3(GM_THREADS), 0, (hipStream_t)hs,
                        (int)cfg->K, (int)cfg->J, (int)dino, q, n1, n0, g_un, s_un);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+// Item-parameter information from the grid posteriors (k_grid_info.hip): derivative tables, person scores, the SYRK over persons
+static bool grid_info_shape_ok(int64_t J, int64_t G, int64_t K, int64_t nb) {
+    return grid_shape_ok(J, G, nb) && K >= 1 && K <= GI_MAXK && J * K <= GI_MAXP;
+}
+
+int64_t vx_grid_wimage_bytes(int32_t P, int32_t G) {
+    if (P < 1 || P > GI_MAXP || G < 1 || G > GP_MAXG) return VX_EINVAL;
+    return gi_wimage_frag_bytes(P, G) + 16;
+}
+
+int vx_grid_wtable_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* a, const float* b, void* wimg, void* hs) {
+    if (!cfg || (cfg->model != 1 && cfg->model != 2) || cfg->D < 1 || cfg->D > GM_MAXD || !grid_shape_ok(cfg->J, G, 1) || !theta ||
+        !b || !wimg || !aligned16(wimg))
+        return VX_EINVAL;
+    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model == 2 && !a)) return VX_EINVAL;
+    const int P = (int)cfg->J * (cfg->model == 1 ? 1 : (int)cfg->D + 1);
+    const int blocks = grid_1d((int64_t)gp_nt(G) * 32 * gi_pt(P) * 32, 256);
+    float* trailer = (float*)((uint8_t*)wimg + gi_wimage_frag_bytes(P, G));
+    hipStream_t st = (hipStream_t)hs;
+    if (cfg->model == 1)
+        hipLaunchKernelGGL((k_grid_wtable_irt<1>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, a, b,
+                           (uint16_t*)wimg, trailer);
+    else
+        hipLaunchKernelGGL((k_grid_wtable_irt<2>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, a, b,
+                           (uint16_t*)wimg, trailer);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_wtable_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* g_un, const float* s_un, void* wimg,
+                       void* hs) {
+    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || cfg->J > GP_MAXJ || (dino != 0 && dino != 1) || !q || !g_un || !s_un || !wimg ||
+        !aligned16(wimg))
+        return VX_EINVAL;
+    const int P = 2 * (int)cfg->J, G = 1 << cfg->K;
+    float* trailer = (float*)((uint8_t*)wimg + gi_wimage_frag_bytes(P, G));
+    hipLaunchKernelGGL(k_grid_wtable_cdm, dim3(grid_1d((int64_t)gp_nt(G) * 32 * gi_pt(P) * 32, 256)), dim3(256), 0, (hipStream_t)hs,
+                       (int)cfg->K, (int)cfg->J, (int)dino, q, g_un, s_un, (uint16_t*)wimg, trailer);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int64_t vx_grid_info_workspace_floats(int64_t nb, int32_t P, int32_t G) {
+    if (P < 1 || P > GI_MAXP || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
+    return gi_plan(nb, P, -1).total;
+}
+
+int64_t vx_grid_info_workspace_min_floats(int32_t P, int32_t G) {
+    if (P < 1 || P > GI_MAXP || G < 1 || G > GP_MAXG) return VX_EINVAL;
+    return gi_min_floats(P);
+}
+
+int vx_grid_info(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, int32_t K, const void* img, const void* wimg,
+                 const float* logw, const float* loglik, float* info, float* gradient, float* workspace, int64_t ws_floats, void* hs) {
+    if (!y || !img || !aligned16(img) || !wimg || !aligned16(wimg) || !logw || !loglik || !info || !gradient || !workspace ||
+        !aligned16(workspace))
+        return VX_EINVAL;
+    if (!grid_info_shape_ok(J, G, K, nb)) return VX_EINVAL;
+    const int P = (int)J * (int)K;
+    if (ws_floats < gi_min_floats(P) || ws_floats > ((int64_t)1 << 48)) return VX_EINVAL;
+    const GiPlan p = gi_plan(nb, P, ws_floats);
+    hipStream_t st = (hipStream_t)hs;
+    const float* trailer = (const float*)((const uint8_t*)wimg + gi_wimage_frag_bytes(P, G));
+    const size_t lds = gi_lds_bytes(G);
+    int rc = set_lds(k_grid_pscores, lds);
+    if (rc) return rc;
+    uint4* S = (uint4*)workspace;
+    float* part = workspace + p.off_part;
+    float* red = workspace + p.off_red;
+    float* acc = workspace + p.off_acc;
+    const int64_t tiles_len = p.n_pairs * GI_TILE;
+    for (int64_t i0 = 0; i0 < nb; i0 += p.slab_persons) {
+        const int64_t ns = nb - i0 < p.slab_persons ? nb - i0 : p.slab_persons;
+        const int64_t units64 = (ns + 32 * GP_MT - 1) / (32 * GP_MT);
+        const int64_t cap = (int64_t)num_cu() * 2;
+        hipLaunchKernelGGL(k_grid_pscores, dim3((unsigned)(units64 < cap ? units64 : cap)), dim3(GP_THREADS), lds, st,
+                           rows ? y : y + i0 * J, rows ? rows + i0 : rows, ns, (int)J, (int)G, (int)K, P, (const uint4*)img,
+                           (const uint4*)wimg, trailer, logw, loglik + i0, S, gi_nsub(G));
+        VX_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_grid_xprod, dim3((unsigned)(p.n_bp * p.n_chunks)), dim3(256), 0, st, (const uint4*)S, p.PT, p.nbb,
+                           units64 * GP_MT, p.units_per_chunk, part, tiles_len);
+        VX_CHECK_LAUNCH();
+        rc = vx_reduce_slabs(part, p.n_chunks, tiles_len, 1.0f, red, hs);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_info_add, dim3(grid_1d(tiles_len, 256)), dim3(256), 0, st, acc, (const float*)red, tiles_len,
+                           i0 == 0 ? 1 : 0);
+        VX_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_info_finish, dim3(grid_1d((int64_t)P * (P + 1), 256)), dim3(256), 0, st, (const float*)acc, P, p.PT, trailer,
+                       info, gradient);
     VX_CHECK_LAUNCH();
     return VX_OK;
 }

@@ -271,6 +271,31 @@ class HipBackend(object):
                                  int(draw0), int(ndraws), int(stride), _hip.ptr(node), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_draw")
 
+    def grid_wimage_bytes(self, P, G):
+        return self._size("vx_grid_wimage_bytes", P, G)
+
+    def grid_wtable_irt(self, cfg, theta, G, a, b, wimg):
+        rc = self.L.vx_grid_wtable_irt(ctypes.byref(cfg), _hip.ptr(theta), G, _hip.ptr(a), _hip.ptr(b), _hip.ptr(wimg),
+                                       _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_wtable_irt")
+
+    def grid_wtable_cdm(self, cfg, dino, q, g, s_, wimg):
+        rc = self.L.vx_grid_wtable_cdm(ctypes.byref(cfg), int(dino), _hip.ptr(q), _hip.ptr(g), _hip.ptr(s_), _hip.ptr(wimg),
+                                       _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_wtable_cdm")
+
+    def grid_info_workspace(self, nb, P, G):
+        return self._size("vx_grid_info_workspace_floats", nb, P, G)
+
+    def grid_info_workspace_min(self, P, G):
+        return self._size("vx_grid_info_workspace_min_floats", P, G)
+
+    def grid_info(self, y, rows, nb, J, G, K, img, wimg, logw, loglik, info, gradient, ws, ws_floats):
+        rc = self.L.vx_grid_info(_hip.ptr(y), _hip.ptr(rows), nb, J, G, K, _hip.ptr(img), _hip.ptr(wimg), _hip.ptr(logw),
+                                 _hip.ptr(loglik), _hip.ptr(info), _hip.ptr(gradient), _hip.ptr(ws), int(ws_floats),
+                                 _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_info")
+
     def cdm_sf_workspace(self, cfg, nb):
         return self._size("vx_cdm_sf_workspace_floats", ctypes.byref(cfg), nb)
 
@@ -600,7 +625,7 @@ class _EngineBase(object):
                                   "persons of the batch, or it has no enumerated likelihood (IrtEngine with x_feature <= 3 and "
                                   "CcdmEngine have them)" % type(self).__name__)
 
-    score = expected_counts = plausible_values = item_fit = marginal_loglik = fit_em = _no_grid
+    score = expected_counts = plausible_values = item_fit = marginal_loglik = fit_em = item_information = item_se = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1601,6 +1626,31 @@ class IrtEngine(GridMixin, _EngineBase):
         return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_irt(call.cfg, call.theta, call.G, n1, n0, free, a, b, newton),
                              {"a": a, "b": b} if two else {"b": b}, max_iter, tol, progress)
 
+    def _info_call(self, y_u8, rows, nodes=61, span=6.0):
+        """What GridMixin.item_information needs of this class: the GridCall, K (columns an item: b, then a_0 .. a_{D-1}; 1PL: b),
+        the filler of the derivative tables and the free mask over the dense layout."""
+        if self.model not in ("irt_1pl", "irt_2pl"):
+            raise NotImplementedError("item_information / item_se for %s: the derivative tables are those of the logistic link of "
+                                      "fit_em's M-step, which a guessing or slipping asymptote does not have; only irt_1pl and "
+                                      "irt_2pl have them" % self.model)
+        call = self._grid_call(y_u8, rows, nodes, span)
+        two = self.model != "irt_1pl"
+        a = self.unconstrained("a").contiguous() if two else None
+        b = self.unconstrained("b").reshape(-1).contiguous()
+        free = torch.ones(self.J_items, self.D_model + 1 if two else 1, dtype=torch.bool, device=self.dev)
+        if two:
+            free[:, 1:] = (self.unconstrained("a", self.free) != 0).t()
+        return call, (self.D_model + 1 if two else 1), lambda wimg: self.be.grid_wtable_irt(call.cfg, call.theta, call.G, a, b, wimg), \
+            free.reshape(-1)
+
+    def _se_leaves(self, se):
+        """Dense [P] -> the leaves' shapes: b (1, J) and, for 2PL, a (D, J)."""
+        se = se.reshape(self.J_items, -1)
+        out = {"b": se[:, 0].reshape(1, -1).copy()}
+        if self.model != "irt_1pl":
+            out["a"] = se[:, 1:].T.copy()
+        return out
+
     # -- one ELBO-gradient step ------------------------------------------------------------------
     def loss_and_grads(self, rows=None, b_global=None, eps=None, stream_id=0, baseline_buf=None, guide_grads=True):
         """Fills self.G (flat grads + loss slot) and per-person grads for ONE particle.
@@ -2011,6 +2061,22 @@ class CcdmEngine(GridMixin, _EngineBase):
         call = self._grid_call(None, None, params=(g, s_))
         return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_cdm(call.cfg, dino, self.q, n1, n0, g, s_), {"g": g, "s": s_},
                              max_iter, tol, progress)
+
+    def _info_call(self, y_u8, rows):
+        """What GridMixin.item_information needs of this class: two columns an item, g_un and s_un, both free."""
+        call = self._grid_call(y_u8, rows)
+        g, s_ = self.view("g"), self.view("s")
+        return call, 2, lambda wimg: self.be.grid_wtable_cdm(call.cfg, self.cdm == "dino", self.q, g, s_, wimg), \
+            torch.ones(2 * self.J, dtype=torch.bool, device=self.dev)
+
+    def _se_leaves(self, se):
+        """Dense [P] -> g_un, s_un (1, J) and, by the delta method, g and s on the probability scale: se x (1 - x)."""
+        se = se.reshape(self.J, 2)
+        out = {"g_un": se[:, 0].reshape(1, -1).copy(), "s_un": se[:, 1].reshape(1, -1).copy()}
+        for k in ("g", "s"):
+            x = self.param(k).detach().cpu().numpy().astype(np.float64).reshape(1, -1)
+            out[k] = out[k + "_un"] * x * (1.0 - x)
+        return out
 
     def _replayable(self, full):
         # VCCDM (vi.py:819-865; test.py:560,585,624: 100-1500 rows a step): no guide, no random numbers -- the pattern

@@ -1,5 +1,5 @@
 """The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide -- score(), expected_counts() /
-item_fit(), fit_em(), plausible_values() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
+item_fit(), fit_em(), plausible_values(), item_information() / item_se() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
 entries of the C ABI (k_grid_*.hip; no reference counterpart).  All of it works in buffers of its own: nothing a step reads is
 touched."""
 from collections import namedtuple
@@ -11,6 +11,7 @@ SCORE_MAX_NODES = 1024           # GP_MAXG (vipsy_amd/csrc/k_grid_post.hip)
 SCORE_MAX_DIMS = 3               # IRT: the tensor-product grid stops being a method beyond three dimensions
 EM_MAX_NEWTON = 64               # GM_MAX_NEWTON (vipsy_amd/csrc/k_grid_mstep.hip)
 PV_MAX_DRAWS = 1024              # PV_MAXDRAWS (vipsy_amd/csrc/k_grid_draw.hip)
+INFO_MAX_PARAMS = 4096           # GI_MAXP (vipsy_amd/csrc/k_grid_info.hip): columns of the information matrix
 PV_STREAM = 0xC7                 # PV_STREAM (vipsy_amd/csrc/vx_common.h): the Philox stream tag of the plausible-value draws
 
 
@@ -78,6 +79,47 @@ def item_fit_stats(n1, n0, prob):
     rmsd = torch.sqrt((resid * resid / safe).sum(1) / n_obs)
     observed = torch.where(pos, n1 / safe, torch.full_like(n, float("nan")))
     return {"n_obs": n_obs, "md": md, "rmsd": rmsd, "observed": observed}
+
+
+def item_se_host(info, gradient, free, names=None):
+    """The host layer of item_se(): standard errors from an information matrix, in float64 numpy.  info [P][P], gradient [P],
+    free bool [P].  Kept are the free columns whose diagonal is not exactly 0 (a column of exact zeros belongs to an item nobody
+    answered or to a class no pattern reaches); the kept block is inverted through its Cholesky factor -- no pseudo-inverse: a
+    block that is not positive definite raises ValueError naming the parameter of the smallest pivot (names: a function of the
+    dense column, by default the column number).  Returns `se` [P] (NaN where fixed or dropped), `cov` [kept][kept], `kept`,
+    `gradient_max` = max |gradient| over the kept columns and `condition`, the 2-norm condition number of the kept block."""
+    info = np.asarray(info, np.float64)
+    gradient = np.asarray(gradient, np.float64).reshape(-1)
+    free = np.asarray(free, bool).reshape(-1)
+    P = info.shape[0]
+    if info.shape != (P, P) or gradient.shape != (P,) or free.shape != (P,):
+        raise ValueError("info must be [P][P], gradient and free [P]")
+    kept = np.flatnonzero(free & (np.diag(info) != 0))
+    A = info[np.ix_(kept, kept)]
+    A = 0.5 * (A + A.T)
+    se = np.full(P, np.nan)
+    if kept.size == 0:
+        return {"se": se, "cov": np.zeros((0, 0)), "kept": kept, "gradient_max": 0.0, "condition": float("nan")}
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        W, piv = A.copy(), np.full(kept.size, np.inf)
+        for i in range(kept.size):                                              # the pivots up to the first that is not positive
+            piv[i] = W[i, i]
+            if not piv[i] > 0:
+                break
+            W[i + 1:, i + 1:] -= np.outer(W[i + 1:, i], W[i, i + 1:]) / piv[i]
+        worst = int(np.argmin(piv))
+        col = int(kept[worst])
+        raise ValueError("the information matrix of the %d estimated parameters is not positive definite: pivot %.3e at %s -- "
+                         "too few persons for the parameters, or parameters the data cannot tell apart; no standard errors"
+                         % (kept.size, piv[worst], names(col) if names else "column %d" % col))
+    Li = np.linalg.solve(L, np.eye(kept.size))
+    cov = Li.T @ Li
+    se[kept] = np.sqrt(np.diag(cov))
+    w = np.linalg.eigvalsh(A)
+    return {"se": se, "cov": cov, "kept": kept, "gradient_max": float(np.abs(gradient[kept]).max()),
+            "condition": float(w[-1] / w[0])}
 
 
 class GridCall(namedtuple("GridCall", "y rows J theta logw fill_tables cfg")):
@@ -218,6 +260,50 @@ class GridMixin(object):
         if bar is not None:
             bar.close()
         return {"loglik": hist, "iterations": len(hist), "converged": converged}
+
+    def item_information(self, y_u8=None, rows=None, **kw):
+        """The cross-product (BHHH, empirical) information of the item parameters over the scored rows, AT THE PARAMETERS
+        AS THEY STAND: with s_i the marginal score of person i (Fisher's identity over the grid posterior of score()), `info` =
+        sum_i s_i s_i^T, float32 [P][P] on the device, symmetric bit for bit, and `gradient` = sum_i s_i [P], the gradient of
+        marginal_loglik() -- what fit_em's M-step forms from the expected counts.  Dense layout: column c = j K + k; IrtEngine:
+        K = x_feature + 1 (k = 0: b, k = 1 + d: a_d; 1PL: K = 1), CcdmEngine: K = 2 (g_un, s_un); P = J K <= 4096.  Also `n`
+        (the persons), `free` bool [P] (the engine's free mask over a; b, g and s are always free) and `index`, the numpy arrays
+        `item` and `k` [P].  Its inverse is a covariance only at the marginal maximum, i.e. after fit_em() has converged;
+        `gradient` says how far from it the parameters are.  Inputs, grid and limits as score(); 1PL / 2PL only; one rank only.
+        Works in buffers of its own.  Deterministic: the same call gives the same bits."""
+        self._one_rank_only("item_information / item_se over a process group: the matrix is the sum over the local shard's "
+                            "persons and the cross-rank sum is not built")
+        call, K, fill_wtable, free = self._info_call(y_u8, rows, **kw)
+        be, J, G, n = self.be, call.J, call.G, call.n
+        P = J * K
+        if P > INFO_MAX_PARAMS:
+            raise NotImplementedError("item_information takes at most %d item parameters (this model has %d x %d)"
+                                      % (INFO_MAX_PARAMS, J, K))
+        post = self._grid_posterior(call)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        wimg = torch.empty(be.grid_wimage_bytes(P, G), dtype=torch.uint8, device=self.dev)
+        fill_wtable(wimg)
+        info, gradient = torch.empty(P, P, **f32), torch.empty(P, **f32)
+        ws_floats = be.grid_info_workspace(n, P, G)
+        ws = torch.empty(ws_floats, **f32)
+        be.grid_info(call.y, call.rows, n, J, G, K, post["img"], wimg, call.logw, post["loglik"], info, gradient, ws, ws_floats)
+        return {"info": info, "gradient": gradient, "n": n, "free": free,
+                "index": {"item": np.repeat(np.arange(J), K), "k": np.tile(np.arange(K), J)}}
+
+    def item_se(self, y_u8=None, rows=None, **kw):
+        """Standard errors of the item parameters from item_information(), as float64 numpy arrays shaped like the leaves
+        (IrtEngine: `b` and, for 2PL, `a`; CcdmEngine: `g_un`, `s_un` and, by the delta method, `g`, `s` on the probability
+        scale), NaN for a parameter that is fixed (a_free = 0) or was dropped because its column of the matrix is exactly zero
+        (an item nobody answered; the s of a DINO single-attribute item).  Also `cov` (float64, kept x kept), `kept` (the dense
+        columns of its rows), `gradient_max` and `condition` (item_se_host).  The matrix is the cross-product information AT THE
+        PARAMETERS AS THEY STAND: these are standard errors only at the marginal maximum, after fit_em() has converged --
+        `gradient_max` shows how far from it the parameters are.  A kept block that is not positive definite raises ValueError."""
+        inf = self.item_information(y_u8, rows, **kw)
+        item, k = inf["index"]["item"], inf["index"]["k"]
+        out = item_se_host(inf["info"].cpu().numpy(), inf["gradient"].cpu().numpy(), inf["free"].cpu().numpy(),
+                           names=lambda c: "item %d, parameter %d of its %d" % (item[c], k[c], int(k.max()) + 1))
+        out.update(self._se_leaves(out.pop("se")))
+        return out
 
     def item_fit(self, y_u8=None, rows=None, **kw):
         """Per-item fit statistics of the scored rows (item_fit_stats over expected_counts): `n_obs`, `md`, `rmsd` [J] and

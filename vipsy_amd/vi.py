@@ -256,6 +256,27 @@ class BasePsy(object):
                                       "cross-rank sum is not built" % self.world)
         return self.engine.fit_em(max_iter=max_iter, tol=tol, newton=newton, progress=progress, **grid_kw)
 
+    def item_information(self, data=None, **grid_kw):
+        """The cross-product (BHHH) information matrix of the item parameters over the persons in `data` (None: the training
+        data) AT THE PARAMETERS AS THEY STAND, and the gradient of the marginal log-likelihood: device tensors `info` [P][P] and
+        `gradient` [P] over the dense layout, with `n`, `free` and `index` (IrtEngine / CcdmEngine.item_information).  The
+        inverse of the matrix is a covariance only at the marginal maximum, that is after fit_em() has converged.  VIRT / VaeIRT
+        with irt_1pl / irt_2pl and x_feature <= 3, VCCDM; the other classes and models refuse.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("item_information with a group of %d ranks: the matrix is the sum over the local shard's "
+                                      "persons; the cross-rank sum is not built" % self.world)
+        return self.engine.item_information(self._score_data(data), **grid_kw)
+
+    def item_se(self, data=None, **grid_kw):
+        """Standard errors of the item parameters, ready to print: numpy arrays shaped like the leaves (`a`, `b`; VCCDM: `g_un`,
+        `s_un` and `g`, `s` on the probability scale), NaN where a parameter is fixed or has no information, with `cov`, `kept`,
+        `gradient_max` and `condition` (GridMixin.item_se).  They come from the inverse of the cross-product information AT THE
+        PARAMETERS AS THEY STAND: standard errors only at the marginal maximum, that is after fit_em() has converged;
+        `gradient_max` shows how far from it the parameters are.  Models and refusals as item_information().  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("item_se with a group of %d ranks: the information matrix is the sum over the local "
+                                      "shard's persons; the cross-rank sum is not built" % self.world)
+        return self.engine.item_se(self._score_data(data), **grid_kw)
 
 class BaseIRT(BasePsy):
     """vi.py:536-656 (constructor kwargs identical: model, x_feature, share_cov, D, a_free, a0, b0)."""
