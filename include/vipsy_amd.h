@@ -527,6 +527,35 @@ int vx_grid_info(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] o
                  const void* img, const void* wimg, const float* logw /*[G]*/, const float* loglik /*[nb]*/, float* info /*[P][P]*/,
                  float* gradient /*[P]*/, float* workspace, int64_t ws_floats, void* hip_stream);
 
+/* ---- Local dependence: the pairwise-complete residual sums behind Yen's Q3.  With m_ij = [y_ij < 2] (254 / 255 cells are not
+ * observed), r_ij = m_ij (y_ij - P_ij) and I_jk the persons with m_ij m_ik = 1, four float32 tables [J][J] on the device:
+ *     n[j][k] = |I_jk|     s[j][k] = sum_{I_jk} r_ij     ss[j][k] = sum_{I_jk} r_ij^2     sp[j][k] = sum_{I_jk} r_ij r_ik
+ * n and sp are symmetric bit for bit (computed for the upper triangle and mirrored); s and ss belong to the ROW item and are not.
+ * From them cov = sp - s s^T / n, v = ss - s^2 / n, q3 = cov / sqrt(v v^T) (float64 on the host: vipsy_amd.grid.pair_q3_host).
+ *   vx_grid_pairs_irt (cfg: model 1..4, D <= 3, J, Dc): P_ij = c_j + (d_j - c_j) sigmoid(Dc (theta_hat_i . a_j + b_j)), z formed as
+ *     vx_grid_table_irt forms it (b first, then the dimensions; 1PL: a = 1), c = sigmoid(c_un), d = sigmoid(d_un), 0 and 1 where
+ *     the model has neither (the pointer may then be NULL).  theta_hat [nb][D] goes by batch position: the `mean` of
+ *     vx_grid_posterior for the same y, rows and nb.
+ *   vx_grid_pairs_cdm (cfg: K <= 10, J; dino, q as vx_grid_table_cdm): P_ij = eta_j(pattern_i) ? 1 - s_j : g_j, pattern [nb] by
+ *     batch position: the `argmax` of vx_grid_posterior.
+ * Products over persons on v_mfma_f32_32x32x16_f16: r and r^2 as fp16 pairs of the value times 2^10, m exact, fp32 accumulation.
+ * The operand fragments of a slab of persons (a multiple of 256, as many as ws_floats allow) live in `workspace`; the slab's
+ * chunks are added in ascending order and the slabs in person order, no atomics: the same call with the same ws_floats gives
+ * the same bits.  Nothing of size persons x items is held outside `workspace`.  vx_grid_pairs_workspace_floats(nb, J): the
+ * preferred size (one slab where 512 MB allow it); vx_grid_pairs_workspace_min_floats(J): the smallest accepted (one slab of 256
+ * persons, one chunk).  workspace is 16-byte aligned.  n is exact while a call scores at most 2^24 persons (fp32 counts).
+ * Limits: model 1..4, 1 <= D <= 3, K <= 10, 1 <= J <= 1024, nb >= 1, ws_floats at least the minimum; VX_EINVAL beyond. */
+int64_t vx_grid_pairs_workspace_floats(int64_t nb, int32_t J);
+int64_t vx_grid_pairs_workspace_min_floats(int32_t J);
+int vx_grid_pairs_irt(const vx_irt_cfg* cfg, const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb,
+                      const float* theta_hat /*[nb][D]*/, const float* a /*[D][J] or NULL (1PL)*/, const float* b /*[J]*/,
+                      const float* c_un /*[J] or NULL*/, const float* d_un /*[J] or NULL*/, float* n /*[J][J]*/, float* s /*[J][J]*/,
+                      float* ss /*[J][J]*/, float* sp /*[J][J]*/, float* workspace, int64_t ws_floats, void* hip_stream);
+int vx_grid_pairs_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const uint8_t* y /*[n_local][J]*/,
+                      const int64_t* rows /*[nb] or NULL*/, int64_t nb, const int32_t* pattern /*[nb]*/, const float* g_un,
+                      const float* s_un, float* n /*[J][J]*/, float* s /*[J][J]*/, float* ss /*[J][J]*/, float* sp /*[J][J]*/,
+                      float* workspace, int64_t ws_floats, void* hip_stream);
+
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,
                     void* hip_stream);

@@ -35,6 +35,7 @@
 #include "k_grid_draw.hip"
 #include "k_grid_mstep.hip"
 #include "k_grid_info.hip"
+#include "k_grid_pairs.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2399,6 +2400,87 @@ int vx_grid_info(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, i
                        info, gradient);
     VX_CHECK_LAUNCH();
     return VX_OK;
+}
+
+// Local dependence (k_grid_pairs.hip): the residual cell as operand fragments, the masked cross products over persons, the sums
+static bool grid_pairs_shape_ok(int64_t J, int64_t nb) { return J >= 1 && J <= GP_MAXJ && nb >= 1 && nb <= ((int64_t)1 << 48); }
+
+int64_t vx_grid_pairs_workspace_floats(int64_t nb, int32_t J) {
+    if (!grid_pairs_shape_ok(J, nb)) return VX_EINVAL;
+    return pp_plan(nb, J, -1).total;
+}
+
+int64_t vx_grid_pairs_workspace_min_floats(int32_t J) {
+    if (!grid_pairs_shape_ok(J, 1)) return VX_EINVAL;
+    return pp_min_floats(J);
+}
+
+// the slab loop both entries share: frag(i0, ns, n_units) launches the cell kernel of a slab
+extern "C++" template <typename Frag>
+static int grid_pairs_run(int64_t nb, int J, float* n, float* s, float* ss, float* sp, float* workspace, int64_t ws_floats,
+                          void* hs, Frag frag) {
+    const PpPlan p = pp_plan(nb, J, ws_floats);
+    hipStream_t st = (hipStream_t)hs;
+    float* part = workspace + p.off_part;
+    float* red = workspace + p.off_red;
+    float* acc = workspace + p.off_acc;
+    for (int64_t i0 = 0; i0 < nb; i0 += p.slab_persons) {
+        const int64_t ns = nb - i0 < p.slab_persons ? nb - i0 : p.slab_persons;
+        const int64_t n_units = (ns + 31) / 32;
+        const int64_t cap = (int64_t)num_cu() * 8;
+        frag(i0, ns, n_units, dim3((unsigned)(n_units < cap ? n_units : cap)));
+        VX_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_pair_xprod, dim3((unsigned)(p.n_bp * p.n_chunks)), dim3(64 * PP_XWAVES), 0, st, (const uint4*)workspace, p.JT,
+                           p.nbb, n_units, p.units_per_chunk, part, p.tiles_len);
+        VX_CHECK_LAUNCH();
+        int rc = vx_reduce_slabs(part, p.n_chunks, p.tiles_len, 1.0f, red, hs);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_info_add, dim3(grid_1d(p.tiles_len, 256)), dim3(256), 0, st, acc, (const float*)red, p.tiles_len,
+                           i0 == 0 ? 1 : 0);
+        VX_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_pair_finish, dim3(grid_1d((int64_t)J * J, 256)), dim3(256), 0, st, (const float*)acc, J, p.JT, n, s, ss, sp);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_pairs_irt(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* theta_hat, const float* a,
+                      const float* b, const float* c_un, const float* d_un, float* n, float* s, float* ss, float* sp, float* workspace,
+                      int64_t ws_floats, void* hs) {
+    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > PP_MAXD || !grid_pairs_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (!y || !theta_hat || !b || !n || !s || !ss || !sp || !workspace || !aligned16(workspace)) return VX_EINVAL;
+    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
+        return VX_EINVAL;
+    if (ws_floats < pp_min_floats((int)cfg->J) || ws_floats > ((int64_t)1 << 48)) return VX_EINVAL;
+    hipStream_t st = (hipStream_t)hs;
+    const int D = (int)cfg->D, J = (int)cfg->J, model = (int)cfg->model;
+    const float Dc = cfg->Dc;
+    auto frag = [=](int64_t i0, int64_t ns, int64_t n_units, dim3 grid) {
+        const uint8_t* ys = rows ? y : y + i0 * J;
+        const int64_t* rs = rows ? rows + i0 : rows;
+        const float* th = theta_hat + i0 * D;
+#define LAUNCH_PF(M)                                                                                                  \
+        hipLaunchKernelGGL((k_pair_frag<M>), grid, dim3(256), 0, st, ys, rs, ns, D, J, Dc, th, a, b, c_un, d_un, (uint4*)workspace, n_units)
+        if (model == 1) { LAUNCH_PF(1); } else if (model == 2) { LAUNCH_PF(2); } else if (model == 3) { LAUNCH_PF(3); }
+        else { LAUNCH_PF(4); }
+#undef LAUNCH_PF
+    };
+    return grid_pairs_run(nb, J, n, s, ss, sp, workspace, ws_floats, hs, frag);
+}
+
+int vx_grid_pairs_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const uint8_t* y, const int64_t* rows, int64_t nb,
+                      const int32_t* pattern, const float* g_un, const float* s_un, float* n, float* s, float* ss, float* sp,
+                      float* workspace, int64_t ws_floats, void* hs) {
+    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || !grid_pairs_shape_ok(cfg->J, nb) || (dino != 0 && dino != 1)) return VX_EINVAL;
+    if (!q || !y || !pattern || !g_un || !s_un || !n || !s || !ss || !sp || !workspace || !aligned16(workspace)) return VX_EINVAL;
+    if (ws_floats < pp_min_floats((int)cfg->J) || ws_floats > ((int64_t)1 << 48)) return VX_EINVAL;
+    hipStream_t st = (hipStream_t)hs;
+    const int K = (int)cfg->K, J = (int)cfg->J;
+    auto frag = [=](int64_t i0, int64_t ns, int64_t n_units, dim3 grid) {
+        hipLaunchKernelGGL(k_pair_frag_cdm, grid, dim3(256), 0, st, rows ? y : y + i0 * J, rows ? rows + i0 : rows, ns, K, J, (int)dino, q,
+                           pattern + i0, g_un, s_un, (uint4*)workspace, n_units);
+    };
+    return grid_pairs_run(nb, J, n, s, ss, sp, workspace, ws_floats, hs, frag);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide -- score(), expected_counts() /
-item_fit(), fit_em(), plausible_values(), item_information() / item_se() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
+item_fit(), fit_em(), plausible_values(), item_information() / item_se(), residual_sums() / local_dependence() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
 entries of the C ABI (k_grid_*.hip; no reference counterpart).  All of it works in buffers of its own: nothing a step reads is
 touched."""
 from collections import namedtuple
@@ -120,6 +120,45 @@ def item_se_host(info, gradient, free, names=None):
     w = np.linalg.eigvalsh(A)
     return {"se": se, "cov": cov, "kept": kept, "gradient_max": float(np.abs(gradient[kept]).max()),
             "condition": float(w[-1] / w[0])}
+
+
+def pair_q3_host(n, s, ss, sp, min_pairs=8):
+    """The host layer of local_dependence(): Yen's Q3 from the four pairwise-complete tables [J][J] (n[j][k] the persons who answered
+    both, s / ss the sums of the ROW item's residuals and their squares over them, sp the sum of the products), in float64 numpy:
+    cov = sp - s s^T / n, v = ss - s^2 / n, q3 = cov / sqrt(v v^T) -- the correlation of the two items' residuals over the persons
+    who answered both.  NaN where n < min_pairs or where either v <= 0 (an item nobody answered, or residuals without spread);
+    the diagonal is exactly 1 where defined."""
+    n, s, ss, sp = (np.asarray(t, np.float64) for t in (n, s, ss, sp))
+    J = n.shape[0]
+    if n.ndim != 2 or any(t.shape != (J, J) for t in (n, s, ss, sp)):
+        raise ValueError("n, s, ss and sp must be [J][J]")
+    safe = np.where(n > 0, n, 1.0)
+    cov = sp - s * s.T / safe
+    v = ss - s * s / safe
+    ok = (n >= min_pairs) & (v > 0) & (v.T > 0)
+    q3 = np.full((J, J), np.nan)
+    q3[ok] = cov[ok] / np.sqrt((v * v.T)[ok])
+    d = np.arange(J)
+    q3[d, d] = np.where(ok[d, d], 1.0, np.nan)
+    return q3
+
+
+def pair_q3_summary(q3, top=20):
+    """`mean` of the finite off-diagonal entries of q3, `max` of the off-diagonal q3 - mean, and the `top` pairs j < k by
+    descending |q3 - mean| (ties: the lower pair first) as `item_j`, `item_k` (int64) and `value` = their q3.  No finite pair:
+    mean and max NaN, no pairs."""
+    J = q3.shape[0]
+    jj, kk = np.triu_indices(J, 1)
+    val = q3[jj, kk]
+    fin = np.isfinite(val)
+    jj, kk, val = jj[fin], kk[fin], val[fin]
+    if val.size == 0:
+        e = np.zeros(0, np.int64)
+        return {"mean": float("nan"), "max": float("nan"), "item_j": e, "item_k": e.copy(), "value": np.zeros(0)}
+    mean = float(val.mean())
+    order = np.argsort(-np.abs(val - mean), kind="stable")[:top]
+    return {"mean": mean, "max": float((val - mean).max()), "item_j": jj[order].astype(np.int64),
+            "item_k": kk[order].astype(np.int64), "value": val[order]}
 
 
 class GridCall(namedtuple("GridCall", "y rows J theta logw fill_tables cfg")):
@@ -303,6 +342,44 @@ class GridMixin(object):
         out = item_se_host(inf["info"].cpu().numpy(), inf["gradient"].cpu().numpy(), inf["free"].cpu().numpy(),
                            names=lambda c: "item %d, parameter %d of its %d" % (item[c], k[c], int(k.max()) + 1))
         out.update(self._se_leaves(out.pop("se")))
+        return out
+
+    def residual_sums(self, y_u8=None, rows=None, **grid_kw):
+        """The pairwise-complete residual sums of the scored rows (vx_grid_pairs_*): with r_ij = y_ij - P_ij the residual of an
+        observed cell AT THE PERSON'S POINT ESTIMATE -- the grid EAP of score() for IrtEngine (all four models), the MAP pattern
+        for CcdmEngine -- under the item parameters as they stand, and I_jk the persons who answered both j and k: float32
+        device tensors [J][J] `n` = |I_jk|, `s` = sum of r_ij, `ss` = sum of r_ij^2 (the ROW item's, over I_jk: not symmetric) and
+        `sp` = sum of r_ij r_ik (symmetric bit for bit, as is n), beside `theta_hat` (n, D) or `pattern` (n,), the estimates the
+        residuals were taken at.  Inputs, grid and refusals as score(); one rank only.  Works in buffers of its own.
+        Deterministic: the same call gives the same bits.  n is exact up to 2**24 scored persons."""
+        self._one_rank_only("residual_sums / local_dependence over a process group: the tables are the sums over the local shard's "
+                            "persons and the cross-rank sum is not built")
+        call, name, key, run = self._pairs_call(y_u8, rows, **grid_kw)
+        post = self._grid_posterior(call)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = {k: torch.empty(call.J, call.J, **f32) for k in ("n", "s", "ss", "sp")}
+        ws_floats = self.be.grid_pairs_workspace(call.n, call.J)
+        ws = torch.empty(ws_floats, **f32)
+        run(post[key], out, ws, ws_floats)
+        out[name] = post[key]
+        return out
+
+    def local_dependence(self, y_u8=None, rows=None, min_pairs=8, top=20, **grid_kw):
+        """Yen's Q3 of every item pair (pair_q3_host over residual_sums): the correlation, over the persons who answered both
+        items, of the residuals y - P taken at the EAP (IrtEngine) or the MAP pattern (CcdmEngine) under the item parameters as
+        they stand.  Pairs are pairwise-complete: a 255 cell takes its person out of the pairs of that item only.  Returns numpy:
+        `q3` float64 [J][J] (NaN where fewer than min_pairs persons answered both items or where an item's residuals have no
+        spread over them; the diagonal is 1 where defined), `n_pairs` int64 [J][J], `mean` = the mean of the finite off-diagonal
+        entries (about -1 / (J - 1) under local independence, which is why it is reported), `max` = the largest off-diagonal
+        q3 - mean, and `item_j`, `item_k`, `value`: the `top` pairs j < k by descending |q3 - mean| with their q3.
+        min_pairs: an integer >= 2; below the default 8 the statistic's own cancellation magnifies float32 rounding."""
+        min_pairs = self._int_in("min_pairs", min_pairs, 2)
+        top = self._int_in("top", top, 0)
+        t = self.residual_sums(y_u8, rows, **grid_kw)
+        n = t["n"].cpu().numpy()
+        q3 = pair_q3_host(n, t["s"].cpu().numpy(), t["ss"].cpu().numpy(), t["sp"].cpu().numpy(), min_pairs)
+        out = pair_q3_summary(q3, top)
+        out["q3"], out["n_pairs"] = q3, np.rint(n).astype(np.int64)
         return out
 
     def item_fit(self, y_u8=None, rows=None, **kw):

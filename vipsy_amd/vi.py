@@ -278,6 +278,33 @@ class BasePsy(object):
                                       "shard's persons; the cross-rank sum is not built" % self.world)
         return self.engine.item_se(self._score_data(data), **grid_kw)
 
+    def residual_sums(self, data=None, **kw):
+        """The pairwise-complete residual sums behind local_dependence(), as device tensors [items][items]: `n` (the persons who
+        answered both items of a pair), `s`, `ss` (the sums of the row item's residuals and of their squares over those persons)
+        and `sp` (the sum of the products of the two items' residuals), beside `theta_hat` or `pattern`.  The residuals y - P are
+        taken at each person's point estimate -- the EAP of score() for VIRT / VaeIRT (every model, x_feature <= 3), the MAP
+        pattern for VCCDM -- under the item parameters as they stand; pairs are pairwise-complete: a missing cell takes its person
+        out of that item's pairs only.  `data`: None = the training data.  The other classes refuse.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("residual_sums with a group of %d ranks: the tables are the sums over the local shard's "
+                                      "persons; the cross-rank sum is not built" % self.world)
+        return self.engine.residual_sums(self._score_data(data), **kw)
+
+    def local_dependence(self, data=None, **kw):
+        """Yen's Q3 for every item pair, ready to print: the correlation, over the persons who answered both items, of the
+        residuals y - P taken at each person's point estimate -- the EAP of score() for VIRT / VaeIRT (every model, x_feature
+        <= 3), the MAP pattern for VCCDM -- under the item parameters as they stand; nothing is refitted.  Pairs are
+        pairwise-complete: a missing cell takes its person out of that item's pairs only.  A dict of numpy values: `q3`
+        [items][items], `n_pairs`, `mean` (about -1 / (items - 1) under local independence), `max` (the largest q3 - mean off
+        the diagonal) and `item_j`, `item_k`, `value`, the `top` (20) pairs by |q3 - mean| (GridMixin.local_dependence).  NaN in
+        `q3` means no statistic: fewer than `min_pairs` (8) persons answered both items, or one item's residuals have no spread
+        over them (an item nobody answered among them).  `data`: None = the training data.  The other classes refuse.  One
+        rank only."""
+        if self.world > 1:
+            raise NotImplementedError("local_dependence with a group of %d ranks: the tables are the sums over the local shard's "
+                                      "persons; the cross-rank sum is not built" % self.world)
+        return self.engine.local_dependence(self._score_data(data), **kw)
+
 class BaseIRT(BasePsy):
     """vi.py:536-656 (constructor kwargs identical: model, x_feature, share_cov, D, a_free, a0, b0)."""
 
