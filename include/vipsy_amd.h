@@ -556,6 +556,30 @@ int vx_grid_pairs_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[
                       const float* s_un, float* n /*[J][J]*/, float* s /*[J][J]*/, float* ss /*[J][J]*/, float* sp /*[J][J]*/,
                       float* workspace, int64_t ws_floats, void* hip_stream);
 
+/* ---- Person fit: the sums behind lz (Drasgow-Levine-Williams) and the infit / outfit mean squares, per person and per item, in
+ * one pass over persons x items.  Observed cells only (y < 2).  P_ij is the probability vx_grid_pairs_* takes the residual from
+ * (same cfg, parameters, theta_hat / pattern and limits), Q = 1 - P formed on its own, never by subtraction, and per cell
+ *     lambda = log(P / Q)   l = y ? log P : log Q   eps = P log P + Q log Q   nu = P Q lambda^2
+ *     r2 = y ? Q^2 : P^2    w = P Q                 zeta = y ? Q / P : P / Q  (= r2 / w)
+ *   person [7][nb]: n (answered items), l0 = sum l, e = sum eps, v = sum nu, sr2 = sum r2, sw = sum w, sz2 = sum zeta over the
+ *     items the person answered, by batch position;
+ *   item [4][J]: n, sr2, sw, sz2 over the persons who answered the item.
+ * lz = (l0 - e) / sqrt(v), outfit = sz2 / n, infit = sr2 / sw (float64 on the host: vipsy_amd.grid.person_fit_host /
+ * item_msq_host).  A person or item without answers has exact zeros in its sums.  workspace holds one partial [4][J] per
+ * workgroup, vx_grid_fit_workspace_floats(nb, J) floats; the number of workgroups depends on nb alone and every sum has a fixed
+ * order, no atomics: the same call gives the same bits on every device.  n is exact while a call scores at most 2^24 persons.
+ * Limits: model 1..4, 1 <= D <= 3, K <= 10, 1 <= J <= 1024, nb >= 1, ws_floats at least the size above; VX_EINVAL beyond. */
+int64_t vx_grid_fit_workspace_floats(int64_t nb, int32_t J);
+int vx_grid_fit_irt(const vx_irt_cfg* cfg, const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb,
+                    const float* theta_hat /*[nb][D]*/, const float* a /*[D][J] or NULL (1PL)*/, const float* b /*[J]*/,
+                    const float* c_un /*[J] or NULL*/, const float* d_un /*[J] or NULL*/,
+                    float* person /*[7][nb]: n, l0, e, v, sr2, sw, sz2*/, float* item /*[4][J]: n, sr2, sw, sz2*/,
+                    float* workspace, int64_t ws_floats, void* hip_stream);
+int vx_grid_fit_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const uint8_t* y /*[n_local][J]*/,
+                    const int64_t* rows /*[nb] or NULL*/, int64_t nb, const int32_t* pattern /*[nb]*/, const float* g_un,
+                    const float* s_un, float* person /*[7][nb]*/, float* item /*[4][J]*/, float* workspace, int64_t ws_floats,
+                    void* hip_stream);
+
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,
                     void* hip_stream);

@@ -143,6 +143,9 @@ SIGNATURES = {
     "vx_grid_pairs_workspace_min_floats": (_I64, [_I32]),
     "vx_grid_pairs_irt": (ctypes.c_int, [_CFG, _P, _P, _I64, _P] + [_P] * 4 + [_P] * 4 + [_P, _I64, _P]),
     "vx_grid_pairs_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32, _P, _P, _P, _I64, _P, _P, _P] + [_P] * 4 + [_P, _I64, _P]),
+    "vx_grid_fit_workspace_floats": (_I64, [_I64, _I32]),
+    "vx_grid_fit_irt": (ctypes.c_int, [_CFG, _P, _P, _I64, _P] + [_P] * 4 + [_P, _P] + [_P, _I64, _P]),
+    "vx_grid_fit_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32, _P, _P, _P, _I64, _P, _P, _P] + [_P, _P] + [_P, _I64, _P]),
     "vx_reduce_slabs": (ctypes.c_int, [_P, _I64, _I64, _F, _P, _P]),
     "vx_sum_workspace_floats": (_I64, []),
     "vx_sum": (ctypes.c_int, [_P, _I64, _F, _P, _P, _P, _P]),

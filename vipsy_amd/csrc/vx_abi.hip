@@ -36,6 +36,7 @@
 #include "k_grid_mstep.hip"
 #include "k_grid_info.hip"
 #include "k_grid_pairs.hip"
+#include "k_grid_fit.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2481,6 +2482,54 @@ int vx_grid_pairs_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, co
                            pattern + i0, g_un, s_un, (uint4*)workspace, n_units);
     };
     return grid_pairs_run(nb, J, n, s, ss, sp, workspace, ws_floats, hs, frag);
+}
+
+// Person fit (k_grid_fit.hip): the sums behind lz and infit / outfit per person and per item, one pass over persons x items
+int64_t vx_grid_fit_workspace_floats(int64_t nb, int32_t J) {
+    if (!grid_pairs_shape_ok(J, nb)) return VX_EINVAL;
+    return gf_ws_floats(nb, J);
+}
+
+// the item partials of the workgroups, added in ascending order
+static int grid_fit_finish(const GfPlan& p, int J, const float* workspace, float* item, void* hs) {
+    VX_CHECK_LAUNCH();
+    const int len = GF_ITEM * J;
+    hipLaunchKernelGGL(k_fit_items, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, (hipStream_t)hs, workspace, p.n_blocks, len, item);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_fit_irt(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* theta_hat, const float* a,
+                    const float* b, const float* c_un, const float* d_un, float* person, float* item, float* workspace,
+                    int64_t ws_floats, void* hs) {
+    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GF_MAXD || !grid_pairs_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (!y || !theta_hat || !b || !person || !item || !workspace) return VX_EINVAL;
+    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
+        return VX_EINVAL;
+    if (ws_floats < gf_ws_floats(nb, (int)cfg->J)) return VX_EINVAL;
+    hipStream_t st = (hipStream_t)hs;
+    const int D = (int)cfg->D, J = (int)cfg->J, model = (int)cfg->model;
+    const GfPlan p = gf_plan(nb);
+#define LAUNCH_GF(M)                                                                                                  \
+    hipLaunchKernelGGL((k_fit_irt<M>), dim3((unsigned)p.n_blocks), dim3(256), 0, st, y, rows, nb, D, J, cfg->Dc, theta_hat, a, b, c_un, \
+                       d_un, person, workspace, p.n_units, p.units_per_block)
+    if (model == 1) { LAUNCH_GF(1); } else if (model == 2) { LAUNCH_GF(2); } else if (model == 3) { LAUNCH_GF(3); }
+    else { LAUNCH_GF(4); }
+#undef LAUNCH_GF
+    return grid_fit_finish(p, J, workspace, item, hs);
+}
+
+int vx_grid_fit_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const uint8_t* y, const int64_t* rows, int64_t nb,
+                    const int32_t* pattern, const float* g_un, const float* s_un, float* person, float* item, float* workspace,
+                    int64_t ws_floats, void* hs) {
+    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || !grid_pairs_shape_ok(cfg->J, nb) || (dino != 0 && dino != 1)) return VX_EINVAL;
+    if (!q || !y || !pattern || !g_un || !s_un || !person || !item || !workspace) return VX_EINVAL;
+    if (ws_floats < gf_ws_floats(nb, (int)cfg->J)) return VX_EINVAL;
+    const int K = (int)cfg->K, J = (int)cfg->J;
+    const GfPlan p = gf_plan(nb);
+    hipLaunchKernelGGL(k_fit_cdm, dim3((unsigned)p.n_blocks), dim3(256), 0, (hipStream_t)hs, y, rows, nb, K, J, (int)dino, q, pattern, g_un,
+                       s_un, person, workspace, p.n_units, p.units_per_block);
+    return grid_fit_finish(p, J, workspace, item, hs);
 }
 
 // ------------------------------------------------------------------------------------------------

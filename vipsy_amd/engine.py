@@ -314,6 +314,21 @@ class HipBackend(object):
                                       int(ws_floats), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_pairs_cdm")
 
+    def grid_fit_workspace(self, nb, J):
+        return self._size("vx_grid_fit_workspace_floats", nb, J)
+
+    def grid_fit_irt(self, cfg, y, rows, nb, theta_hat, a, b, c_un, d_un, person, item, ws, ws_floats):
+        rc = self.L.vx_grid_fit_irt(ctypes.byref(cfg), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(theta_hat), _hip.ptr(a), _hip.ptr(b),
+                                    _hip.ptr(c_un), _hip.ptr(d_un), _hip.ptr(person), _hip.ptr(item), _hip.ptr(ws), int(ws_floats),
+                                    _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_fit_irt")
+
+    def grid_fit_cdm(self, cfg, dino, q, y, rows, nb, pattern, g, s_, person, item, ws, ws_floats):
+        rc = self.L.vx_grid_fit_cdm(ctypes.byref(cfg), int(dino), _hip.ptr(q), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(pattern),
+                                    _hip.ptr(g), _hip.ptr(s_), _hip.ptr(person), _hip.ptr(item), _hip.ptr(ws), int(ws_floats),
+                                    _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_fit_cdm")
+
     def cdm_sf_workspace(self, cfg, nb):
         return self._size("vx_cdm_sf_workspace_floats", ctypes.byref(cfg), nb)
 
@@ -645,6 +660,7 @@ class _EngineBase(object):
 
     score = expected_counts = plausible_values = item_fit = marginal_loglik = fit_em = item_information = item_se = _no_grid
     residual_sums = local_dependence = _no_grid
+    fit_sums = person_fit = item_msq = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1673,6 +1689,17 @@ class IrtEngine(GridMixin, _EngineBase):
         return call, "theta_hat", "mean", lambda est, t, ws, ws_floats: self.be.grid_pairs_irt(
             call.cfg, call.y, call.rows, call.n, est, *params, t["n"], t["s"], t["ss"], t["sp"], ws, ws_floats)
 
+    def _fit_call(self, y_u8, rows, nodes=61, span=6.0):
+        """What GridMixin.fit_sums needs of this class, shaped like _pairs_call: the GridCall (all four models; x_feature > 3 is
+        refused with the wording of score()), the name and the key of the point estimate, and the fit call over compact copies of
+        the engine's own items."""
+        call = self._grid_call(y_u8, rows, nodes, span)
+        flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()      # noqa: E731
+        params = (self.unconstrained("a").contiguous() if self.model != "irt_1pl" else None, flat("b"),
+                  flat("c") if self.model in ("irt_3pl", "irt_4pl") else None, flat("d") if self.model == "irt_4pl" else None)
+        return call, "theta_hat", "mean", lambda est, person, item, ws, ws_floats: self.be.grid_fit_irt(
+            call.cfg, call.y, call.rows, call.n, est, *params, person, item, ws, ws_floats)
+
     def _se_leaves(self, se):
         """Dense [P] -> the leaves' shapes: b (1, J) and, for 2PL, a (D, J)."""
         se = se.reshape(self.J_items, -1)
@@ -2105,6 +2132,13 @@ class CcdmEngine(GridMixin, _EngineBase):
         g, s_ = self.view("g").contiguous(), self.view("s").contiguous()
         return call, "pattern", "node", lambda est, t, ws, ws_floats: self.be.grid_pairs_cdm(
             call.cfg, self.cdm == "dino", self.q, call.y, call.rows, call.n, est, g, s_, t["n"], t["s"], t["ss"], t["sp"], ws, ws_floats)
+
+    def _fit_call(self, y_u8, rows):
+        """What GridMixin.fit_sums needs of this class (IrtEngine._fit_call): the point estimate is the MAP pattern."""
+        call = self._grid_call(y_u8, rows)
+        g, s_ = self.view("g").contiguous(), self.view("s").contiguous()
+        return call, "pattern", "node", lambda est, person, item, ws, ws_floats: self.be.grid_fit_cdm(
+            call.cfg, self.cdm == "dino", self.q, call.y, call.rows, call.n, est, g, s_, person, item, ws, ws_floats)
 
     def _se_leaves(self, se):
         """Dense [P] -> g_un, s_un (1, J) and, by the delta method, g and s on the probability scale: se x (1 - x)."""

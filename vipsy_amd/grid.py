@@ -1,5 +1,5 @@
 """The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide -- score(), expected_counts() /
-item_fit(), fit_em(), plausible_values(), item_information() / item_se(), residual_sums() / local_dependence() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
+item_fit(), fit_em(), plausible_values(), item_information() / item_se(), residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
 entries of the C ABI (k_grid_*.hip; no reference counterpart).  All of it works in buffers of its own: nothing a step reads is
 touched."""
 from collections import namedtuple
@@ -159,6 +159,47 @@ def pair_q3_summary(q3, top=20):
     order = np.argsort(-np.abs(val - mean), kind="stable")[:top]
     return {"mean": mean, "max": float((val - mean).max()), "item_j": jj[order].astype(np.int64),
             "item_k": kk[order].astype(np.int64), "value": val[order]}
+
+
+PERSON_SUMS = ("n", "l0", "e", "v", "sr2", "sw", "sz2")          # the rows of vx_grid_fit_*'s `person` ...
+ITEM_SUMS = ("n", "sr2", "sw", "sz2")                            # ... and of its `item`
+
+
+def _msq(n, sr2, sw, sz2):
+    """outfit = sz2 / n and infit = sr2 / sw in float64, NaN where n = 0 or sw <= 0."""
+    n, sr2, sw, sz2 = (np.asarray(t, np.float64) for t in (n, sr2, sw, sz2))
+    outfit, infit = np.full(n.shape, np.nan), np.full(n.shape, np.nan)
+    ok = n > 0
+    outfit[ok] = sz2[ok] / n[ok]
+    ok = ok & (sw > 0)
+    infit[ok] = sr2[ok] / sw[ok]
+    return infit, outfit
+
+
+def person_fit_host(person):
+    """The host layer of person_fit(): from the seven sums of a person's answered items ({n, l0, e, v, sr2, sw, sz2}, each
+    [persons]), in float64 numpy: `lz` = (l0 - e) / sqrt(v), the standardised log-likelihood of Drasgow, Levine and Williams
+    (e and v are the mean and the variance of l0 under the model at the estimate), `outfit` = sz2 / n, the mean squared
+    standardised residual, and `infit` = sr2 / sw, the information-weighted one.  NaN where the person answered nothing
+    (n = 0) or where v <= 0 (lz) / sw <= 0 (infit)."""
+    s = {k: np.asarray(person[k], np.float64) for k in PERSON_SUMS}
+    if any(v.ndim != 1 or v.shape != s["n"].shape for v in s.values()):
+        raise ValueError("the person sums must be vectors of one length")
+    lz = np.full(s["n"].shape, np.nan)
+    ok = (s["n"] > 0) & (s["v"] > 0)
+    lz[ok] = (s["l0"][ok] - s["e"][ok]) / np.sqrt(s["v"][ok])
+    infit, outfit = _msq(s["n"], s["sr2"], s["sw"], s["sz2"])
+    return {"lz": lz, "infit": infit, "outfit": outfit}
+
+
+def item_msq_host(item):
+    """The host layer of item_msq(): `infit` = sr2 / sw and `outfit` = sz2 / n from the four sums over the persons who answered
+    an item ({n, sr2, sw, sz2}, each [items]), float64 numpy; NaN for an item nobody answered (n = 0) or with sw <= 0."""
+    s = {k: np.asarray(item[k], np.float64) for k in ITEM_SUMS}
+    if any(v.ndim != 1 or v.shape != s["n"].shape for v in s.values()):
+        raise ValueError("the item sums must be vectors of one length")
+    infit, outfit = _msq(s["n"], s["sr2"], s["sw"], s["sz2"])
+    return {"infit": infit, "outfit": outfit}
 
 
 class GridCall(namedtuple("GridCall", "y rows J theta logw fill_tables cfg")):
@@ -380,6 +421,49 @@ class GridMixin(object):
         q3 = pair_q3_host(n, t["s"].cpu().numpy(), t["ss"].cpu().numpy(), t["sp"].cpu().numpy(), min_pairs)
         out = pair_q3_summary(q3, top)
         out["q3"], out["n_pairs"] = q3, np.rint(n).astype(np.int64)
+        return out
+
+    def fit_sums(self, y_u8=None, rows=None, **grid_kw):
+        """The sums behind person_fit() and item_msq() (vx_grid_fit_*), over the observed cells of the scored rows.  With P the
+        model probability AT THE PERSON'S POINT ESTIMATE -- the grid EAP of score() for IrtEngine (all four models), the MAP
+        pattern for CcdmEngine -- under the item parameters as they stand, Q = 1 - P and lambda = log(P / Q): float32 device
+        tensors `person` = {n, l0 = sum(y ? log P : log Q), e = sum(P log P + Q log Q), v = sum(P Q lambda^2), sr2 = sum(y ? Q^2
+        : P^2), sw = sum(P Q), sz2 = sum(y ? Q / P : P / Q)}, each (n,), over the items a person answered, and `item` = {n, sr2,
+        sw, sz2}, each (J,), over the persons who answered an item, beside `theta_hat` (n, D) or `pattern` (n,), the estimates
+        they were taken at.  A person or item without answers has exact zeros.  Inputs, grid and refusals as score(); with a
+        process group the sums are this rank's shard's (the person sums are complete, the item sums are not).  Works in buffers
+        of its own.  Deterministic: the same call gives the same bits.  The counts are exact up to 2**24 scored persons."""
+        call, name, key, run = self._fit_call(y_u8, rows, **grid_kw)
+        post = self._grid_posterior(call)
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        person, item = torch.empty(len(PERSON_SUMS), call.n, **f32), torch.empty(len(ITEM_SUMS), call.J, **f32)
+        ws_floats = self.be.grid_fit_workspace(call.n, call.J)
+        ws = torch.empty(ws_floats, **f32)
+        run(post[key], person, item, ws, ws_floats)
+        return {"person": dict(zip(PERSON_SUMS, person.unbind(0))), "item": dict(zip(ITEM_SUMS, item.unbind(0))), name: post[key]}
+
+    def person_fit(self, y_u8=None, rows=None, **grid_kw):
+        """Person fit of the scored rows (person_fit_host over fit_sums), numpy: `lz`, `infit`, `outfit` float64 (n,), `n_obs`
+        int64, `loglik0`, `expected`, `variance` (the l0, e, v of lz) and `theta_hat` or `pattern`.  lz is taken at the estimate
+        without Snijders' correction: on short tests its null distribution is somewhat narrower than N(0, 1).  NaN where a
+        person answered nothing.  With a process group: this rank's shard, as score()."""
+        t = self.fit_sums(y_u8, rows, **grid_kw)
+        s = {k: v.cpu().numpy() for k, v in t["person"].items()}
+        out = person_fit_host(s)
+        out["n_obs"] = np.rint(s["n"]).astype(np.int64)
+        out["loglik0"], out["expected"], out["variance"] = (s[k].astype(np.float64) for k in ("l0", "e", "v"))
+        name = "theta_hat" if "theta_hat" in t else "pattern"
+        out[name] = t[name].cpu().numpy()
+        return out
+
+    def item_msq(self, y_u8=None, rows=None, **grid_kw):
+        """The residual mean squares of every item over the scored rows (item_msq_host over fit_sums), numpy: `infit`, `outfit`
+        float64 (J,) and `n_obs` int64; NaN for an item nobody answered.  One rank only."""
+        self._one_rank_only("item_msq over a process group: fit_sums() gives the local shard's sums; the cross-rank sum is not "
+                            "built")
+        s = {k: v.cpu().numpy() for k, v in self.fit_sums(y_u8, rows, **grid_kw)["item"].items()}
+        out = item_msq_host(s)
+        out["n_obs"] = np.rint(s["n"]).astype(np.int64)
         return out
 
     def item_fit(self, y_u8=None, rows=None, **kw):

@@ -305,6 +305,34 @@ class BasePsy(object):
                                       "persons; the cross-rank sum is not built" % self.world)
         return self.engine.local_dependence(self._score_data(data), **kw)
 
+    def fit_sums(self, data=None, **grid_kw):
+        """The sums behind person_fit() and item_msq(), as device tensors: `person` {n, l0, e, v, sr2, sw, sz2}, each [persons],
+        `item` {n, sr2, sw, sz2}, each [items], and `theta_hat` or `pattern` (GridMixin.fit_sums).  `data`: None = the training
+        data; with a `group` this rank's shard.  The classes score() refuses refuse."""
+        return self.engine.fit_sums(self._score_data(data), **grid_kw)
+
+    def person_fit(self, data=None, **grid_kw):
+        """Person fit, ready to print: which response vectors the model cannot explain (guessing, copying, carelessness, a
+        booklet keyed with the wrong form).  For every person in `data` (None: the training data; with a `group` this rank's
+        shard, as score()), over the items the person answered and at the person's point estimate -- the EAP of score() for VIRT
+        / VaeIRT (every model, x_feature <= 3), the MAP pattern for VCCDM -- under the item parameters as they stand, numpy
+        arrays [persons]: `lz` (the standardised log-likelihood of Drasgow, Levine and Williams: large negative values are
+        misfit), `infit` and `outfit` (the information-weighted and the plain mean square of the standardised residuals: about
+        1 under the model), `n_obs` (int64, the answered items), `loglik0`, `expected`, `variance` (the log-likelihood at the
+        estimate, its mean and its variance under the model: lz = (loglik0 - expected) / sqrt(variance)) and `theta_hat` or
+        `pattern`.  lz is taken at the estimate WITHOUT Snijders' correction: its null distribution is somewhat narrower than
+        N(0, 1) on short tests.  NaN for a person who answered nothing.  The other classes refuse."""
+        return self.engine.person_fit(self._score_data(data), **grid_kw)
+
+    def item_msq(self, data=None, **grid_kw):
+        """The residual mean squares of every item over the persons in `data` (None: the training data), numpy arrays [items]:
+        `infit`, `outfit` (about 1 under the model; residuals and point estimates as person_fit()) and `n_obs` (int64, the
+        persons who answered the item); NaN for an item nobody answered.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("item_msq with a group of %d ranks: fit_sums() gives the local shard's sums; the "
+                                      "cross-rank sum is not built" % self.world)
+        return self.engine.item_msq(self._score_data(data), **grid_kw)
+
 class BaseIRT(BasePsy):
     """vi.py:536-656 (constructor kwargs identical: model, x_feature, share_cov, D, a_free, a0, b0)."""
 
