@@ -458,6 +458,28 @@ int vx_grid_draw(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] o
                  const void* img, const float* logw /*[G]*/, uint64_t seed, int64_t row_offset, int32_t draw0, int32_t ndraws,
                  int64_t stride, int32_t* node /*[nb][stride]*/, void* hip_stream);
 
+/* ---- Conditioned grid posteriors and draws: vx_grid_posterior / vx_grid_draw under a prior that differs from person to person,
+ * theta_i ~ N(mu_i, Sigma) (the latent regression mu_i = Gamma^T x_i of IrtEngine.fit_population).  On the grid its log density is
+ * logw[g] + tilt[i] . coord[g] + const_i with logw[g] = -1/2 coord[g]^T Sigma^-1 coord[g] (any shift) and tilt[i] = Sigma^-1 mu_i,
+ * [nb][D] by BATCH POSITION (row i of the call, not rows[i]).  With f[i][g] = (logw[g] + ll[i][g]) + tilt[i] . coord[g] and
+ * h[i][g] = logw[g] + tilt[i] . coord[g]:
+ *     logjoint[i] = log sum_g exp f[i][g]      lognorm[i] = log sum_g exp h[i][g]      (loglik_i = logjoint[i] - lognorm[i])
+ *     mean[i][D], argmax[i]                    as vx_grid_posterior, of this f
+ *     cov[i][D (D + 1) / 2]                    the posterior covariance of coord, upper triangle row by row (00, 01, 02, 11, 12, 22)
+ * A zero tilt gives vx_grid_posterior's loglik, mean and argmax in logjoint, mean and argmax bit for bit, sqrtf(cov_dd) its sd, and
+ * vx_grid_draw's nodes; noise, keys (seed, row_offset + row, node, draw) and ties of the draws are vx_grid_draw's, and a draw does
+ * not depend on how the draws are cut into launches.  No atomics, no workspace, every sum in a fixed order: the same call gives the
+ * same bits, and a person gives the same bits through `rows`.
+ * Limits: those of vx_grid_posterior / vx_grid_draw with 1 <= D <= 3; VX_EINVAL beyond them. */
+int vx_grid_posterior_cond(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G,
+                           int32_t D, const void* img, const float* logw /*[G]*/, const float* coord /*[G][D]*/,
+                           const float* tilt /*[nb][D]*/, float* logjoint /*[nb]*/, float* lognorm /*[nb]*/, float* mean /*[nb][D]*/,
+                           float* cov /*[nb][D (D + 1) / 2]*/, int32_t* argmax /*[nb]*/, void* hip_stream);
+int vx_grid_draw_cond(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G,
+                      int32_t D, const void* img, const float* logw /*[G]*/, const float* coord /*[G][D]*/,
+                      const float* tilt /*[nb][D]*/, uint64_t seed, int64_t row_offset, int32_t draw0, int32_t ndraws,
+                      int64_t stride, int32_t* node /*[nb][stride]*/, void* hip_stream);
+
 /* ---- Expected counts from the grid posteriors (the Bock-Aitkin E-step; the per-item half of what vx_grid_posterior gives per
  * person).  With p_i(g) = exp(logw[g] + ll[i][g] - loglik[i]), loglik being vx_grid_posterior's output for the same y, rows, nb,
  * img and logw:

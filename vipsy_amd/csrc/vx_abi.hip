@@ -37,6 +37,7 @@
 #include "k_grid_info.hip"
 #include "k_grid_pairs.hip"
 #include "k_grid_fit.hip"
+#include "k_grid_cond.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2239,6 +2240,43 @@ int vx_grid_draw(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, i
     for (int base = draw0 & ~3; base < hi; base += PV_CAP) {
         hipLaunchKernelGGL(k_grid_draw, dim3(blocks), dim3(GP_THREADS), pv_lds_bytes(G), (hipStream_t)hs, y, rows, nb, (int)J,
                            (int)G, (const uint4*)img, logw, seed, row_offset, base, (int)draw0, hi, stride, node);
+        VX_CHECK_LAUNCH();
+    }
+    return VX_OK;
+}
+
+// The conditioned entries (k_grid_cond.hip): vx_grid_posterior / vx_grid_draw with a tilt a person; launch shapes as theirs
+int vx_grid_posterior_cond(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, int32_t D, const void* img,
+                           const float* logw, const float* coord, const float* tilt, float* logjoint, float* lognorm, float* mean,
+                           float* cov, int32_t* argmax, void* hs) {
+    if (!y || !img || !aligned16(img) || !logw || !coord || !tilt || !logjoint || !lognorm || !mean || !cov || !argmax) return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb) || D < 1 || D > GPC_MAXD) return VX_EINVAL;
+    const int blocks = grid_unit_blocks(nb);
+    hipStream_t st = (hipStream_t)hs;
+    const uint4* im = (const uint4*)img;
+#define LAUNCH_GPC(DPV)                                                                                               \
+    hipLaunchKernelGGL((k_grid_post_cond<DPV>), dim3(blocks), dim3(GP_THREADS), (size_t)gp_nt(G) * 32 * (DPV + 1) * sizeof(float), \
+                       st, y, rows, nb, (int)J, (int)G, (int)D, im, logw, coord, tilt, logjoint, lognorm, mean, cov, argmax)
+    if (D == 1) { LAUNCH_GPC(1); } else if (D == 2) { LAUNCH_GPC(2); } else { LAUNCH_GPC(3); }
+#undef LAUNCH_GPC
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_draw_cond(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, int32_t D, const void* img,
+                      const float* logw, const float* coord, const float* tilt, uint64_t seed, int64_t row_offset, int32_t draw0,
+                      int32_t ndraws, int64_t stride, int32_t* node, void* hs) {
+    if (!y || !img || !aligned16(img) || !logw || !coord || !tilt || !node) return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb) || D < 1 || D > GPC_MAXD) return VX_EINVAL;
+    if (draw0 < 0 || draw0 > PV_MAXDRAWS || ndraws < 1 || ndraws > PV_MAXDRAWS || draw0 + ndraws > PV_MAXDRAWS ||
+        (int64_t)draw0 + ndraws > stride)
+        return VX_EINVAL;
+    const int blocks = grid_unit_blocks(nb);
+    const int hi = draw0 + ndraws;
+    for (int base = draw0 & ~3; base < hi; base += PVC_CAP) {
+        hipLaunchKernelGGL(k_grid_draw_cond, dim3(blocks), dim3(GP_THREADS), pvc_lds_bytes(G), (hipStream_t)hs, y, rows, nb, (int)J,
+                           (int)G, (int)D, (const uint4*)img, logw, coord, tilt, seed, row_offset, base, (int)draw0, hi, stride,
+                           node);
         VX_CHECK_LAUNCH();
     }
     return VX_OK;

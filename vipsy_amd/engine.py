@@ -16,7 +16,7 @@ import torch
 
 from . import _hip
 from .grid import (EM_MAX_NEWTON, PV_MAX_DRAWS, PV_STREAM, SCORE_MAX_DIMS, SCORE_MAX_NODES, GridCall, GridMixin,  # noqa: F401
-                   grid_image_prob, item_fit_stats, score_grid)     # (re-exported: the grid family lives in grid.py)
+                   design_cholesky, grid_image_prob, item_fit_stats, population_logw, score_grid, tri_to_full)     # (re-exported: the grid family lives in grid.py)
 
 MODEL_CODE = {"irt_1pl": 1, "irt_2pl": 2, "irt_3pl": 3, "irt_4pl": 4}       # vi.py:538-543
 LOSS_RING = 64                                                               # VX_LOSS_RING (include/vipsy_amd.h)
@@ -270,6 +270,18 @@ class HipBackend(object):
         rc = self.L.vx_grid_draw(_hip.ptr(y), _hip.ptr(rows), nb, J, G, _hip.ptr(img), _hip.ptr(logw), int(seed), int(row_offset),
                                  int(draw0), int(ndraws), int(stride), _hip.ptr(node), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_draw")
+
+    def grid_posterior_cond(self, y, rows, nb, J, G, D, img, logw, coord, tilt, logjoint, lognorm, mean, cov, argmax):
+        rc = self.L.vx_grid_posterior_cond(_hip.ptr(y), _hip.ptr(rows), nb, J, G, D, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord),
+                                           _hip.ptr(tilt), _hip.ptr(logjoint), _hip.ptr(lognorm), _hip.ptr(mean), _hip.ptr(cov),
+                                           _hip.ptr(argmax), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_posterior_cond")
+
+    def grid_draw_cond(self, y, rows, nb, J, G, D, img, logw, coord, tilt, seed, row_offset, draw0, ndraws, stride, node):
+        rc = self.L.vx_grid_draw_cond(_hip.ptr(y), _hip.ptr(rows), nb, J, G, D, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord),
+                                      _hip.ptr(tilt), int(seed), int(row_offset), int(draw0), int(ndraws), int(stride),
+                                      _hip.ptr(node), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_draw_cond")
 
     def grid_wimage_bytes(self, P, G):
         return self._size("vx_grid_wimage_bytes", P, G)
@@ -659,6 +671,7 @@ class _EngineBase(object):
                                   "CcdmEngine have them)" % type(self).__name__)
 
     score = expected_counts = plausible_values = item_fit = marginal_loglik = fit_em = item_information = item_se = _no_grid
+    fit_population = _no_grid
     residual_sums = local_dependence = _no_grid
     fit_sums = person_fit = item_msq = _no_grid
 
@@ -1580,15 +1593,73 @@ class IrtEngine(GridMixin, _EngineBase):
             return torch.tril(u, -1) + torch.diag_embed(torch.exp(diag))
         return u.clone()
 
-    def score(self, y_u8=None, rows=None, nodes=61, span=6.0):
+    population = None            # fit_population()'s result: {"gamma" [p][D], "sigma" [D][D], "intercept"}
+
+    def score(self, y_u8=None, rows=None, nodes=61, span=6.0, covariates=None):
         """Person scores by quadrature over a grid (score_grid): for each scored row the posterior mean `eap` (n, D) and
         standard deviation `psd` (n, D) of the latent under the N(0, I) prior and the item parameters as they stand, the
         marginal log-likelihood `loglik` (n,) and the MAP grid node `node` (n,).  y_u8: responses to score ([n, item_size]
         uint8, 255 = missing), by default the training responses; rows: indices into them.  Exact and deterministic, needs
         no guide: new respondents are scored like training ones.  The model's own items and dimensions only -- phantom
-        items / dimensions of a padded engine are not in the tables.  x_feature <= 3 and nodes ** x_feature <= 1024."""
+        items / dimensions of a padded engine are not in the tables.  x_feature <= 3 and nodes ** x_feature <= 1024.
+        covariates ([rows of y_u8][p], indexed by `rows` where rows is given): score under each person's own prior
+        N(Gamma^T x_i, Sigma) of the population fit_population() estimated, instead of N(0, I); then also `cov` (n, D, D), the
+        posterior covariance (psd = the square roots of its diagonal), and `prior_mean` (n, D) = Gamma^T x_i."""
+        if covariates is not None:
+            call, tilt, mu = self._population_call(y_u8, rows, nodes, span, covariates)
+            out = self._grid_posterior_cond(call, tilt)
+            cov = tri_to_full(out["cov"], call.D)
+            return {"eap": out["mean"], "psd": torch.sqrt(torch.diagonal(cov, dim1=-2, dim2=-1)).contiguous(),
+                    "loglik": out["logjoint"] - out["lognorm"], "node": out["node"], "cov": cov, "prior_mean": mu}
         out = self._grid_posterior(self._grid_call(y_u8, rows, nodes, span))
         return {"eap": out["mean"], "psd": out["sd"], "loglik": out["loglik"], "node": out["node"]}
+
+    def _population_call(self, y_u8, rows, nodes, span, covariates):
+        """The GridCall of a conditioned score: the nodes of score() with the log-weights of engine.population's Sigma, the tilt
+        Lambda Gamma^T x_i [n][D] float32 by batch position and the prior means Gamma^T x_i."""
+        pop = self.population
+        if pop is None:
+            raise ValueError("covariates need a fitted population: call fit_population() first")
+        if isinstance(nodes, (tuple, list)):
+            raise ValueError("a conditioned score takes `nodes` points a dimension: the population sets the log-weights")
+        call = self._grid_call(y_u8, rows, nodes, span)
+        X = self._design(covariates, int(call.y.shape[0]), pop["intercept"], pop["gamma"].shape[0])
+        if call.rows is not None:
+            X = X[call.rows]
+        mu = X @ torch.from_numpy(pop["gamma"]).to(self.dev)
+        tilt = (mu @ torch.from_numpy(np.linalg.inv(pop["sigma"])).to(self.dev)).to(torch.float32).contiguous()
+        logw = torch.from_numpy(population_logw(call.theta.cpu().numpy(), pop["sigma"])).to(self.dev)
+        return call._replace(logw=logw), tilt, mu.to(torch.float32)
+
+    def fit_population(self, covariates, rows=None, max_iter=200, tol=1e-7, intercept=True, nodes=61, span=6.0, progress=False):
+        """The latent regression (conditioning model) of the training responses on `covariates` ([training rows][p], float,
+        finite; intercept: a column of ones in front): theta_i ~ N(Gamma^T x_i, Sigma), fitted by EM with the item parameters
+        fixed as they stand -- each iteration scores the rows under their own priors (vx_grid_posterior_cond) and solves the
+        normal equations of the posterior means, Sigma' = the mean of the posterior covariances plus the residuals' cross
+        products -- from Gamma = 0, Sigma = I, until the log-likelihood sum_i log p(y_i | x_i) changes by no more than tol times
+        its size between two iterations, or for max_iter iterations.  rows: the training rows to fit on (default all).
+        Returns {"gamma": float64 numpy [p][D], "sigma": [D][D], "loglik": [floats], "iterations", "converged"}, loglik[k] under
+        the parameters iteration k STARTED from (as fit_em reports it), and keeps the result as `engine.population`, which
+        score(covariates=...) and plausible_values(covariates=...) condition on.  All four models, x_feature <= 3; one rank.
+        Nothing else of the engine changes: the leaves, the guide, Adam's state and the step count stay.
+        ValueError: X^T X not positive definite; fewer persons than p + D + 1; a diagonal entry of Sigma below (half the node
+        spacing)^2 or a singular Sigma (the grid cannot resolve such a population); max_i |mu_id| + 4 sqrt(Sigma_dd) beyond span (raise span)."""
+        self._one_rank_only("fit_population over a process group: the M-step's sums are the local shard's and the cross-rank sum "
+                            "is not built")
+        self._int_in("max_iter", max_iter, 1)
+        if isinstance(nodes, (tuple, list)):
+            raise ValueError("fit_population takes `nodes` points a dimension: the population sets the log-weights")
+        call = self._grid_call(None, rows, nodes, span)
+        X = self._design(covariates, int(call.y.shape[0]), bool(intercept))
+        if call.rows is not None:
+            X = X[call.rows].contiguous()
+        n, p, D = call.n, int(X.shape[1]), call.D
+        if n < p + D + 1:
+            raise ValueError("fit_population needs at least p + D + 1 = %d persons (got %d)" % (p + D + 1, n))
+        out = self._population_em(call, X, design_cholesky(X), 2.0 * float(span) / (int(nodes) - 1), float(span), max_iter,
+                                  float(tol), progress)
+        self.population = {"gamma": out["gamma"], "sigma": out["sigma"], "intercept": bool(intercept)}
+        return out
 
     def _grid_call(self, y_u8, rows, nodes, span, params=None):
         """The GridCall of score() and its kin.  params: the tensors to tabulate, compact (a [D_model][J_items] or None, b, c_un,
@@ -1608,7 +1679,7 @@ class IrtEngine(GridMixin, _EngineBase):
         return GridCall(y, rows, J, theta, logw,
                         lambda img: self.be.grid_table_irt(cfg, theta, int(theta.shape[0]), *params, img), cfg)
 
-    def plausible_values(self, y_u8=None, rows=None, draws=5, seed=0, nodes=61, span=6.0):
+    def plausible_values(self, y_u8=None, rows=None, draws=5, seed=0, nodes=61, span=6.0, covariates=None):
         """Plausible values: `draws` independent draws of each scored row's latent from its posterior on the grid of score()
         (the N(0, I) prior times the likelihood under the item parameters as they stand): `theta` float32 (n, draws, D), the
         coordinates of the drawn nodes, and `node` int32 (n, draws).  Inputs, grid and refusals as score().  draws: 1 .. 1024;
@@ -1617,8 +1688,15 @@ class IrtEngine(GridMixin, _EngineBase):
         call's rows, and the shards of a process group draw independently.
         The draws sit ON grid nodes: their resolution is the node spacing (2 span / (nodes - 1) a dimension); ask for more
         nodes for finer draws.  They are taken under the item parameters as they stand, as fixed: the uncertainty of the item
-        parameters is not in them."""
+        parameters is not in them.
+        covariates (as score() takes them): draw under each person's own prior N(Gamma^T x_i, Sigma) of the population
+        fit_population() estimated -- the conditioning model a regression of the draws on those covariates needs, without
+        which its slopes are attenuated by about the test's reliability.  The noise is keyed as before."""
         draws, seed = self._draw_args(draws, seed)
+        if covariates is not None:
+            call, tilt, _ = self._population_call(y_u8, rows, nodes, span, covariates)
+            node, theta = self._grid_draws_cond(call, tilt, draws, seed, self.gid0 if y_u8 is None else 0)
+            return {"theta": theta, "node": node}
         node, theta = self._grid_draws(self._grid_call(y_u8, rows, nodes, span), draws, seed, self.gid0 if y_u8 is None else 0)
         return {"theta": theta, "node": node}
 

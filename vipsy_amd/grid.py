@@ -1,7 +1,9 @@
-"""The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide -- score(), expected_counts() /
-item_fit(), fit_em(), plausible_values(), item_information() / item_se(), residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq() and marginal_loglik() of IrtEngine (x_feature <= 3) and CcdmEngine, on the vx_grid_*
-entries of the C ABI (k_grid_*.hip; no reference counterpart).  All of it works in buffers of its own: nothing a step reads is
-touched."""
+"""The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide.  On IrtEngine (x_feature <= 3)
+and CcdmEngine: score(), expected_counts() / item_fit(), fit_em(), plausible_values(), item_information() / item_se(),
+residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq() and marginal_loglik().  On IrtEngine alone:
+fit_population(), the latent regression, and the score() / plausible_values() conditioned on it (covariates=).  All of it runs
+on the vx_grid_* entries of the C ABI (k_grid_*.hip; no reference counterpart) and works in buffers of its own: nothing a step
+reads is touched."""
 from collections import namedtuple
 
 import numpy as np
@@ -51,6 +53,82 @@ def score_grid(D, nodes=61, span=6.0):
     lw = -0.5 * (theta ** 2).sum(axis=1)
     lw = lw - (lw.max() + np.log(np.exp(lw - lw.max()).sum()))
     return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
+
+
+def population_logw(theta, sigma):
+    """The shared log-weights of the nodes under a population N(mu_i, sigma): -1/2 theta_g^T sigma^-1 theta_g, shifted so that the
+    largest is 0 (the per-person normaliser is the kernel's lognorm), computed in float64, returned as float32 [G]."""
+    theta = np.asarray(theta, np.float64)
+    sigma = np.asarray(sigma, np.float64)
+    if theta.ndim != 2 or sigma.shape != (theta.shape[1], theta.shape[1]):
+        raise ValueError("theta must be [G, D] and sigma [D, D]")
+    lw = -0.5 * np.einsum("gd,de,ge->g", theta, np.linalg.inv(sigma), theta)
+    return np.ascontiguousarray(lw - lw.max(), dtype=np.float32)
+
+
+def tri_to_full(tri, D):
+    """[..., D (D + 1) / 2] upper triangle row by row (00, 01, 02, 11, 12, 22) -> the symmetric [..., D, D]."""
+    iu = np.triu_indices(D)
+    if isinstance(tri, torch.Tensor):
+        full = tri.new_empty(tri.shape[:-1] + (D, D))
+        r, c = torch.as_tensor(iu[0], device=tri.device), torch.as_tensor(iu[1], device=tri.device)
+    else:
+        tri = np.asarray(tri)
+        full = np.empty(tri.shape[:-1] + (D, D), tri.dtype)
+        r, c = iu
+    full[..., r, c] = tri
+    full[..., c, r] = tri
+    return full
+
+
+def _population_sums(X, mean, cov):
+    """What the M-step needs of the persons, in float64 torch where X lives, as one flat tensor: X^T m [p][D], m^T m [D][D] and
+    the sum of the persons' covariance triangles [D (D + 1) / 2]."""
+    m = mean.to(torch.float64)
+    # elementwise products and a column reduction, not a GEMM: see _population_em
+    xtm = torch.stack([(X * m[:, d:d + 1]).sum(0) for d in range(m.shape[1])], 1)
+    mtm = (m[:, :, None] * m[:, None, :]).sum(0)
+    return torch.cat([xtm.reshape(-1), mtm.reshape(-1), cov.to(torch.float64).sum(0).reshape(-1)])
+
+
+def _population_solve(sums, XtX_chol, n, p, D):
+    """Gamma' and Sigma' from _population_sums on the host.  With X^T X Gamma' = X^T m the residual cross products are
+    sum_i (m_i - Gamma'^T x_i)(m_i - Gamma'^T x_i)^T = m^T m - Gamma'^T (X^T m)."""
+    sums = np.asarray(sums, np.float64)
+    xtm, mtm = sums[:p * D].reshape(p, D), sums[p * D:p * D + D * D].reshape(D, D)
+    csum = tri_to_full(sums[p * D + D * D:], D)
+    L = np.asarray(XtX_chol, np.float64)
+    gamma = np.linalg.solve(L.T, np.linalg.solve(L, xtm))
+    rss = mtm - gamma.T @ xtm
+    sigma = (csum + 0.5 * (rss + rss.T)) / float(n)
+    return gamma, sigma
+
+
+def population_mstep(X, XtX_chol, mean, cov):
+    """The M-step of the latent regression theta_i ~ N(Gamma^T x_i, Sigma) from the persons' posterior means m_i and covariances
+    C_i, in float64: Gamma' = (X^T X)^-1 X^T m and Sigma' = (1 / n) sum_i [C_i + (m_i - Gamma'^T x_i)(m_i - Gamma'^T x_i)^T].
+    X [n][p] float64 torch (on any device: the n x p products run there), XtX_chol the lower Cholesky factor of X^T X (numpy
+    [p][p]: the solve runs on the host), mean [n][D], cov [n][D (D + 1) / 2] (upper triangle row by row) torch, any float dtype.
+    Returns (Gamma' [p][D], Sigma' [D][D]) as float64 numpy."""
+    n, p = int(X.shape[0]), int(X.shape[1])
+    D = int(mean.shape[1])
+    if X.dtype != torch.float64 or mean.shape[0] != n or tuple(cov.shape) != (n, D * (D + 1) // 2):
+        raise ValueError("X must be float64 [n][p], mean [n][D] and cov [n][D (D + 1) / 2]")
+    return _population_solve(_population_sums(X, mean, cov).cpu().numpy(), XtX_chol, n, p, D)
+
+
+def design_cholesky(X):
+    """The lower Cholesky factor of X^T X (float64 numpy [p][p]) of a design X float64 torch [n][p]; ValueError naming the
+    column of the failing pivot if X^T X is not positive definite (a constant column beside the intercept, collinear columns)."""
+    A = torch.stack([(X * X[:, j:j + 1]).sum(0) for j in range(X.shape[1])]).cpu().numpy()      # (X^T X as _population_sums forms X^T m)
+    A = 0.5 * (A + A.T)
+    W = A.copy()
+    for i in range(A.shape[0]):                     # the pivots: one below 1e-10 of its diagonal entry is rounding, not information
+        if not W[i, i] > 1e-10 * A[i, i]:
+            raise ValueError("X^T X of the %d design columns is not positive definite: pivot %.3e at column %d (the intercept, "
+                             "where there is one, is column 0) -- a constant or collinear covariate" % (A.shape[0], W[i, i], i))
+        W[i + 1:, i + 1:] -= np.outer(W[i + 1:, i], W[i, i + 1:]) / W[i, i]
+    return np.linalg.cholesky(A)
 
 
 def grid_image_prob(img, J, G):
@@ -285,6 +363,168 @@ class GridMixin(object):
         node = torch.empty(call.n, draws, dtype=torch.int32, device=self.dev)
         self.be.grid_draw(call.y, call.rows, call.n, call.J, call.G, img, call.logw, seed, row_offset, 0, draws, draws, node)
         return node, call.theta[node.long()]
+
+    def _grid_posterior_cond(self, call, tilt, img=None, out=None):
+        """Tables (unless img holds them) and the conditioned posterior kernel under call.logw and a tilt a person ([n][D] float32,
+        by batch position): logjoint, lognorm [n], mean [n][D], cov [n][D (D + 1) / 2], node [n], and the image."""
+        n, D = call.n, call.D
+        if img is None:
+            img = self._grid_image(call)
+        if out is None:
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            out = {"logjoint": torch.empty(n, **f32), "lognorm": torch.empty(n, **f32), "mean": torch.empty(n, D, **f32),
+                   "cov": torch.empty(n, D * (D + 1) // 2, **f32), "node": torch.empty(n, dtype=torch.int32, device=self.dev)}
+        self.be.grid_posterior_cond(call.y, call.rows, n, call.J, call.G, D, img, call.logw, call.theta, tilt, out["logjoint"],
+                                    out["lognorm"], out["mean"], out["cov"], out["node"])
+        out["img"] = img
+        return out
+
+    def _grid_draws_cond(self, call, tilt, draws, seed, row_offset):
+        """_grid_draws under call.logw and a tilt a person (vx_grid_draw_cond): the noise goes by the row, the tilt by the batch
+        position."""
+        img = self._grid_image(call)
+        node = torch.empty(call.n, draws, dtype=torch.int32, device=self.dev)
+        self.be.grid_draw_cond(call.y, call.rows, call.n, call.J, call.G, call.D, img, call.logw, call.theta, tilt, seed, row_offset,
+                               0, draws, draws, node)
+        return node, call.theta[node.long()]
+
+    def _design(self, covariates, n_rows, intercept, p=None):
+        """covariates [n_rows][p'] -> the design X float64 [n_rows][p] on the device, a column of ones in front where intercept."""
+        X = torch.as_tensor(covariates)
+        if X.dim() == 1:
+            X = X[:, None]
+        if X.dim() != 2 or not (X.dtype.is_floating_point or X.dtype in (torch.int32, torch.int64, torch.uint8, torch.bool)):
+            raise ValueError("covariates must be a numeric matrix [persons][p]")
+        X = X.to(device=self.dev, dtype=torch.float64)
+        if int(X.shape[0]) != n_rows:
+            raise ValueError("covariates have %d rows, the responses %d" % (X.shape[0], n_rows))
+        if intercept:
+            X = torch.cat([torch.ones(n_rows, 1, dtype=torch.float64, device=self.dev), X], 1)
+        if p is not None and int(X.shape[1]) != p:
+            raise ValueError("the population was fitted on %d design columns (intercept %s), these covariates give %d"
+                             % (p, "included" if intercept else "not used", X.shape[1]))
+        if not bool(torch.isfinite(X).all()):
+            raise ValueError("covariates must be finite")
+        return X.contiguous()
+
+    @staticmethod
+    def _population_check(sigma, spacing):
+        """The refusal of a Sigma the grid cannot resolve, before anything is computed from it: a diagonal entry below (half the
+        node spacing)^2, or -- for D > 1, where the diagonal can stay healthy while a correlation runs to +-1 -- a smallest
+        eigenvalue at or below 1e-6 of the largest: Lambda = Sigma^-1 then has entries a million times the scale of the problem,
+        and the float32 log-weights and tilts built from it carry nothing."""
+        lim = (0.5 * spacing) ** 2
+        ev = np.linalg.eigvalsh(0.5 * (sigma + sigma.T)) if np.isfinite(sigma).all() else np.full(1, np.nan)
+        if not np.isfinite(sigma).all() or (np.diag(sigma) < lim).any() or not ev[0] > 1e-6 * ev[-1]:
+            raise ValueError("the population covariance collapses: diag(Sigma) = %s fell below (half the node spacing)^2 = %.3e, or "
+                             "Sigma is singular (eigenvalues %s) -- the grid cannot resolve such a population (more nodes, or a "
+                             "test that measures every dimension)" % (np.diag(sigma), lim, ev))
+
+    @staticmethod
+    def _population_reach(mu_max, sigma, span):
+        """The refusal of a population that leaves the grid."""
+        reach = np.asarray(mu_max, np.float64) + 4.0 * np.sqrt(np.diag(sigma))
+        if (reach > span).any():
+            raise ValueError("the population leaves the grid: max_i |mu_id| + 4 sqrt(Sigma_dd) = %s exceeds span = %g -- raise span "
+                             "(and nodes with it)" % (reach, span))
+
+    def _population_em(self, call, X, chol, spacing, span, max_iter, tol, progress):
+        """The EM iterations of fit_population over a call whose tables stay fixed: logw and tilt = X Gamma Lambda of the
+        parameters as they stand, vx_grid_posterior_cond, the sum of logjoint - lognorm (as marginal_loglik sums), and the
+        sums of the M-step on the device; the p x p solve runs on the host.  Every buffer, on the device and pinned on the host,
+        is made once, before the loop, and an iteration writes into them (out=): it allocates nothing on the device.  The
+        parameters of an iteration (logw, Gamma, Lambda) go up in ONE asynchronous copy out of a pinned staging buffer, and its
+        results (the log-likelihood, max |mu|, X^T m, m^T m, the sum of the covariance triangles) come back in ONE copy into a
+        pinned buffer, behind which the host waits: the one host sync of an iteration."""
+        be, dev, n, D, p, G = self.be, self.dev, call.n, call.D, int(X.shape[1]), call.G
+        T = D * (D + 1) // 2
+        f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
+        img = self._grid_image(call)                                             # (the item parameters are fixed: filled once)
+        out = {"logjoint": torch.empty(n, **f32), "lognorm": torch.empty(n, **f32), "mean": torch.empty(n, D, **f32),
+               "cov": torch.empty(n, T, **f32), "node": torch.empty(n, dtype=torch.int32, device=dev)}
+        diff, tilt, logw = torch.empty(n, **f32), torch.empty(n, D, **f32), torch.empty(G, **f32)
+        total, sum_ws = torch.empty(1, **f32), torch.empty(1024, **f32)          # vx_sum_workspace_floats(); not the step's
+        # up: [logw G | Gamma p D | Lambda D D]; down: [loglik 1 | max |mu| D | (X^T m)^T D p | m^T m D D | sum C T]
+        up_h = torch.empty(G + p * D + D * D, dtype=torch.float64).pin_memory()
+        up = torch.empty(G + p * D + D * D, **f64)
+        down_h = torch.empty(1 + D + D * p + D * D + T, dtype=torch.float64).pin_memory()
+        down = torch.empty(1 + D + D * p + D * D + T, **f64)
+        up_np, down_np = up_h.numpy(), down_h.numpy()
+        gam_d, lam_d = up[G:G + p * D].view(p, D), up[G + p * D:].view(D, D)
+        mumax_d, xtm_d = down[1:1 + D], down[1 + D:1 + D + D * p].view(D, p)
+        mtm_d, csum_d = down[1 + D + D * p:1 + D + D * p + D * D].view(D, D), down[1 + D + D * p + D * D:]
+        mu, work, m64, c64 = torch.empty(n, D, **f64), torch.empty(n, D, **f64), torch.empty(n, D, **f64), torch.empty(n, T, **f64)
+        xw = torch.empty(n, p, **f64)
+        theta64 = call.theta.cpu().numpy().astype(np.float64)
+        cond = call._replace(logw=logw)
+        stream = torch.cuda.current_stream(dev)
+
+        def mu_into():
+            """mu = X Gamma and max_i |mu_id| (into the results buffer) of the Gamma that has gone up."""
+            torch.matmul(X, gam_d, out=mu)
+            torch.abs(mu, out=work)
+            torch.amax(work, 0, out=mumax_d)
+
+        gamma, sigma = np.zeros((p, D)), np.eye(D)
+        bar = None
+        if progress:
+            try:
+                from tqdm import trange
+                bar = trange(max_iter)
+            except Exception:  # pragma: no cover
+                bar = None
+        hist, converged = [], False
+        for _ in range(max_iter):
+            self._population_check(sigma, spacing)                               # (before Sigma is inverted)
+            lam = np.linalg.inv(sigma)
+            lw = -0.5 * np.einsum("gd,de,ge->g", theta64, lam, theta64)
+            up_np[:G], up_np[G:G + p * D], up_np[G + p * D:] = lw - lw.max(), gamma.reshape(-1), lam.reshape(-1)
+            up.copy_(up_h, non_blocking=True)
+            logw.copy_(up[:G])                                                   # (float64 -> float32: population_logw's rounding)
+            mu_into()
+            torch.matmul(mu, lam_d, out=work)
+            tilt.copy_(work)
+            self._grid_posterior_cond(cond, tilt, img, out)
+            torch.sub(out["logjoint"], out["lognorm"], out=diff)
+            be.sum_into(diff, n, 1.0, total, sum_ws)
+            down[0:1].copy_(total)
+            # the M-step's sums as elementwise products and column reductions: a float64 GEMM whose inner dimension is the
+            # persons and whose outer ones are 1 .. 8 takes 20 ms at a million persons where these take 0.04 (DESIGN.md section 6)
+            m64.copy_(out["mean"])
+            c64.copy_(out["cov"])
+            for d in range(D):
+                torch.mul(X, m64[:, d:d + 1], out=xw)
+                torch.sum(xw, 0, out=xtm_d[d])
+                torch.mul(m64, m64[:, d:d + 1], out=work)
+                torch.sum(work, 0, out=mtm_d[d])
+            torch.sum(c64, 0, out=csum_d)
+            down_h.copy_(down, non_blocking=True)
+            stream.synchronize()                                                 # the iteration's one host sync
+            self._population_reach(down_np[1:1 + D], sigma, span)                # (of the parameters this iteration started from)
+            sums = np.concatenate([down_np[1 + D:1 + D + D * p].reshape(D, p).T.reshape(-1), down_np[1 + D + D * p:]])
+            hist.append(float(down_np[0]))
+            gamma, sigma = _population_solve(sums, chol, n, p, D)
+            if bar is not None:
+                bar.update(1)
+                bar.set_postfix(loglik="{0:1.4f}".format(hist[-1]))
+            if len(hist) > 1 and abs(hist[-1] - hist[-2]) <= tol * abs(hist[-2]):
+                converged = True
+                break
+        if bar is not None:
+            bar.close()
+        self._population_check(sigma, spacing)                                   # what is returned is held to the same two rules
+        up_np[G:G + p * D] = gamma.reshape(-1)
+        up.copy_(up_h, non_blocking=True)
+        mu_into()
+        down_h.copy_(down, non_blocking=True)
+        stream.synchronize()
+        self._population_reach(down_np[1:1 + D], sigma, span)
+        return {"gamma": gamma, "sigma": sigma, "loglik": hist, "iterations": len(hist), "converged": converged}
+
+    def fit_population(self, covariates, **kw):
+        raise NotImplementedError("%s has no latent regression: fit_population models a continuous latent, theta_i ~ N(Gamma^T x_i, "
+                                  "Sigma); attribute patterns have no such population (IrtEngine with x_feature <= 3 has it)"
+                                  % type(self).__name__)
 
     def _grid_counts(self, call):
         """The posterior kernel for loglik, then the counts kernel over the same image: n1, n0 [J][G], mass [G] and prob [J][G] =

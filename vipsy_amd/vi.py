@@ -219,6 +219,19 @@ class BasePsy(object):
         under the item parameters as they stand, without item-parameter uncertainty.  The other classes refuse."""
         return self.engine.plausible_values(self._score_data(data), **kw)
 
+    def fit_population(self, covariates, **kw):
+        """The latent regression of the training data on `covariates` ([persons][p], float, finite): theta_i ~ N(Gamma^T x_i,
+        Sigma), fitted by EM over the grid of score() with the item parameters fixed as they stand (IrtEngine.fit_population:
+        rows, max_iter=200, tol=1e-7, intercept=True, nodes=61, span=6.0).  Returns {"gamma" [p][x_feature], "sigma", "loglik",
+        "iterations", "converged"} and keeps the population on the engine: score(covariates=...), plausible_values(covariates=...)
+        and marginal_loglik(covariates=...) then work under each person's own prior -- the conditioning model a secondary
+        analysis of plausible values needs.  VIRT / VaeIRT with x_feature <= 3, every IRT model; the classes score() refuses and
+        VCCDM refuse.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("fit_population with a group of %d ranks: the M-step's sums are the local shard's; the "
+                                      "cross-rank sum is not built" % self.world)
+        return self.engine.fit_population(covariates, **kw)
+
     def expected_counts(self, data=None, **kw):
         """The expected-count tables of the persons in `data` (None: the training data) over the grid of score(): device
         tensors n1, n0 [items][nodes], mass [nodes], prob [items][nodes], and theta / logw (IRT) or patterns (VCCDM); see
