@@ -495,6 +495,30 @@ int vx_grid_counts(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb]
                    const void* img, const float* logw /*[G]*/, const float* loglik /*[nb]*/, float* n1 /*[J][G]*/,
                    float* n0 /*[J][G]*/, float* mass /*[G]*/, float* workspace, void* hip_stream);
 
+/* ---- Expected counts under a prior of each person's own, a table set a SEGMENT of the persons: vx_grid_counts for the
+ * conditioned posterior of vx_grid_posterior_cond, and the E-step of the item-by-group fit statistics (differential item
+ * functioning).  With p_i(g) = exp(f[i][g] - logjoint[i]), f[i][g] = (logw[g] + ll[i][g]) + tilt[i] . coord[g] as defined there
+ * and logjoint that entry's output for the same y, rows, nb, img, logw, coord and tilt (tilt and logjoint by BATCH POSITION), the
+ * batch positions are cut into n_seg consecutive segments [seg_start[s], seg_start[s + 1]) and
+ *     n1[s][j][g] = sum_{i in s} p_i(g) [y_ij == 1]    n0[s][j][g] = sum_{i in s} p_i(g) [y_ij == 0]    mass[s][g] = sum_{i in s} p_i(g)
+ * An empty segment (equal neighbours in seg_start) gets zeros.  Response bytes as vx_grid_counts; a person with no response adds
+ * exp(h[i][g] - lognorm[i]), their conditioned prior, to the mass of their segment.
+ * seg_start is HOST memory, int64 [n_seg + 1]: the call checks it, plans the launch from it and hands the plan to the device
+ * in kernel arguments -- it is not read after the call returns, nothing is copied, allocated or waited for.  ONE launch covers
+ * all segments: a workgroup never mixes two; the chunks of a segment write slabs of their own into the workspace
+ * (vx_grid_counts_cond_workspace_floats(nb, n_seg, J, G) floats, 16-byte aligned: enough for any cut of nb into n_seg segments),
+ * which a second launch adds in ascending order.  No atomics, every sum in a fixed order: the same call gives the same bits, and a
+ * segment's tables do not depend on the other segments' persons.  With n_seg = 1 and a zero tilt the three tables are
+ * vx_grid_counts' bit for bit (logjoint = its loglik).
+ * Limits: those of vx_grid_counts, 1 <= D <= 3, 1 <= n_seg <= 4096, seg_start[0] = 0, seg_start[n_seg] = nb, seg_start
+ * non-decreasing; VX_EINVAL beyond any of them. */
+int64_t vx_grid_counts_cond_workspace_floats(int64_t nb, int32_t n_seg, int32_t J, int32_t G);
+int vx_grid_counts_cond(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J, int32_t G,
+                        int32_t D, const void* img, const float* logw /*[G]*/, const float* coord /*[G][D]*/,
+                        const float* tilt /*[nb][D]*/, const float* logjoint /*[nb]*/, const int64_t* seg_start /*HOST [n_seg + 1]*/,
+                        int32_t n_seg, float* n1 /*[n_seg][J][G]*/, float* n0 /*[n_seg][J][G]*/, float* mass /*[n_seg][G]*/,
+                        float* workspace, void* hip_stream);
+
 /* ---- The M-step of the Bock-Aitkin EM on those tables (marginal maximum likelihood of the item parameters; with the E-step of
  * vx_grid_posterior + vx_grid_counts one EM iteration).  Every item is a problem of its own; a and b / g_un and s_un are updated
  * in place, [D][J] / [J] as the table builders take them, and nothing else is written.

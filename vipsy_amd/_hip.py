@@ -133,6 +133,8 @@ SIGNATURES = {
     "vx_grid_draw_cond": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 4 + [_U64, _I64, _I32, _I32, _I64, _P, _P]),
     "vx_grid_counts_workspace_floats": (_I64, [_I64, _I32, _I32]),
     "vx_grid_counts": (ctypes.c_int, [_P, _P, _I64, _I32, _I32] + [_P] * 3 + [_P] * 3 + [_P, _P]),
+    "vx_grid_counts_cond_workspace_floats": (_I64, [_I64, _I32, _I32, _I32]),
+    "vx_grid_counts_cond": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 5 + [_P, _I32] + [_P] * 3 + [_P, _P]),
     "vx_grid_mstep_irt": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 3 + [_P, _P, _I32, _P]),
     "vx_grid_mstep_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32] + [_P] * 3 + [_P, _P, _P]),
     "vx_grid_wimage_bytes": (_I64, [_I32, _I32]),

@@ -38,6 +38,7 @@
 #include "k_grid_pairs.hip"
 #include "k_grid_fit.hip"
 #include "k_grid_cond.hip"
+#include "k_grid_counts_cond.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2313,6 +2314,69 @@ int vx_grid_counts(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J,
     for (int k = 0; k < 3; ++k) {
         hipLaunchKernelGGL(k_reduce_slabs, dim3(grid_1d(lens[k], 64)), dim3(256), 0, st, workspace + offs[k], p.n_chunks,
                            p.slab_len, lens[k], 1.0f, outs[k]);
+        VX_CHECK_LAUNCH();
+    }
+    return VX_OK;
+}
+
+// Expected counts under a tilt a person, a table set a segment (k_grid_counts_cond.hip): the plan's table into the head of the
+// workspace (from kernel arguments), one kernel over (the chunks of all segments x node groups), then every segment's slabs added
+// in ascending order.  seg_start is HOST memory: it is checked and planned from here, and not used after the call returns.
+int64_t vx_grid_counts_cond_workspace_floats(int64_t nb, int32_t n_seg, int32_t J, int32_t G) {
+    if (!grid_shape_ok(J, G, nb) || n_seg < 1 || n_seg > GCC_MAXSEG) return VX_EINVAL;
+    const GccPlan p = gcc_plan(nb, n_seg, J, G);
+    return p.tab_floats + p.max_chunks * p.gc.slab_len;
+}
+
+int vx_grid_counts_cond(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, int32_t D, const void* img,
+                        const float* logw, const float* coord, const float* tilt, const float* logjoint, const int64_t* seg_start,
+                        int32_t n_seg, float* n1, float* n0, float* mass, float* workspace, void* hs) {
+    if (!y || !img || !aligned16(img) || !logw || !coord || !tilt || !logjoint || !seg_start || !n1 || !n0 || !mass || !workspace ||
+        !aligned16(workspace))
+        return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb) || D < 1 || D > GPC_MAXD || n_seg < 1 || n_seg > GCC_MAXSEG) return VX_EINVAL;
+    if (seg_start[0] != 0 || seg_start[n_seg] != nb) return VX_EINVAL;
+    for (int s = 0; s < n_seg; ++s)
+        if (seg_start[s + 1] < seg_start[s]) return VX_EINVAL;
+    const GccPlan p = gcc_plan(nb, n_seg, J, G);
+    // the table: [seg_start (n_seg + 1) | chunk_start (n_seg + 1)]
+    std::vector<int64_t> tab(2 * ((size_t)n_seg + 1));
+    const int64_t rpc = gcc_rounds_per_chunk(seg_start, (int)n_seg, p.gc);
+    int64_t chunks = 0;
+    for (int s = 0; s <= n_seg; ++s) {
+        tab[s] = seg_start[s];
+        tab[(size_t)n_seg + 1 + s] = chunks;
+        if (s < n_seg) chunks += gcc_chunks(seg_start[s + 1] - seg_start[s], rpc);
+    }
+    if (chunks < 1 || chunks > p.max_chunks) return VX_EINVAL;                      // (cannot happen: gcc_plan's bound)
+    hipStream_t st = (hipStream_t)hs;
+    int64_t* dtab = (int64_t*)workspace;
+    for (size_t o = 0; o < tab.size(); o += GCC_TAB_VALUES) {
+        GccTabArgs a;
+        const int n = (int)(tab.size() - o < GCC_TAB_VALUES ? tab.size() - o : GCC_TAB_VALUES);
+        for (int i = 0; i < GCC_TAB_VALUES; ++i) a.v[i] = i < n ? tab[o + i] : 0;
+        hipLaunchKernelGGL(k_gcc_table, dim3(1), dim3(GCC_TAB_VALUES), 0, st, a, n, dtab + o);
+        VX_CHECK_LAUNCH();
+    }
+    float* slabs = workspace + p.tab_floats;
+    const uint4* im = (const uint4*)img;
+    const dim3 grid((unsigned)(p.gc.n_groups * chunks));
+    int rc;
+#define LAUNCH_GCC(ITV, NTGV)                                                                                         \
+    rc = set_lds(k_grid_counts_cond<ITV, NTGV>, gcc_lds_bytes<NTGV>());                                               \
+    if (rc) return rc;                                                                                                \
+    hipLaunchKernelGGL((k_grid_counts_cond<ITV, NTGV>), grid, dim3(GC_THREADS), gcc_lds_bytes<NTGV>(), st, y, rows, (int)J, (int)G, \
+                       (int)D, im, logw, coord, tilt, logjoint, (const int64_t*)dtab, (int)n_seg, p.gc.n_groups, slabs, \
+                       p.gc.slab_len)
+    if (p.gc.it == 1) { LAUNCH_GCC(1, 2); } else if (p.gc.it == 2) { LAUNCH_GCC(2, 2); } else { LAUNCH_GCC(4, 1); }
+#undef LAUNCH_GCC
+    VX_CHECK_LAUNCH();
+    const int64_t JG = (int64_t)J * G;
+    float* const outs[3] = {n1, n0, mass};
+    const int64_t offs[3] = {0, JG, 2 * JG}, lens[3] = {JG, JG, (int64_t)G};
+    for (int k = 0; k < 3; ++k) {
+        hipLaunchKernelGGL(k_reduce_segments, dim3(grid_1d(lens[k], 64), (unsigned)n_seg), dim3(256), 0, st, slabs + offs[k],
+                           (const int64_t*)dtab, (int)n_seg, p.gc.slab_len, lens[k], outs[k]);
         VX_CHECK_LAUNCH();
     }
     return VX_OK;

@@ -251,6 +251,17 @@ class HipBackend(object):
                                    _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(mass), _hip.ptr(ws), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_counts")
 
+    def grid_counts_cond_workspace(self, nb, n_seg, J, G):
+        return self._size("vx_grid_counts_cond_workspace_floats", nb, n_seg, J, G)
+
+    def grid_counts_cond(self, y, rows, nb, J, G, D, img, logw, coord, tilt, logjoint, seg_start, n1, n0, mass, ws):
+        """seg_start: int64 numpy [n_seg + 1] on the HOST (the entry checks it and plans the launch from it)."""
+        seg = np.ascontiguousarray(seg_start, dtype=np.int64)
+        rc = self.L.vx_grid_counts_cond(_hip.ptr(y), _hip.ptr(rows), nb, J, G, D, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord),
+                                        _hip.ptr(tilt), _hip.ptr(logjoint), seg.ctypes.data_as(ctypes.c_void_p), int(seg.size) - 1,
+                                        _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(mass), _hip.ptr(ws), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_counts_cond")
+
     def grid_mstep_irt(self, cfg, theta, G, n1, n0, a_free, a, b, newton):
         rc = self.L.vx_grid_mstep_irt(ctypes.byref(cfg), _hip.ptr(theta), G, _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(a_free),
                                       _hip.ptr(a), _hip.ptr(b), int(newton), _hip.stream_ptr())
@@ -674,6 +685,7 @@ class _EngineBase(object):
     fit_population = _no_grid
     residual_sums = local_dependence = _no_grid
     fit_sums = person_fit = item_msq = _no_grid
+    group_counts = dif = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1661,7 +1673,7 @@ class IrtEngine(GridMixin, _EngineBase):
         self.population = {"gamma": out["gamma"], "sigma": out["sigma"], "intercept": bool(intercept)}
         return out
 
-    def _grid_call(self, y_u8, rows, nodes, span, params=None):
+    def _grid_call(self, y_u8, rows, nodes=61, span=6.0, params=None):
         """The GridCall of score() and its kin.  params: the tensors to tabulate, compact (a [D_model][J_items] or None, b, c_un,
         d_un [J_items] or None) -- by default the leaves as they stand, the problem's own items."""
         if self.D_model > SCORE_MAX_DIMS:
@@ -1700,15 +1712,80 @@ class IrtEngine(GridMixin, _EngineBase):
         node, theta = self._grid_draws(self._grid_call(y_u8, rows, nodes, span), draws, seed, self.gid0 if y_u8 is None else 0)
         return {"theta": theta, "node": node}
 
-    def expected_counts(self, y_u8=None, rows=None, nodes=61, span=6.0):
+    def expected_counts(self, y_u8=None, rows=None, nodes=61, span=6.0, covariates=None):
         """The expected-count tables of the scored rows over the grid of score() (the Bock-Aitkin E-step): `n1`, `n0` [J][G] =
         the posterior mass at node g of the persons who answered item j correctly / wrongly, `mass` [G] = the posterior mass
         of all scored persons, `prob` [J][G] = P(y_j = 1 | node g) as the tables hold it, `theta` [G][D] and `logw` [G].
-        Inputs and refusals as score(); the model's own items only.  Deterministic: the same call gives the same bits."""
-        call = self._grid_call(y_u8, rows, nodes, span)
-        out = self._grid_counts(call)
+        Inputs and refusals as score(); the model's own items only.  Deterministic: the same call gives the same bits.
+        covariates (as score() takes them): the tables under each person's own prior N(Gamma^T x_i, Sigma) of the population
+        fit_population() estimated (vx_grid_posterior_cond, vx_grid_counts_cond with one segment); `logw` is then that
+        population's shared log-weight.  Without them nothing changes, bits included."""
+        if covariates is not None:
+            call, tilt, _ = self._population_call(y_u8, rows, nodes, span, covariates)
+            out = self._grid_counts_cond(call, tilt, np.array([0, call.n], np.int64))
+            out["n1"], out["n0"], out["mass"] = out["n1"][0], out["n0"][0], out["mass"][0]
+        else:
+            call = self._grid_call(y_u8, rows, nodes, span)
+            out = self._grid_counts(call)
         out["theta"], out["logw"] = call.theta, call.logw
         return out
+
+    def _group_refusals(self, covariates, impact):
+        if impact is not None and not isinstance(impact, (bool, np.bool_)):
+            raise ValueError("impact must be True, False or None")
+        if covariates is not None and impact:
+            raise ValueError("covariates= scores under engine.population as it stands; impact must then be None or False")
+        if covariates is not None and self.population is None:
+            raise ValueError("covariates need a fitted population: call fit_population() first")
+
+    def _group_prior(self, call, seg_start, covariates, impact, nodes=61, span=6.0):
+        """The prior of GridMixin.dif / group_counts for a call whose rows are sorted by group (seg_start): (the call under that
+        prior's log-weights, the tilt [n][D] by batch position or None for N(0, I), group_mean [H][D], sigma [D][D])."""
+        H, D, n = len(seg_start) - 1, call.D, call.n
+        counts = np.diff(seg_start)
+        if covariates is not None:
+            cond, tilt, mu = self._population_call(call.y, call.rows, nodes, span, covariates)
+            mu = mu.cpu().numpy().astype(np.float64)
+            return cond, tilt, np.add.reduceat(mu, seg_start[:-1], axis=0) / counts[:, None], np.array(self.population["sigma"])
+        if impact is not None and not impact:
+            return call, None, np.zeros((H, D)), np.eye(D)
+        if isinstance(nodes, (tuple, list)):
+            raise ValueError("dif(impact=True) takes `nodes` points a dimension: the fitted population sets the log-weights")
+        if n < H + D + 1:
+            raise ValueError("dif(impact=True) fits %d group means and Sigma: it needs at least %d persons (got %d)"
+                             % (H, H + D + 1, n))
+        gidx = torch.from_numpy(np.repeat(np.arange(H), counts)).to(self.dev)
+        X = torch.zeros(n, H, dtype=torch.float64, device=self.dev)              # the intercept and a dummy for every label but the first
+        X[torch.arange(n, device=self.dev), gidx] = 1.0
+        X[:, 0] = 1.0
+        fit = self._population_em(call, X, design_cholesky(X), 2.0 * float(span) / (int(nodes) - 1), float(span), 200, 1e-7, False)
+        gamma, sigma = fit["gamma"], fit["sigma"]
+        group_mean = gamma.copy()
+        group_mean[1:] += gamma[0]
+        lam = torch.from_numpy(np.linalg.inv(sigma)).to(self.dev)
+        tilt = (torch.from_numpy(group_mean).to(self.dev)[gidx] @ lam).to(torch.float32).contiguous()
+        logw = torch.from_numpy(population_logw(call.theta.cpu().numpy(), sigma)).to(self.dev)
+        return call._replace(logw=logw), tilt, group_mean, sigma
+
+    def _group_refit_check(self):
+        if self.model not in ("irt_1pl", "irt_2pl"):
+            raise NotImplementedError("dif(refit=True) for %s: with a guessing or slipping asymptote the M-step is not concave and "
+                                      "wants priors on the items; only irt_1pl and irt_2pl have it" % self.model)
+
+    def _group_refit(self, call, n1, n0, newton):
+        """Every group's items from the pooled values by `newton` steps of vx_grid_mstep_irt on that group's tables."""
+        two = self.model != "irt_1pl"
+        H = int(n1.shape[0])
+        b0 = self.unconstrained("b").reshape(-1).contiguous()
+        b_g = b0[None, :].repeat(H, 1)
+        a0 = self.unconstrained("a").contiguous() if two else torch.ones(self.D_model, self.J_items, device=self.dev)
+        a_g = a0[None].repeat(H, 1, 1)
+        free = self.unconstrained("a", self.free).contiguous().clone() if two else None
+        for h in range(H):
+            self.be.grid_mstep_irt(call.cfg, call.theta, call.G, n1[h], n0[h], free, a_g[h] if two else None, b_g[h], newton)
+        b_np = b_g.cpu().numpy().astype(np.float64)
+        return {"b_group": b_np, "a_group": a_g.cpu().numpy().astype(np.float64),
+                "delta_b": b_np - b0.cpu().numpy().astype(np.float64)[None, :]}
 
     def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, nodes=61, span=6.0):
         """Marginal maximum likelihood of a and b by Bock-Aitkin EM over the grid of score(): each iteration scores the training
@@ -2182,6 +2259,20 @@ class CcdmEngine(GridMixin, _EngineBase):
         out = self._grid_counts(call)
         out["patterns"] = call.theta
         return out
+
+    def _group_refusals(self, covariates, impact):
+        if covariates is not None or impact:
+            raise NotImplementedError("dif with impact=True or covariates= on %s: there is no latent regression for attribute "
+                                      "patterns (fit_population); the groups are scored under the uniform pattern prior"
+                                      % type(self).__name__)
+
+    def _group_prior(self, call, seg_start, covariates, impact):
+        """GridMixin.dif / group_counts score every group under the uniform pattern prior: the zero tilt."""
+        return call, None, None, None
+
+    def _group_refit_check(self):
+        raise NotImplementedError("dif(refit=True) on %s: the group refit is the Newton M-step of irt_1pl / irt_2pl "
+                                  "(vx_grid_mstep_irt); only IrtEngine has it" % type(self).__name__)
 
     def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False):
         """Marginal maximum likelihood of g and s by EM over the 2^K patterns (IrtEngine.fit_em): the E-step of

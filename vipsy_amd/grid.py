@@ -1,7 +1,8 @@
 """The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide.  On IrtEngine (x_feature <= 3)
 and CcdmEngine: score(), expected_counts() / item_fit(), fit_em(), plausible_values(), item_information() / item_se(),
-residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq() and marginal_loglik().  On IrtEngine alone:
-fit_population(), the latent regression, and the score() / plausible_values() conditioned on it (covariates=).  All of it runs
+residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq(), group_counts() / dif() and marginal_loglik().  On
+IrtEngine alone: fit_population(), the latent regression, and the score() / plausible_values() / expected_counts() conditioned on
+it (covariates=).  All of it runs
 on the vx_grid_* entries of the C ABI (k_grid_*.hip; no reference counterpart) and works in buffers of its own: nothing a step
 reads is touched."""
 from collections import namedtuple
@@ -150,13 +151,57 @@ def item_fit_stats(n1, n0, prob):
     n = n1 + n0
     pos = n > 0
     zero = torch.zeros_like(n)
-    n_obs = torch.where(pos, n, zero).sum(1)
+    n_obs = torch.where(pos, n, zero).sum(-1)
     safe = torch.where(pos, n, torch.ones_like(n))
     resid = torch.where(pos, n1 - n * prob, zero)
-    md = resid.sum(1) / n_obs                                                 # 0 / 0 = NaN: nobody answered
-    rmsd = torch.sqrt((resid * resid / safe).sum(1) / n_obs)
+    md = resid.sum(-1) / n_obs                                                # 0 / 0 = NaN: nobody answered
+    rmsd = torch.sqrt((resid * resid / safe).sum(-1) / n_obs)
     observed = torch.where(pos, n1 / safe, torch.full_like(n, float("nan")))
     return {"n_obs": n_obs, "md": md, "rmsd": rmsd, "observed": observed}
+
+
+DIF_MAX_GROUPS = 4096            # GCC_MAXSEG (vipsy_amd/csrc/k_grid_counts_cond.hip): segments of a vx_grid_counts_cond call
+
+
+def group_labels(groups, n):
+    """The groups of dif(): `groups`, one integer label a person ([n]; numpy, torch, or a list), -> (labels [H] as np.unique sorts
+    them, order int64 [n]: the persons sorted by label, stably, and seg_start int64 [H + 1]: group h holds the batch positions
+    seg_start[h] .. seg_start[h + 1] of that order).  ValueError for labels that are not integers, a wrong length, fewer than two
+    groups or more than DIF_MAX_GROUPS."""
+    g = groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)
+    if g.dtype.kind not in "iu":
+        raise ValueError("groups must be integer labels, one a person (got dtype %s)" % g.dtype)
+    g = g.reshape(-1)
+    if g.shape[0] != n:
+        raise ValueError("groups has %d labels, the scored rows are %d" % (g.shape[0], n))
+    labels, inv = np.unique(g, return_inverse=True)
+    H = int(labels.shape[0])
+    if not 2 <= H <= DIF_MAX_GROUPS:
+        raise ValueError("dif needs 2 .. %d groups (got %d)" % (DIF_MAX_GROUPS, H))
+    inv = inv.reshape(-1)
+    order = np.argsort(inv, kind="stable").astype(np.int64)
+    seg_start = np.concatenate([np.zeros(1, np.int64), np.cumsum(np.bincount(inv, minlength=H)).astype(np.int64)])
+    return labels, order, seg_start
+
+
+def group_fit_stats(n1, n0, prob, min_obs=8):
+    """item_fit_stats a group: n1, n0 [H][J][G] against the pooled prob [J][G] -> `n_obs`, `md`, `rmsd` [H][J] and `observed`
+    [H][J][G], float64 on the tables' device; md and rmsd NaN where fewer than min_obs persons of the group answered the item."""
+    s = item_fit_stats(n1, n0, prob)
+    few = torch.round(s["n_obs"]) < min_obs
+    nan = torch.full_like(s["md"], float("nan"))
+    s["md"], s["rmsd"] = torch.where(few, nan, s["md"]), torch.where(few, nan, s["rmsd"])
+    return s
+
+
+def group_fit_top(rmsd, top=20):
+    """The `top` finite cells of rmsd [H][J] by descending value (ties: the lower cell first), as `group` (the index into labels),
+    `item` (int64) and `value`."""
+    rmsd = np.asarray(rmsd, np.float64)
+    flat = rmsd.reshape(-1)
+    fin = np.flatnonzero(np.isfinite(flat))
+    sel = fin[np.argsort(-flat[fin], kind="stable")[:top]]
+    return {"group": (sel // rmsd.shape[1]).astype(np.int64), "item": (sel % rmsd.shape[1]).astype(np.int64), "value": flat[sel]}
 
 
 def item_se_host(info, gradient, free, names=None):
@@ -536,6 +581,94 @@ class GridMixin(object):
         ws = torch.empty(be.grid_counts_workspace(call.n, J, G), **f32)
         be.grid_counts(call.y, call.rows, call.n, J, G, post["img"], call.logw, post["loglik"], out["n1"], out["n0"], out["mass"], ws)
         out["prob"] = grid_image_prob(post["img"], J, G)
+        return out
+
+    def _grid_counts_cond(self, call, tilt, seg_start):
+        """The counts of `call` under call.logw and a tilt a person ([n][D] float32 by batch position), a table set a segment of
+        the batch positions (seg_start: int64 numpy [S + 1] on the host): the conditioned posterior kernel for logjoint, then
+        vx_grid_counts_cond over the same image -- n1, n0 [S][J][G], mass [S][G] and prob [J][G].  tilt None: the zero tilt, with
+        the unconditioned posterior kernel's loglik as the normaliser (the same bits) and one zero coordinate a node, which
+        also serves nodes of more than three dimensions (the patterns of CcdmEngine)."""
+        be, J, G, n = self.be, call.J, call.G, call.n
+        S = int(len(seg_start)) - 1
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        if tilt is None:
+            post = self._grid_posterior(call)
+            D, coord, tilt, logjoint = 1, torch.zeros(G, 1, **f32), torch.zeros(n, 1, **f32), post["loglik"]
+        else:
+            post = self._grid_posterior_cond(call, tilt)
+            D, coord, logjoint = call.D, call.theta, post["logjoint"]
+        out = {"n1": torch.empty(S, J, G, **f32), "n0": torch.empty(S, J, G, **f32), "mass": torch.empty(S, G, **f32)}
+        ws = torch.empty(be.grid_counts_cond_workspace(n, S, J, G), **f32)
+        be.grid_counts_cond(call.y, call.rows, n, J, G, D, post["img"], call.logw, coord, tilt, logjoint, seg_start, out["n1"],
+                            out["n0"], out["mass"], ws)
+        out["prob"] = grid_image_prob(post["img"], J, G)
+        return out
+
+    def _group_counts(self, groups, y_u8, covariates, impact, **grid_kw):
+        """What group_counts() and dif() share: the persons sorted by label, the prior each is scored under (_group_prior, the
+        engine's own) and the grouped tables of ONE vx_grid_counts_cond launch.  Returns (tables, call, labels, seg_start)."""
+        self._one_rank_only("dif / group_counts over a process group: the tables are the sums over the local shard's persons and "
+                            "the cross-rank sum is not built")
+        self._group_refusals(covariates, impact)
+        call = self._grid_call(y_u8, None, **grid_kw)
+        labels, order, seg_start = group_labels(groups, call.n)
+        call = call._replace(rows=torch.from_numpy(order).to(self.dev))
+        call, tilt, group_mean, sigma = self._group_prior(call, seg_start, covariates, impact, **grid_kw)
+        out = self._grid_counts_cond(call, tilt, seg_start)
+        if group_mean is not None:
+            out["group_mean"], out["sigma"] = group_mean, sigma
+        return out, call, labels, seg_start
+
+    def group_counts(self, groups, y_u8=None, covariates=None, impact=None, **grid_kw):
+        """The tables behind dif(), as device tensors: `n1`, `n0` [H][J][G] and `mass` [H][G], the expected counts of every group
+        of persons (`groups`: one integer label a person; H = the distinct labels, `labels`, sorted) under the prior dif()
+        describes for `impact` / `covariates`, beside `prob` [J][G], `n_group` (int64 [H], the persons of each group) and, for
+        IrtEngine, `group_mean` [H][D] and `sigma` [D][D] (numpy).  One launch over all groups.  Deterministic: the same call
+        gives the same bits, and a group's tables do not depend on the other groups' persons (under impact=True the prior does:
+        Sigma is shared).  Refusals as dif()."""
+        out, _, labels, seg_start = self._group_counts(groups, y_u8, covariates, impact, **grid_kw)
+        out["labels"], out["n_group"] = labels, np.diff(seg_start)
+        return out
+
+    def dif(self, groups, y_u8=None, covariates=None, impact=None, min_obs=8, top=20, refit=False, newton=8, **grid_kw):
+        """Differential item functioning as the item-by-group fit of the large-scale assessments: for every group of persons
+        (`groups`: one integer label a person of the scored rows; `labels` = np.unique of them, H = 2 .. 4096 groups) the RMSD
+        and MD of the group's observed item characteristic curve -- from the group's own expected counts -- against the POOLED
+        fitted curve `prob` under the item parameters as they stand.  Nothing of the engine changes.
+        The prior a person is scored under decides what the statistic means:
+          impact=True (IrtEngine's default) fits a private latent regression on group dummies first (reference: the first
+            label; one shared Sigma; the EM of fit_population with its refusals, 200 iterations at most, not kept in
+            engine.population), so that a group whose ability differs is scored around its own mean;
+          covariates=x scores under engine.population as it stands (fit_population()); impact must then be None or False;
+          impact=False scores everybody under N(0, I) (CcdmEngine: the uniform pattern prior, its only setting).  A group
+            whose mean is off centre is then shrunk towards 0 and its observed curve is bent on EVERY item: this setting reads
+            impact as DIF.
+        Returns numpy: `labels` [H], `n_group` [H], `rmsd`, `md` float64 [H][J] (item_fit_stats a group; NaN where fewer than
+        min_obs persons of the group answered the item), `n_obs` int64 [H][J], `observed` [H][J][G], `prob` [J][G], `mass`
+        [H][G], `group_mean` [H][D] and `sigma` [D][D] (IrtEngine; zeros and I for impact=False), and `group` (index into
+        labels), `item`, `value`: the `top` cells by descending rmsd.
+        refit=True (irt_1pl / irt_2pl): every group's items refitted to that group's tables from the pooled values -- `newton`
+        steps of fit_em's M-step (vx_grid_mstep_irt), one call a group, under the engine's free mask -- as `b_group` [H][J],
+        `a_group` [H][D][J] and `delta_b` = b_group - b.  No test statistic is attached: expected counts are not data, and a
+        standard error computed from them as if they were would be too small.
+        Inputs and grid as score(); one rank only."""
+        min_obs = self._int_in("min_obs", min_obs, 1)
+        top = self._int_in("top", top, 0)
+        if refit:
+            self._int_in("newton", newton, 1, EM_MAX_NEWTON,
+                         "in 1 .. %d (Newton steps of an item inside one M-step launch)" % EM_MAX_NEWTON)
+            self._group_refit_check()
+        c, call, labels, seg_start = self._group_counts(groups, y_u8, covariates, impact, **grid_kw)
+        s = group_fit_stats(c["n1"], c["n0"], c["prob"], min_obs)
+        out = {"labels": labels, "n_group": np.diff(seg_start), "rmsd": s["rmsd"].cpu().numpy(), "md": s["md"].cpu().numpy(),
+               "n_obs": np.rint(s["n_obs"].cpu().numpy()).astype(np.int64), "observed": s["observed"].cpu().numpy(),
+               "prob": c["prob"].cpu().numpy(), "mass": c["mass"].cpu().numpy()}
+        if "group_mean" in c:
+            out["group_mean"], out["sigma"] = c["group_mean"], c["sigma"]
+        out.update(group_fit_top(out["rmsd"], top))
+        if refit:
+            out.update(self._group_refit(call, c["n1"], c["n0"], newton))
         return out
 
     def _em_loop(self, call, mstep, leaves, max_iter, tol, progress):

@@ -236,7 +236,9 @@ class BasePsy(object):
         """The expected-count tables of the persons in `data` (None: the training data) over the grid of score(): device
         tensors n1, n0 [items][nodes], mass [nodes], prob [items][nodes], and theta / logw (IRT) or patterns (VCCDM); see
         IrtEngine.expected_counts / CcdmEngine.expected_counts.  With a `group` of more than one rank these are the sums over
-        THIS rank's shard only: add them across ranks yourself.  The classes without score() refuse."""
+        THIS rank's shard only: add them across ranks yourself.  The classes without score() refuse.
+        covariates=x (VIRT / VaeIRT, as score() takes them): the tables under each person's own prior of the population
+        fit_population() estimated, instead of N(0, I); item_fit() takes it too."""
         return self.engine.expected_counts(self._score_data(data), **kw)
 
     def item_fit(self, data=None, **kw):
@@ -247,6 +249,38 @@ class BasePsy(object):
             raise NotImplementedError("item_fit with a group of %d ranks: expected_counts() gives the local shard's sums; the "
                                       "cross-rank sum is not built" % self.world)
         return {k: v.detach().cpu().numpy() for k, v in self.engine.item_fit(self._score_data(data), **kw).items()}
+
+    def group_counts(self, groups, data=None, **kw):
+        """The grouped expected-count tables behind dif(), as device tensors: n1, n0 [groups][items][nodes] and mass
+        [groups][nodes], one launch over all groups, beside prob, labels, n_group and (IRT) group_mean, sigma
+        (GridMixin.group_counts; kw: covariates, impact, nodes, span).  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("group_counts with a group of %d ranks: the tables are the sums over the local shard's "
+                                      "persons; the cross-rank sum is not built" % self.world)
+        return self.engine.group_counts(groups, self._score_data(data), **kw)
+
+    def dif(self, groups, data=None, covariates=None, impact=None, min_obs=8, top=20, refit=False, newton=8, **grid_kw):
+        """Differential item functioning, ready to print: does an item work the same way in every group (country, language,
+        booklet)?  `groups`: one integer label a person of `data` (None: the training data).  For every (group, item) cell the
+        RMSD and MD of the group's observed item characteristic curve against the pooled fitted curve under the item parameters
+        as they stand -- the item-by-group fit of PISA and PIAAC -- from ONE launch over all groups.  A dict of numpy arrays:
+        labels, n_group [groups], rmsd, md, n_obs [groups][items] (NaN where fewer than min_obs persons of a group answered an
+        item), observed [groups][items][nodes], prob [items][nodes], mass [groups][nodes], group_mean, sigma, and group, item,
+        value: the `top` cells by rmsd (GridMixin.dif).
+        Each person is scored under a prior: impact=True (the default of VIRT / VaeIRT) first fits every group's mean and a
+        shared Sigma by a private latent regression on group dummies, so that a difference in ABILITY between the groups
+        (impact) is not read as DIF; covariates=x uses the population fit_population() left on the engine instead; impact=False
+        keeps N(0, I) for everybody, which bends the observed curve of every item of a group whose mean is off centre.  VCCDM
+        has the uniform pattern prior only: impact=True, covariates= and refit=True are refused there.
+        refit=True (irt_1pl / irt_2pl): also b_group, a_group and delta_b, every group's items refitted to its own tables by
+        `newton` steps of fit_em's M-step; no test statistic is attached, since expected counts are not data.
+        VIRT / VaeIRT with x_feature <= 3 (grid_kw: nodes, span), VCCDM; the other classes refuse.  Nothing of the model
+        changes.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("dif with a group of %d ranks: the tables are the sums over the local shard's persons; the "
+                                      "cross-rank sum is not built" % self.world)
+        return self.engine.dif(groups, self._score_data(data), covariates=covariates, impact=impact, min_obs=min_obs, top=top,
+                               refit=refit, newton=newton, **grid_kw)
 
     def marginal_loglik(self, data=None, **kw):
         """The marginal log-likelihood of `data` (None: the training data), a Python float.  One rank only."""
