@@ -626,6 +626,33 @@ int vx_grid_fit_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K]
                     const float* s_un, float* person /*[7][nb]*/, float* item /*[4][J]*/, float* workspace, int64_t ws_floats,
                     void* hip_stream);
 
+/* ---- Summed-score tables (k_sumscore.hip): the model side of Orlando & Thissen's S-X2 item fit and of the score -> latent
+ * conversion table, by the Lord-Wingersky recursion, and the observed side, over a list of Js items.
+ * vx_sumscore_model: p1, p0 [Js][G] = P(y_j = 1 | node g) and P(y_j = 0 | node g) of the listed items (both given; p0 is never
+ *   formed as 1 - p1), w_g = exp(logw[g]).  With S(s | g) the probability of the summed score s at node g -- S = delta_0, then for
+ *   every item in ascending order S'[s] = p0 S[s] + p1 S[s - 1] -- and S_-j the same without item j:
+ *     e1[j][s] = sum_g w_g p1[j][g] S_-j(s - 1 | g)   e0[j][s] = sum_g w_g p0[j][g] S_-j(s | g)     float32 [Js][Js + 1]
+ *     dist[g][s] = S(s | g) over all Js items, float32 [G][Js + 1]; NULL: not computed.
+ *   e1[j][0], e0[j][Js] and every entry above the number of folded items are exact zeros; e1[j][s] + e0[j][s] = P(score = s).
+ *   workspace: vx_sumscore_model_workspace_floats(Js, G) floats, the slabs of the node chunks, added in ascending order
+ *   (vx_reduce_slabs).  The chunking depends on Js and G alone, there is no atomic: the same call gives the same bits.
+ * vx_sumscore_persons: score[i] = the number of 1s of person rows[i] (rows NULL: i) over the listed columns of y (items[k], int32,
+ *   ascending; NULL: the first Js columns), or -1 unless every listed cell is 0 or 1 (255 and 254 take the person out).
+ * vx_sumscore_observed: o1[k][s] = the persons i with score[i] = s and y[rows[i]][items[k]] = 1, int32 [Js][Js + 1], zeroed by
+ *   the entry; rows and score [nb] are the complete persons, best sorted by score (the counts are right in any order; integer
+ *   atomics, the same bits in any order).  A score outside 0 .. Js counts nothing.
+ * Limits: 1 <= Js <= 1023, 1 <= G <= 1024, Js <= J <= 4096, nb >= 0 (vx_sumscore_model_workspace_floats: -1 beyond);
+ * VX_EINVAL beyond, before anything is read. */
+int64_t vx_sumscore_model_workspace_floats(int32_t Js, int32_t G);
+int vx_sumscore_model(const float* p1 /*[Js][G]*/, const float* p0 /*[Js][G]*/, const float* logw /*[G]*/, int32_t Js, int32_t G,
+                      float* e1 /*[Js][Js + 1]*/, float* e0 /*[Js][Js + 1]*/, float* dist /*[G][Js + 1] or NULL*/,
+                      float* workspace, int64_t ws_floats, void* hip_stream);
+int vx_sumscore_persons(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J,
+                        const int32_t* items /*[Js] or NULL*/, int32_t Js, int32_t* score /*[nb]*/, void* hip_stream);
+int vx_sumscore_observed(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb]*/, int64_t nb, int32_t J,
+                         const int32_t* items /*[Js] or NULL*/, int32_t Js, const int32_t* score /*[nb]*/,
+                         int32_t* o1 /*[Js][Js + 1]*/, void* hip_stream);
+
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,
                     void* hip_stream);

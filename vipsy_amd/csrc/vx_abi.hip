@@ -39,6 +39,7 @@
 #include "k_grid_fit.hip"
 #include "k_grid_cond.hip"
 #include "k_grid_counts_cond.hip"
+#include "k_sumscore.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2632,6 +2633,84 @@ int vx_grid_fit_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, cons
     hipLaunchKernelGGL(k_fit_cdm, dim3((unsigned)p.n_blocks), dim3(256), 0, (hipStream_t)hs, y, rows, nb, K, J, (int)dino, q, pattern, g_un,
                        s_un, person, workspace, p.n_units, p.units_per_block);
     return grid_fit_finish(p, J, workspace, item, hs);
+}
+
+// Summed-score tables (k_sumscore.hip): the Lord-Wingersky recursion behind S-X2 and the score table, and the observed tables
+static bool sumscore_shape_ok(int32_t Js, int32_t G) { return Js >= 1 && Js <= SS_MAXJ && G >= 1 && G <= SS_MAXG; }
+static bool sumscore_data_ok(int64_t nb, int32_t J, int32_t Js) {
+    return nb >= 0 && nb <= ((int64_t)1 << 40) && J >= 1 && J <= SS_MAXJ_ALL && Js >= 1 && Js <= SS_MAXJ && Js <= J;
+}
+
+int64_t vx_sumscore_model_workspace_floats(int32_t Js, int32_t G) {
+    if (!sumscore_shape_ok(Js, G)) return VX_EINVAL;
+    return ss_ws_floats(Js, G);
+}
+
+static void sumscore_launch(bool leave, const SsPlan& p, int n_waves, hipStream_t st, const float* p1, const float* p0, const float* logw,
+                            int Js, int G, float* out1, float* out0) {
+    const dim3 grid((unsigned)((n_waves + SS_WAVES - 1) / SS_WAVES)), block(64 * SS_WAVES);
+#define LAUNCH_SS(R)                                                                                                             \
+    do {                                                                                                                         \
+        if (leave) hipLaunchKernelGGL((k_sumscore<R, true>), grid, block, 0, st, p1, p0, logw, Js, G, p.chunk, p.n_chunks, out1, out0); \
+        else hipLaunchKernelGGL((k_sumscore<R, false>), grid, block, 0, st, p1, p0, logw, Js, G, p.chunk, p.n_chunks, out1, out0);      \
+    } while (0)
+    if (p.R == 1) { LAUNCH_SS(1); } else if (p.R == 2) { LAUNCH_SS(2); } else if (p.R == 4) { LAUNCH_SS(4); }
+    else if (p.R == 8) { LAUNCH_SS(8); } else { LAUNCH_SS(16); }
+#undef LAUNCH_SS
+}
+
+int vx_sumscore_model(const float* p1, const float* p0, const float* logw, int32_t Js, int32_t G, float* e1, float* e0, float* dist,
+                      float* workspace, int64_t ws_floats, void* hs) {
+    if (!sumscore_shape_ok(Js, G) || !p1 || !p0 || !logw || !e1 || !e0 || !workspace) return VX_EINVAL;
+    if (ws_floats < ss_ws_floats(Js, G)) return VX_EINVAL;
+    hipStream_t st = (hipStream_t)hs;
+    const SsPlan p = ss_plan(Js, G);
+    const int64_t len = (int64_t)Js * (Js + 1);
+    float* slabs1 = workspace;
+    float* slabs0 = workspace + p.n_chunks * len;
+    sumscore_launch(true, p, Js * p.n_chunks, st, p1, p0, logw, Js, G, slabs1, slabs0);
+    VX_CHECK_LAUNCH();
+    int rc = vx_reduce_slabs(slabs1, p.n_chunks, len, 1.0f, e1, hs);
+    if (rc) return rc;
+    rc = vx_reduce_slabs(slabs0, p.n_chunks, len, 1.0f, e0, hs);
+    if (rc) return rc;
+    if (dist) {
+        // nothing left out: one wave a node, so that the G vectors spread over the chip
+        SsPlan pd = p;
+        pd.chunk = 1;
+        pd.n_chunks = G;
+        sumscore_launch(false, pd, G, st, p1, p0, logw, Js, G, dist, nullptr);
+        VX_CHECK_LAUNCH();
+    }
+    return VX_OK;
+}
+
+int vx_sumscore_persons(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, const int32_t* items, int32_t Js, int32_t* score,
+                        void* hs) {
+    if (!sumscore_data_ok(nb, J, Js) || !y || !score) return VX_EINVAL;
+    if (nb == 0) return VX_OK;
+    int64_t blocks = (nb + 3) / 4;
+    const int64_t cap = (int64_t)num_cu() * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(k_sumscore_persons, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hs, y, rows, nb, (int)J, items, (int)Js, score);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_sumscore_observed(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, const int32_t* items, int32_t Js,
+                         const int32_t* score, int32_t* o1, void* hs) {
+    if (!sumscore_data_ok(nb, J, Js) || !y || !o1 || (nb > 0 && (!rows || !score))) return VX_EINVAL;
+    hipStream_t st = (hipStream_t)hs;
+    if (hipMemsetAsync(o1, 0, sizeof(int32_t) * (size_t)Js * (size_t)(Js + 1), st) != hipSuccess) return VX_EINVAL;
+    if (nb == 0) return VX_OK;
+    // chunks of at least 64 persons: the integer sums do not depend on the chunking
+    int64_t per_block = (nb + SS_OBS_MAX_BLOCKS - 1) / SS_OBS_MAX_BLOCKS;
+    if (per_block < 64) per_block = 64;
+    const int64_t blocks = (nb + per_block - 1) / per_block;
+    hipLaunchKernelGGL(k_sumscore_observed, dim3((unsigned)blocks), dim3(SS_OBS_THREADS), 0, st, y, rows, nb, (int)J, items, (int)Js,
+                       score, o1, per_block);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

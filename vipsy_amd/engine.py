@@ -352,6 +352,23 @@ class HipBackend(object):
                                     _hip.stream_ptr())
         _hip.check(rc, "vx_grid_fit_cdm")
 
+    def sumscore_model_workspace(self, Js, G):
+        return self._size("vx_sumscore_model_workspace_floats", Js, G)
+
+    def sumscore_model(self, p1, p0, logw, Js, G, e1, e0, dist, ws, ws_floats):
+        rc = self.L.vx_sumscore_model(_hip.ptr(p1), _hip.ptr(p0), _hip.ptr(logw), Js, G, _hip.ptr(e1), _hip.ptr(e0), _hip.ptr(dist),
+                                      _hip.ptr(ws), int(ws_floats), _hip.stream_ptr())
+        _hip.check(rc, "vx_sumscore_model")
+
+    def sumscore_persons(self, y, rows, nb, J, items, Js, score):
+        rc = self.L.vx_sumscore_persons(_hip.ptr(y), _hip.ptr(rows), nb, J, _hip.ptr(items), Js, _hip.ptr(score), _hip.stream_ptr())
+        _hip.check(rc, "vx_sumscore_persons")
+
+    def sumscore_observed(self, y, rows, nb, J, items, Js, score, o1):
+        rc = self.L.vx_sumscore_observed(_hip.ptr(y), _hip.ptr(rows), nb, J, _hip.ptr(items), Js, _hip.ptr(score), _hip.ptr(o1),
+                                         _hip.stream_ptr())
+        _hip.check(rc, "vx_sumscore_observed")
+
     def cdm_sf_workspace(self, cfg, nb):
         return self._size("vx_cdm_sf_workspace_floats", ctypes.byref(cfg), nb)
 
@@ -686,6 +703,7 @@ class _EngineBase(object):
     residual_sums = local_dependence = _no_grid
     fit_sums = person_fit = item_msq = _no_grid
     group_counts = dif = _no_grid
+    sumscore_tables = sx2 = score_table = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1855,6 +1873,19 @@ class IrtEngine(GridMixin, _EngineBase):
         return call, "theta_hat", "mean", lambda est, person, item, ws, ws_floats: self.be.grid_fit_irt(
             call.cfg, call.y, call.rows, call.n, est, *params, person, item, ws, ws_floats)
 
+    def _sx2_params(self, items):
+        """The free parameters of each listed item, for the df of GridMixin.sx2: b; for 2PL and up the item's free loadings; the
+        lower asymptote of 3PL / 4PL and the upper one of 4PL."""
+        k = np.ones(len(items), np.int64)
+        if self.model != "irt_1pl":
+            free = self.unconstrained("a", self.free).reshape(self.D_model, -1).cpu().numpy()
+            k += (free[:, items] != 0).sum(0)
+        return k + {"irt_3pl": 1, "irt_4pl": 2}.get(self.model, 0)
+
+    @staticmethod
+    def _score_table_leaves(out):
+        return out
+
     def _se_leaves(self, se):
         """Dense [P] -> the leaves' shapes: b (1, J) and, for 2PL, a (D, J)."""
         se = se.reshape(self.J_items, -1)
@@ -2308,6 +2339,17 @@ class CcdmEngine(GridMixin, _EngineBase):
         g, s_ = self.view("g").contiguous(), self.view("s").contiguous()
         return call, "pattern", "node", lambda est, person, item, ws, ws_floats: self.be.grid_fit_cdm(
             call.cfg, self.cdm == "dino", self.q, call.y, call.rows, call.n, est, g, s_, person, item, ws, ws_floats)
+
+    def _sx2_params(self, items):
+        """Two free parameters an item (g, s), for the df of GridMixin.sx2."""
+        return np.full(len(items), 2, np.int64)
+
+    @staticmethod
+    def _score_table_leaves(out):
+        """The nodes are the patterns with 0 / 1 coordinates: the posterior mean of a coordinate is the mastery probability."""
+        out["attr_prob"] = out.pop("eap")
+        del out["psd"]
+        return out
 
     def _se_leaves(self, se):
         """Dense [P] -> g_un, s_un (1, J) and, by the delta method, g and s on the probability scale: se x (1 - x)."""

@@ -1,6 +1,7 @@
 """The grid family: what needs a person's posterior over a fixed set of latent nodes and no guide.  On IrtEngine (x_feature <= 3)
 and CcdmEngine: score(), expected_counts() / item_fit(), fit_em(), plausible_values(), item_information() / item_se(),
-residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq(), group_counts() / dif() and marginal_loglik().  On
+residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq(), group_counts() / dif(), sumscore_tables() /
+sx2() / score_table() and marginal_loglik().  On
 IrtEngine alone: fit_population(), the latent regression, and the score() / plausible_values() / expected_counts() conditioned on
 it (covariates=).  All of it runs
 on the vx_grid_* entries of the C ABI (k_grid_*.hip; no reference counterpart) and works in buffers of its own: nothing a step
@@ -158,6 +159,127 @@ def item_fit_stats(n1, n0, prob):
     rmsd = torch.sqrt((resid * resid / safe).sum(-1) / n_obs)
     observed = torch.where(pos, n1 / safe, torch.full_like(n, float("nan")))
     return {"n_obs": n_obs, "md": md, "rmsd": rmsd, "observed": observed}
+
+
+SUMSCORE_MAX_ITEMS = 1023        # SS_MAXJ (vipsy_amd/csrc/k_sumscore.hip): a score vector of Js + 1 <= 1024 entries
+
+
+def grid_image_probs(img, J, G):
+    """(p1, p0) = P(y_j = 1 | node g) and P(y_j = 0 | node g), float32 [J][G] each, read back from the operand image as
+    grid_image_prob reads T1: the exponentials of the very T1 and T0 the kernels multiply with.  p0 comes from T0, never as
+    1 - p1."""
+    KC, NT = (J + 15) // 16, (G + 31) // 32
+    t = img.view(torch.float16).view(NT, KC, 4, 2, 32, 8).to(torch.float64)
+    out = []
+    for h in (0, 2):                                                          # [T1 head, T1 low, T0 head, T0 low]
+        tt = (t[:, :, h] + t[:, :, h + 1]) / 1024.0                           # [node tile][item chunk][item half][node][item]
+        tt = tt.permute(1, 2, 4, 0, 3).reshape(KC * 16, NT * 32)[:J, :G]
+        out.append(torch.exp(tt).to(torch.float32).contiguous())
+    return out[0], out[1]
+
+
+def chi2_sf(x, df):
+    """The upper tail of the chi-square distribution with an integer df >= 1 at x >= 0, in closed form: for even df = 2 m
+    exp(-x / 2) sum_{k < m} (x / 2)^k / k!, for odd df = 2 m + 1 erfc(sqrt(x / 2)) + sqrt(2 x / pi) exp(-x / 2) sum_{k < m} x^k /
+    (1 * 3 * .. * (2 k + 1)).  The finite sum is carried with a scale of its own (rescaled whenever a term passes 1e250) and meets
+    exp(-x / 2) in the exponent, so that a large statistic on many cells gives its tail -- 0 once that leaves float64 -- and never
+    inf * 0.  NaN for df <= 0 or an x that is negative or not finite."""
+    import math
+    x, df = float(x), int(df)
+    if df <= 0 or not math.isfinite(x) or x < 0:
+        return float("nan")
+    h = 0.5 * x
+    even = df % 2 == 0
+    term, total, scale = 1.0, (1.0 if even else 0.0), 0.0                       # sum = total * exp(scale)
+    big, log_big = 1e250, math.log(1e250)
+    for k in (range(1, df // 2) if even else range(df // 2)):
+        if even:
+            term *= h / k
+        elif k:
+            term *= x / (2 * k + 1)
+        total += term
+        if term > big:
+            term, total, scale = term / big, total / big, scale + log_big
+    if even:
+        return min(1.0, math.exp(math.log(total) + scale - h))
+    tail = math.erfc(math.sqrt(h))
+    if total > 0 and x > 0:
+        tail += math.exp(0.5 * math.log(2.0 * x / math.pi) + math.log(total) + scale - h)
+    return min(1.0, tail)
+
+
+def sx2_host(e1, e0, o1, n, n_params, min_expected=1.0):
+    """The host layer of sx2(): Orlando & Thissen's S-X2 of every listed item from the summed-score tables, in float64 numpy.
+    e1, e0 [Js][Js + 1] (the model's joint probabilities of score s with y_j = 1 / 0), o1 [Js][Js + 1] and n [Js + 1] (the
+    observed counts), n_params [Js] (the free parameters of each item).  For item j the score groups s = 1 .. Js - 1, with E_s =
+    e1 / (e1 + e0), are collapsed by ONE left-to-right sweep -- this project's own rule; other packages merge neighbours in other
+    orders, which gives the same statistic over other cells: a cell takes groups in until both its expected counts, sum n[s] E_s and sum
+    n[s] (1 - E_s) (the latter from e0, not by subtraction), reach min_expected, then closes; what remains at the right end joins
+    the last closed cell, or forms the only cell.  `sx2` = sum over the cells of (O - E)^2 / E + (O - E)^2 / (N - E), `n_cells`,
+    `df` = n_cells - n_params, `p` = chi2_sf(sx2, df) (NaN for df <= 0), beside `observed` = o1 / n and `expected` = E_s
+    [Js][Js + 1], NaN where n[s] = 0.  A cell whose expected count is 0 adds 0 where its observed count agrees and inf where not."""
+    e1, e0 = np.asarray(e1, np.float64), np.asarray(e0, np.float64)
+    o1, n = np.asarray(o1, np.float64), np.asarray(n, np.float64).reshape(-1)
+    n_params = np.asarray(n_params, np.int64).reshape(-1)
+    Js = e1.shape[0]
+    if e1.shape != (Js, Js + 1) or e0.shape != e1.shape or o1.shape != e1.shape or n.shape != (Js + 1,) or n_params.shape != (Js,):
+        raise ValueError("e1, e0 and o1 must be [Js][Js + 1], n [Js + 1] and n_params [Js]")
+    if isinstance(min_expected, bool) or not (isinstance(min_expected, (int, float, np.floating, np.integer))
+                                              and np.isfinite(min_expected) and min_expected > 0):
+        raise ValueError("min_expected must be a positive finite number")
+    tot = e1 + e0
+    safe = np.where(tot > 0, tot, 1.0)
+    E1, E0 = e1 / safe, e0 / safe                                             # (a score the model gives no mass: 0 and 0)
+
+    def term(O, E, F):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d2 = (O - E) ** 2
+            return np.where(d2 > 0, d2 / E + d2 / F, 0.0)
+
+    z = np.zeros(Js)
+    run_O, run_E, run_F = z.copy(), z.copy(), z.copy()
+    last_O, last_E, last_F = z.copy(), z.copy(), z.copy()
+    have = np.zeros(Js, bool)
+    stat, cells = z.copy(), np.zeros(Js, np.int64)
+    for s in range(1, Js):
+        run_O += o1[:, s]
+        run_E += n[s] * E1[:, s]
+        run_F += n[s] * E0[:, s]
+        close = (run_E >= min_expected) & (run_F >= min_expected)
+        stat += np.where(close & have, term(last_O, last_E, last_F), 0.0)
+        last_O, last_E, last_F = (np.where(close, r, l) for r, l in ((run_O, last_O), (run_E, last_E), (run_F, last_F)))
+        have |= close
+        cells += close
+        run_O, run_E, run_F = (np.where(close, 0.0, r) for r in (run_O, run_E, run_F))
+    if Js >= 2:
+        last_O, last_E, last_F = last_O + run_O, last_E + run_E, last_F + run_F      # (never closed: last is 0, the only cell)
+        cells = np.where(have, cells, 1)
+        stat += term(last_O, last_E, last_F)
+    df = cells - n_params
+    p = np.array([chi2_sf(x, d) for x, d in zip(stat, df)], np.float64).reshape(Js)
+    nan = np.full((Js, Js + 1), np.nan)
+    pos = np.broadcast_to(n > 0, (Js, Js + 1))
+    observed = np.where(pos, o1 / np.where(n > 0, n, 1.0), nan)
+    expected = np.where(pos, E1, nan)
+    return {"sx2": stat, "df": df, "p": p, "n_cells": cells, "observed": observed, "expected": expected}
+
+
+def score_table_host(dist, logw, theta):
+    """The host layer of score_table(): the summed-score -> latent conversion table in float64 numpy from dist [G][Js + 1] = S(s |
+    node g), logw [G] and the nodes theta [G][D].  With w_g = exp(logw[g]): `prob` [Js + 1] = sum_g w_g S(s | g), the posterior of
+    the nodes given the score post = w S / prob, `eap` [Js + 1][D] = sum_g post theta_g and `psd` = the square root of sum_g post
+    (theta_g - eap)^2; NaN for a score the model gives no mass."""
+    dist, logw, theta = np.asarray(dist, np.float64), np.asarray(logw, np.float64).reshape(-1), np.asarray(theta, np.float64)
+    if dist.ndim != 2 or theta.ndim != 2 or dist.shape[0] != logw.shape[0] or theta.shape[0] != logw.shape[0]:
+        raise ValueError("dist must be [G][Js + 1], logw [G] and theta [G][D]")
+    joint = np.exp(logw)[:, None] * dist
+    prob = joint.sum(0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        post = joint / prob[None, :]
+    eap = np.einsum("gs,gd->sd", post, theta)
+    dev = theta[:, None, :] - eap[None, :, :]
+    psd = np.sqrt(np.einsum("gs,gsd->sd", post, dev * dev))
+    return {"score": np.arange(dist.shape[1], dtype=np.int64), "prob": prob, "eap": eap, "psd": psd}
 
 
 DIF_MAX_GROUPS = 4096            # GCC_MAXSEG (vipsy_amd/csrc/k_grid_counts_cond.hip): segments of a vx_grid_counts_cond call
@@ -848,6 +970,115 @@ class GridMixin(object):
         out = item_fit_stats(c["n1"], c["n0"], c["prob"])
         out["prob"] = c["prob"]
         return out
+
+    def _sumscore_items(self, items, J):
+        """`items` -> the sorted distinct item indices as int64 numpy [Js] (None: all J), refused as sx2() describes."""
+        if items is None:
+            it = np.arange(J, dtype=np.int64)
+        else:
+            it = items.detach().cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
+            if it.dtype.kind not in "iu" or it.ndim != 1 or it.size < 1:
+                raise ValueError("items must be a list of integer item indices, sorted and distinct")
+            it = it.astype(np.int64)
+            if it.min() < 0 or it.max() >= J or (np.diff(it) <= 0).any():
+                raise ValueError("items must be sorted, distinct and in 0 .. %d" % (J - 1))
+        if it.size > SUMSCORE_MAX_ITEMS:
+            raise NotImplementedError("summed-score tables take at most %d items (got %d): name a booklet with items="
+                                      % (SUMSCORE_MAX_ITEMS, it.size))
+        return it
+
+    def _sumscore_refusals(self, what, covariates, grid_kw):
+        if "rows" in grid_kw:
+            raise NotImplementedError("%s with rows=: a row subset is not built -- pass those persons' responses as data (the "
+                                      "complete persons among them are found by the call itself)" % what)
+        self._one_rank_only("%s over a process group: the tables are the sums over the local shard's persons and the cross-rank "
+                            "sum is not built" % what)
+        if covariates is not None:
+            raise NotImplementedError("%s with covariates=: the summed-score tables are built under the prior score() uses "
+                                      "without covariates; the latent regression's is not built" % what)
+
+    def _sumscore_model(self, call, it, want_dist=True):
+        """The model side: p1, p0 of the listed items out of the operand image and vx_sumscore_model."""
+        be, G, Js = self.be, call.G, int(it.size)
+        p1, p0 = grid_image_probs(self._grid_image(call), call.J, G)
+        if Js != call.J:
+            sel = torch.from_numpy(it).to(self.dev)
+            p1, p0 = p1[sel].contiguous(), p0[sel].contiguous()
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        out = {"e1": torch.empty(Js, Js + 1, **f32), "e0": torch.empty(Js, Js + 1, **f32),
+               "dist": torch.empty(G, Js + 1, **f32) if want_dist else None}
+        ws_floats = be.sumscore_model_workspace(Js, G)
+        ws = torch.empty(ws_floats, **f32)
+        be.sumscore_model(p1, p0, call.logw, Js, G, out["e1"], out["e0"], out["dist"], ws, ws_floats)
+        return out
+
+    def sumscore_tables(self, y_u8=None, items=None, covariates=None, **grid_kw):
+        """The summed-score tables behind sx2() and score_table(), as device tensors, over `items` (a sorted list of Js distinct
+        item indices; default all, Js <= 1023) and the nodes of score().  The model side, by the Lord-Wingersky recursion over
+        p1 = P(y_j = 1 | node) and p0 = P(y_j = 0 | node) as the operand image holds them (vx_sumscore_model): `e1`, `e0` float32
+        [Js][Js + 1], the joint probability of summed score s with y_j = 1 / 0 (e1 + e0 = P(score = s) for every j), and `dist`
+        [G][Js + 1] = P(score = s | node g).  The observed side, over the COMPLETE persons of the scored rows -- every listed
+        cell 0 or 1; a 255 or 254 among the listed items takes the person out -- (vx_sumscore_persons, vx_sumscore_observed):
+        `score` int32 [n] (-1: not complete), `o1` int32 [Js][Js + 1] = the complete persons of score s with y_j = 1, `n` int64
+        [Js + 1] = the complete persons of score s.  Also `items` (int64), `theta` [G][D] and `logw` [G].  Inputs, grid and
+        refusals as score(); covariates= and rows= are not built; one rank only.  Deterministic: the same call gives the same
+        bits."""
+        self._sumscore_refusals("sumscore_tables / sx2", covariates, grid_kw)
+        call = self._grid_call(y_u8, None, **grid_kw)
+        it = self._sumscore_items(items, call.J)
+        be, Js, n = self.be, int(it.size), call.n
+        out = self._sumscore_model(call, it)
+        items_dev = torch.from_numpy(it.astype(np.int32)).to(self.dev) if Js != call.J else None
+        score = torch.empty(n, dtype=torch.int32, device=self.dev)
+        be.sumscore_persons(call.y, None, n, call.J, items_dev, Js, score)
+        rows = torch.nonzero(score >= 0).reshape(-1)
+        sc, order = torch.sort(score[rows], stable=True)                         # (plumbing: the kernel wants the persons by score)
+        rows, sc = rows[order].contiguous(), sc.contiguous()
+        o1 = torch.empty(Js, Js + 1, dtype=torch.int32, device=self.dev)
+        be.sumscore_observed(call.y, rows, int(rows.numel()), call.J, items_dev, Js, sc, o1)
+        out.update({"o1": o1, "n": torch.bincount(sc.long(), minlength=Js + 1), "score": score,
+                    "items": torch.from_numpy(it).to(self.dev), "theta": call.theta, "logw": call.logw})
+        return out
+
+    def sx2(self, y_u8=None, items=None, min_expected=1.0, covariates=None, **grid_kw):
+        """Orlando & Thissen's S-X2 item-fit test of every listed item (sx2_host over sumscore_tables): within each summed-score
+        group, the observed proportion correct against the proportion the model predicts for that group under the item
+        parameters as they stand.  The cells are observable, so a chi-square reference applies.  Returns numpy: `sx2`, `df`, `p`,
+        `n_cells` [Js]; `observed`, `expected` [Js][Js + 1], the proportions correct per score group (NaN where n[s] = 0);
+        `n_persons` (the complete persons), `n_dropped` and `items`.  df = cells - the item's free parameters (1PL: 1; 2PL: 1 +
+        its free loadings; 3PL / 4PL: + 1 / + 2; DINA / DINO: 2); p is NaN where df <= 0.  The score groups are collapsed by one
+        left-to-right sweep until both expected counts of a cell reach min_expected (sx2_host): this project's own rule.
+        Only COMPLETE persons count: with a design that leaves cells missing, name one booklet's items with items=.
+        ValueError when no person is complete.  Not built: sampling weights, covariates=, more than one rank, polytomous
+        items."""
+        if not (isinstance(min_expected, (int, float, np.floating, np.integer)) and not isinstance(min_expected, bool)
+                and np.isfinite(min_expected) and min_expected > 0):
+            raise ValueError("min_expected must be a positive finite number")
+        t = self.sumscore_tables(y_u8, items, covariates, **grid_kw)
+        n = t["n"].cpu().numpy()
+        n_persons = int(n.sum())
+        total = int(t["score"].numel())
+        if n_persons == 0:
+            raise ValueError("no person of the %d scored rows is complete on the %d listed items: S-X2 counts complete response "
+                             "vectors only -- pass items= to score one booklet of a missing-by-design test"
+                             % (total, int(t["items"].numel())))
+        it = t["items"].cpu().numpy()
+        out = sx2_host(t["e1"].cpu().numpy(), t["e0"].cpu().numpy(), t["o1"].cpu().numpy(), n, self._sx2_params(it), min_expected)
+        out.update({"n_persons": n_persons, "n_dropped": total - n_persons, "items": it})
+        return out
+
+    def score_table(self, items=None, covariates=None, **grid_kw):
+        """The summed-score -> latent conversion table of the listed items (score_table_host over vx_sumscore_model's `dist`),
+        under the item parameters as they stand and the prior of score(); takes no data.  Returns numpy, float64: `score`
+        [Js + 1], `prob` = the model's P(score = s), and what score() reports of a person, given the summed score alone: `eap`,
+        `psd` [Js + 1][D] (IrtEngine) or `attr_prob` [Js + 1][K] (CcdmEngine).  Refusals as sumscore_tables()."""
+        self._sumscore_refusals("score_table", covariates, grid_kw)
+        call = self._grid_call(None, None, **grid_kw)
+        it = self._sumscore_items(items, call.J)
+        m = self._sumscore_model(call, it)
+        out = score_table_host(m["dist"].cpu().numpy(), call.logw.cpu().numpy(), call.theta.cpu().numpy())
+        out["items"] = it
+        return self._score_table_leaves(out)
 
     def marginal_loglik(self, y_u8=None, rows=None, **kw):
         """sum_i log p(y_i) under the item parameters as they stand, summed on the device in a fixed order."""

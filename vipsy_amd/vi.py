@@ -380,6 +380,44 @@ class BasePsy(object):
                                       "cross-rank sum is not built" % self.world)
         return self.engine.item_msq(self._score_data(data), **grid_kw)
 
+    def sumscore_tables(self, data=None, items=None, **grid_kw):
+        """The summed-score tables behind sx2() and score_table(), as device tensors: the model's `e1`, `e0` [items][items + 1]
+        and `dist` [nodes][items + 1] by the Lord-Wingersky recursion, the observed `o1`, `n` and `score` over the complete
+        persons of `data` (None: the training data), and `items`, `theta`, `logw` (GridMixin.sumscore_tables).  `items`: a sorted
+        list of distinct item indices, at most 1023 (default: all).  VIRT / VaeIRT with x_feature <= 3 (grid_kw: nodes, span),
+        VCCDM; the other classes refuse.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("sumscore_tables with a group of %d ranks: the tables are the sums over the local shard's "
+                                      "persons; the cross-rank sum is not built" % self.world)
+        return self.engine.sumscore_tables(self._score_data(data), items, **grid_kw)
+
+    def sx2(self, data=None, items=None, min_expected=1.0, **grid_kw):
+        """Orlando & Thissen's S-X2 item-fit test, ready to print beside the item parameters: for every listed item the
+        statistic `sx2`, its `df`, the chi-square tail probability `p` and `n_cells`, with `observed` and `expected`
+        [items][items + 1], the proportions correct per summed-score group, `n_persons`, `n_dropped` and `items`
+        (GridMixin.sx2).  Within each summed-score group the observed proportion correct is compared with the one the model
+        predicts for that group (Lord-Wingersky); the cells are observable, so the statistic has a chi-square reference, which
+        the RMSD of item_fit() has not.  Score groups are collapsed by one left-to-right sweep until both expected counts of a
+        cell reach min_expected -- this project's own rule; other packages merge in other orders.  Only persons who answered
+        every listed item count: for a test with cells missing by design pass one booklet's items as items=; ValueError when no
+        person is complete.  `data`: None = the training data.  VIRT / VaeIRT with x_feature <= 3, every IRT model (grid_kw:
+        nodes, span), VCCDM; the other classes refuse.  covariates= is not built.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("sx2 with a group of %d ranks: the tables are the sums over the local shard's persons; the "
+                                      "cross-rank sum is not built" % self.world)
+        return self.engine.sx2(self._score_data(data), items, min_expected, **grid_kw)
+
+    def score_table(self, items=None, **grid_kw):
+        """The summed-score -> latent conversion table a testing programme publishes, numpy float64: `score` [items + 1], `prob`
+        = the model's P(score = s), and for VIRT / VaeIRT `eap`, `psd` [items + 1][x_feature], for VCCDM `attr_prob`
+        [items + 1][K]: what score() would say of a person of whom only the summed score over `items` is known
+        (GridMixin.score_table).  Takes no data.  Classes and refusals as sx2().  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("score_table with a group of %d ranks is not built: every rank holds the item parameters; "
+                                      "ask one" % self.world)
+        return self.engine.score_table(items, **grid_kw)
+
+
 class BaseIRT(BasePsy):
     """vi.py:536-656 (constructor kwargs identical: model, x_feature, share_cov, D, a_free, a0, b0)."""
 
