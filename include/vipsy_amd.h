@@ -626,6 +626,40 @@ int vx_grid_fit_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K]
                     const float* s_un, float* person /*[7][nb]*/, float* item /*[4][J]*/, float* workspace, int64_t ws_floats,
                     void* hip_stream);
 
+/* ---- Point estimates: the ML, MAP and Warm's weighted-likelihood (WLE) estimate of every scored person by Fisher scoring, from
+ * theta0 [nb][D] (by batch position; the `mean` of vx_grid_posterior), over the observed cells of the person's row (y < 2) under
+ * the item parameters as they stand (cfg, parameters and limits as vx_grid_fit_irt).  With z = Dc (theta . a + b), P = c + (d - c)
+ * sigmoid(z), Q = (1 - d) + (d - c) sigmoid(-z), P_z = (d - c) sigmoid(z) sigmoid(-z):
+ *     g_d = Dc sum_j a_jd (y_j ? Q_j : -P_j) P_z / (P_j Q_j)        I_de = Dc^2 sum_j a_jd a_je P_z^2 / (P_j Q_j)
+ *   method VX_POINT_ML: g, M = I;  VX_POINT_MAP: g - theta, M = I + 1 (the N(0, I) prior);  VX_POINT_WLE (D = 1): g + J / (2 I),
+ *   M = I, J = sum_j P'_j P''_j / (P_j Q_j) (Warm 1989; Firth's penalised score for 1PL / 2PL).
+ * An evaluation at theta gives delta = M^-1 g (Cholesky); a person stops AT THE POINT OF THE EVALUATION with status
+ *     VX_POINT_CONVERGED  max |delta| <= tol (before the cap)
+ *     VX_POINT_AT_BOUND   on two consecutive evaluations a coordinate sits on +-bound and delta points outward
+ *     VX_POINT_MAX_ITER   the max_iter-th evaluation did neither
+ *     VX_POINT_SINGULAR   a pivot (or the step) is not positive and finite
+ *     VX_POINT_EMPTY      no observed cell: theta_hat NaN, info 0, iters 0
+ *   and otherwise moves to clamp(theta + delta min(1, step_cap / max |delta|), -bound, bound) (theta0 is clamped alike).
+ * theta_hat [nb][D]; info [D (D + 1) / 2][nb]: the upper triangle (00, 01, 02, 11, 12, 22) of I at theta_hat -- the likelihood's,
+ * without the prior, for every method; status, iters (the evaluations) [nb] int32.  A person's results depend on its own row
+ * and start alone -- not on the persons scored beside it -- every sum has a fixed order, the grid depends on nb alone, there is
+ * no atomic: the same call gives the same bits.  y is read once a person; no workspace.
+ * Limits: model 1..4, 1 <= D <= 3 (wle: D = 1), 1 <= J <= 1024, nb >= 1, 1 <= max_iter <= 255, tol, bound and step_cap positive
+ * and finite; VX_EINVAL beyond, before anything is read. */
+#define VX_POINT_ML 0
+#define VX_POINT_MAP 1
+#define VX_POINT_WLE 2
+#define VX_POINT_CONVERGED 0
+#define VX_POINT_AT_BOUND 1
+#define VX_POINT_MAX_ITER 2
+#define VX_POINT_SINGULAR 3
+#define VX_POINT_EMPTY 4
+int vx_grid_point_irt(const vx_irt_cfg* cfg, const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb,
+                      const float* theta0 /*[nb][D]*/, const float* a /*[D][J] or NULL (1PL)*/, const float* b /*[J]*/,
+                      const float* c_un /*[J] or NULL*/, const float* d_un /*[J] or NULL*/, int32_t method, int32_t max_iter,
+                      float tol, float bound, float step_cap, float* theta_hat /*[nb][D]*/, float* info /*[D (D + 1) / 2][nb]*/,
+                      int32_t* status /*[nb]*/, int32_t* iters /*[nb]*/, void* hip_stream);
+
 /* ---- Summed-score tables (k_sumscore.hip): the model side of Orlando & Thissen's S-X2 item fit and of the score -> latent
  * conversion table, by the Lord-Wingersky recursion, and the observed side, over a list of Js items.
  * vx_sumscore_model: p1, p0 [Js][G] = P(y_j = 1 | node g) and P(y_j = 0 | node g) of the listed items (both given; p0 is never

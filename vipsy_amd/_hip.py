@@ -150,6 +150,7 @@ SIGNATURES = {
     "vx_grid_fit_workspace_floats": (_I64, [_I64, _I32]),
     "vx_grid_fit_irt": (ctypes.c_int, [_CFG, _P, _P, _I64, _P] + [_P] * 4 + [_P, _P] + [_P, _I64, _P]),
     "vx_grid_fit_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32, _P, _P, _P, _I64, _P, _P, _P] + [_P, _P] + [_P, _I64, _P]),
+    "vx_grid_point_irt": (ctypes.c_int, [_CFG, _P, _P, _I64, _P] + [_P] * 4 + [_I32, _I32, _F, _F, _F] + [_P] * 4 + [_P]),
     "vx_sumscore_model_workspace_floats": (_I64, [_I32, _I32]),
     "vx_sumscore_model": (ctypes.c_int, [_P, _P, _P, _I32, _I32] + [_P] * 3 + [_P, _I64, _P]),
     "vx_sumscore_persons": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P]),

@@ -37,6 +37,7 @@
 #include "k_grid_info.hip"
 #include "k_grid_pairs.hip"
 #include "k_grid_fit.hip"
+#include "k_grid_point.hip"
 #include "k_grid_cond.hip"
 #include "k_grid_counts_cond.hip"
 #include "k_sumscore.hip"
@@ -2633,6 +2634,40 @@ int vx_grid_fit_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, cons
     hipLaunchKernelGGL(k_fit_cdm, dim3((unsigned)p.n_blocks), dim3(256), 0, (hipStream_t)hs, y, rows, nb, K, J, (int)dino, q, pattern, g_un,
                        s_un, person, workspace, p.n_units, p.units_per_block);
     return grid_fit_finish(p, J, workspace, item, hs);
+}
+
+// Point estimates (k_grid_point.hip): ML / MAP / WLE by Fisher scoring, a person's row held on chip; no workspace
+static bool point_number_ok(float v) { return v > 0.f && v < INFINITY; }
+
+int vx_grid_point_irt(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* theta0, const float* a,
+                      const float* b, const float* c_un, const float* d_un, int32_t method, int32_t max_iter, float tol, float bound,
+                      float step_cap, float* theta_hat, float* info, int32_t* status, int32_t* iters, void* hs) {
+    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GF_MAXD || !grid_pairs_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (method != GPT_ML && method != GPT_MAP && method != GPT_WLE) return VX_EINVAL;
+    if ((method == GPT_WLE && cfg->D != 1) || max_iter < 1 || max_iter > GPT_MAX_ITERS) return VX_EINVAL;
+    if (!point_number_ok(tol) || !point_number_ok(bound) || !point_number_ok(step_cap)) return VX_EINVAL;
+    if (!y || !theta0 || !b || !theta_hat || !info || !status || !iters) return VX_EINVAL;
+    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
+        return VX_EINVAL;
+    hipStream_t st = (hipStream_t)hs;
+    const int D = (int)cfg->D, J = (int)cfg->J, model = (int)cfg->model, map = method == GPT_MAP ? 1 : 0;
+    const GfPlan p = gf_plan(nb);
+#define LAUNCH_GPT(M, DD, W)                                                                                                        \
+    hipLaunchKernelGGL((k_point_irt<M, DD, W>), dim3((unsigned)p.n_blocks), dim3(256), 0, st, y, rows, nb, D, J, cfg->Dc, theta0, a, b, \
+                       c_un, d_un, map, (int)max_iter, tol, bound, step_cap, theta_hat, info, status, iters, p.n_units,             \
+                       p.units_per_block)
+#define LAUNCH_GPT_MODEL(M)                                                                                           \
+    do {                                                                                                              \
+        if (method == GPT_WLE) { LAUNCH_GPT(M, 1, true); }                                                            \
+        else if (D == 1) { LAUNCH_GPT(M, 1, false); }                                                                 \
+        else { LAUNCH_GPT(M == 1 ? 2 : M, 3, false); }                                                                \
+    } while (0)
+    if (model == 1) { LAUNCH_GPT_MODEL(1); } else if (model == 2) { LAUNCH_GPT_MODEL(2); } else if (model == 3) { LAUNCH_GPT_MODEL(3); }
+    else { LAUNCH_GPT_MODEL(4); }
+#undef LAUNCH_GPT_MODEL
+#undef LAUNCH_GPT
+    VX_CHECK_LAUNCH();
+    return VX_OK;
 }
 
 // Summed-score tables (k_sumscore.hip): the Lord-Wingersky recursion behind S-X2 and the score table, and the observed tables

@@ -17,6 +17,8 @@ import torch
 from . import _hip
 from .grid import (EM_MAX_NEWTON, PV_MAX_DRAWS, PV_STREAM, SCORE_MAX_DIMS, SCORE_MAX_NODES, GridCall, GridMixin,  # noqa: F401
                    design_cholesky, grid_image_prob, item_fit_stats, population_logw, score_grid, tri_to_full)     # (re-exported: the grid family lives in grid.py)
+from .grid import (POINT_AT_BOUND, POINT_CONVERGED, POINT_EMPTY, POINT_MAX_ITER, POINT_MAX_ITERS, POINT_METHODS,  # noqa: F401
+                   POINT_SINGULAR, POINT_STATUS, POINT_STEP_CAP, point_estimates_host)
 
 MODEL_CODE = {"irt_1pl": 1, "irt_2pl": 2, "irt_3pl": 3, "irt_4pl": 4}       # vi.py:538-543
 LOSS_RING = 64                                                               # VX_LOSS_RING (include/vipsy_amd.h)
@@ -345,6 +347,14 @@ class HipBackend(object):
                                     _hip.ptr(c_un), _hip.ptr(d_un), _hip.ptr(person), _hip.ptr(item), _hip.ptr(ws), int(ws_floats),
                                     _hip.stream_ptr())
         _hip.check(rc, "vx_grid_fit_irt")
+
+    def grid_point_irt(self, cfg, y, rows, nb, theta0, a, b, c_un, d_un, method, max_iter, tol, bound, step_cap, theta_hat, info,
+                       status, iters):
+        rc = self.L.vx_grid_point_irt(ctypes.byref(cfg), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(theta0), _hip.ptr(a), _hip.ptr(b),
+                                      _hip.ptr(c_un), _hip.ptr(d_un), int(method), int(max_iter), float(tol), float(bound),
+                                      float(step_cap), _hip.ptr(theta_hat), _hip.ptr(info), _hip.ptr(status), _hip.ptr(iters),
+                                      _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_point_irt")
 
     def grid_fit_cdm(self, cfg, dino, q, y, rows, nb, pattern, g, s_, person, item, ws, ws_floats):
         rc = self.L.vx_grid_fit_cdm(ctypes.byref(cfg), int(dino), _hip.ptr(q), _hip.ptr(y), _hip.ptr(rows), nb, _hip.ptr(pattern),
@@ -704,6 +714,7 @@ class _EngineBase(object):
     fit_sums = person_fit = item_msq = _no_grid
     group_counts = dif = _no_grid
     sumscore_tables = sx2 = score_table = _no_grid
+    point_estimates = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1873,6 +1884,68 @@ class IrtEngine(GridMixin, _EngineBase):
         return call, "theta_hat", "mean", lambda est, person, item, ws, ws_floats: self.be.grid_fit_irt(
             call.cfg, call.y, call.rows, call.n, est, *params, person, item, ws, ws_floats)
 
+    def _point_refusals(self, method):
+        """wle beyond one dimension (x_feature > 3 is left to _grid_call, which refuses in the words of score())."""
+        if method == "wle" and 1 < self.D_model <= SCORE_MAX_DIMS:
+            raise NotImplementedError("the weighted likelihood estimate ('wle') needs x_feature = 1 (this model has %d): the "
+                                      "multidimensional Firth term needs M^-1 inside the item sum; it is not built -- 'ml' and "
+                                      "'map' serve x_feature <= %d" % (self.D_model, SCORE_MAX_DIMS))
+
+    def _point_run(self, call, theta0, method, max_iter=32, tol=1e-6, bound=None):
+        """vx_grid_point_irt over a call, from theta0 [n][D] (float32 on the device), on compact copies of the engine's own items
+        as _fit_call makes them and in buffers of its own: device tensors `theta_hat` (n, D), `info` [D (D + 1) / 2][n], `status`
+        and `iters` (n,) int32.  bound None: the reach of the call's nodes."""
+        n, D = call.n, call.D
+        if bound is None:
+            bound = float(call.theta.abs().max())
+        flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()      # noqa: E731
+        params = (self.unconstrained("a").contiguous() if self.model != "irt_1pl" else None, flat("b"),
+                  flat("c") if self.model in ("irt_3pl", "irt_4pl") else None, flat("d") if self.model == "irt_4pl" else None)
+        out = {"theta_hat": torch.empty(n, D, dtype=torch.float32, device=self.dev),
+               "info": torch.empty(D * (D + 1) // 2, n, dtype=torch.float32, device=self.dev),
+               "status": torch.empty(n, dtype=torch.int32, device=self.dev), "iters": torch.empty(n, dtype=torch.int32, device=self.dev)}
+        self.be.grid_point_irt(call.cfg, call.y, call.rows, n, theta0.contiguous(), *params, POINT_METHODS[method], max_iter, tol, bound,
+                               POINT_STEP_CAP, out["theta_hat"], out["info"], out["status"], out["iters"])
+        return out
+
+    def point_estimates(self, y_u8=None, rows=None, method="wle", max_iter=32, tol=1e-6, bound=None, nodes=61, span=6.0,
+                        covariates=None):
+        """Likelihood-based person scores: for each scored row the estimate `theta_hat` (n, D) that Fisher scoring reaches from
+        the grid EAP of score(), over the items the person answered and under the item parameters as they stand
+        (vx_grid_point_irt) -- method "ml", the maximum of the likelihood; "map", of the likelihood times the N(0, I) prior of
+        score(); "wle" (x_feature = 1), Warm's weighted likelihood estimate, the score PISA, TIMSS, ConQuest and TAM report
+        (for 1PL / 2PL Firth's penalised score) -- with its standard error.  Unlike the EAP it is not shrunk towards the prior
+        mean (ml, wle) and not tied to the node spacing.  A step is capped at 1 a coordinate and theta is kept in [-bound,
+        bound] (bound None: span); a person stops when the step falls to tol or below.
+        Returns numpy: `theta_hat` float32 (n, D); `info` float64 (n, D, D), the likelihood's expected information at
+        theta_hat (without the prior, for every method); `cov` = M^-1 with M = info (+ I for "map") and `se` (n, D) = the square
+        roots of its diagonal, inverted in float64; `status` int32 (n,) -- POINT_STATUS names the codes: 0 converged, 1 at_bound
+        (the ML estimate of an all-correct or all-wrong row lies beyond the bound: theta_hat sits on it, se is the finite value
+        there), 2 max_iter, 3 singular, 4 empty (the person answered nothing: theta_hat NaN) --; `iterations` (n,), the
+        evaluations taken; `n_converged`; and `reliability` (D,) = 1 - mean(se^2) / var(theta_hat) over the converged persons, the
+        person separation reliability of a TAM / ConQuest report (NaN with fewer than two).  se and cov are NaN where status is
+        empty or singular.  Inputs, data contract, grid and refusals as score(); with a process group this rank's shard.  Works
+        in buffers of its own: nothing of the engine changes.  Deterministic: the same call gives the same bits, and a
+        person's result does not depend on the persons scored beside it.
+        Not built: "wle" with x_feature > 1 (the multidimensional Firth term needs M^-1 inside the item sum), covariates=
+        (a MAP under the population of fit_population), Snijders' correction, observed-information standard errors."""
+        if method not in POINT_METHODS:
+            raise ValueError("method must be one of %s (got %r)" % (", ".join(repr(k) for k in sorted(POINT_METHODS)), method))
+        max_iter = self._int_in("max_iter", max_iter, 1, POINT_MAX_ITERS)
+        for name, v in (("tol", tol), ("bound", span if bound is None else bound)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(v) or not v > 0:
+                raise ValueError("%s must be a positive finite number" % name)
+        if covariates is not None:
+            raise NotImplementedError("point_estimates with covariates=: the estimates are taken under the likelihood alone (ml, "
+                                      "wle) or the N(0, I) prior of score() (map); a MAP under the population of "
+                                      "fit_population() is not built")
+        self._point_refusals(method)
+        call = self._grid_call(y_u8, rows, nodes, span)
+        theta0 = self._grid_posterior(call)["mean"]
+        pt = self._point_run(call, theta0, method, max_iter, float(tol), float(span if bound is None else bound))
+        return point_estimates_host(pt["theta_hat"].cpu().numpy(), pt["info"].cpu().numpy(), pt["status"].cpu().numpy(),
+                                    pt["iters"].cpu().numpy(), method)
+
     def _sx2_params(self, items):
         """The free parameters of each listed item, for the df of GridMixin.sx2: b; for 2PL and up the item's free loadings; the
         lower asymptote of 3PL / 4PL and the upper one of 4PL."""
@@ -2290,6 +2363,11 @@ class CcdmEngine(GridMixin, _EngineBase):
         out = self._grid_counts(call)
         out["patterns"] = call.theta
         return out
+
+    def point_estimates(self, *args, **kw):
+        raise NotImplementedError("%s has no point_estimates: the point estimate of an attribute pattern is the MAP pattern "
+                                  "score() already returns (`pattern`); ML / MAP / WLE by Fisher scoring belong to a continuous "
+                                  "latent (IrtEngine with x_feature <= 3)" % type(self).__name__)
 
     def _group_refusals(self, covariates, impact):
         if covariates is not None or impact:

@@ -447,6 +447,46 @@ def item_msq_host(item):
     return {"infit": infit, "outfit": outfit}
 
 
+POINT_METHODS = {"ml": 0, "map": 1, "wle": 2}                    # VX_POINT_ML / _MAP / _WLE (include/vipsy_amd.h)
+POINT_STATUS = ("converged", "at_bound", "max_iter", "singular", "empty")        # the names of vx_grid_point_irt's status codes
+POINT_CONVERGED, POINT_AT_BOUND, POINT_MAX_ITER, POINT_SINGULAR, POINT_EMPTY = range(5)
+POINT_MAX_ITERS = 255            # GPT_MAX_ITERS (vipsy_amd/csrc/k_grid_point.hip)
+POINT_STEP_CAP = 1.0             # the largest component of a Fisher-scoring step
+POINT_AT = ("eap",) + tuple(POINT_METHODS)                       # what the diagnostics take as at=
+
+
+def point_estimates_host(theta_hat, info_tri, status, iterations, method):
+    """The host layer of point_estimates(): from vx_grid_point_irt's theta_hat (n, D) float32, info_tri [D (D + 1) / 2][n] (the
+    upper triangle of the likelihood's information at theta_hat), status and iterations (n,), in float64 numpy: `info` (n, D, D),
+    `cov` = M^-1 with M = info (+ the unit matrix for method "map", the N(0, I) prior), `se` = the square roots of its diagonal,
+    `n_converged` and the person separation `reliability` (D,) = 1 - mean(se^2) / var(theta_hat) over the persons with status
+    `converged` (var with n - 1; NaN with fewer than two of them).  cov and se are NaN where status is `empty` or `singular`, or
+    where M is not positive definite."""
+    th = np.asarray(theta_hat)
+    n, D = th.shape
+    status = np.asarray(status).astype(np.int32)
+    info = tri_to_full(np.asarray(info_tri, np.float64).T, D)
+    M = info + (np.eye(D) if method == "map" else 0.0)
+    cov = np.full((n, D, D), np.nan)
+    ok = (status != POINT_EMPTY) & (status != POINT_SINGULAR) & np.isfinite(M).all((1, 2))
+    if D == 1:                                                                  # (a million persons: no batched LAPACK for 1 x 1)
+        ok &= M[:, 0, 0] > 0
+        cov[ok, 0, 0] = 1.0 / M[ok, 0, 0]
+    else:
+        for d in range(D):                                                      # positive definite: every leading minor
+            ok &= np.linalg.det(np.where(ok[:, None, None], M, np.eye(D))[:, :d + 1, :d + 1]) > 0
+        if ok.any():
+            cov[ok] = np.linalg.inv(M[ok])
+    se = np.sqrt(np.diagonal(cov, axis1=1, axis2=2)).copy()
+    conv = status == POINT_CONVERGED
+    rel = np.full(D, np.nan)
+    if conv.sum() >= 2:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel = 1.0 - (se[conv] ** 2).mean(0) / th[conv].astype(np.float64).var(0, ddof=1)
+    return {"theta_hat": th, "se": se, "cov": cov, "info": info, "status": status,
+            "iterations": np.asarray(iterations).astype(np.int32), "n_converged": int(conv.sum()), "reliability": rel}
+
+
 class GridCall(namedtuple("GridCall", "y rows J theta logw fill_tables cfg")):
     """What an engine's `_grid_call` hands to the grid kernels: the responses y ([n][J] u8 on the device) and the rows of them to
     score (int64 on the device, or None: all), the nodes theta [G][D] with their log-weights logw [G], fill_tables(img), which
@@ -880,27 +920,54 @@ class GridMixin(object):
         out.update(self._se_leaves(out.pop("se")))
         return out
 
-    def residual_sums(self, y_u8=None, rows=None, **grid_kw):
+    def _point_refusals(self, method):
+        """What a class without point_estimates() says to at= other than "eap" (IrtEngine has its own)."""
+        raise ValueError("at=%r on %s: its point estimate is the MAP pattern of score(); only at='eap' is served"
+                         % (method, type(self).__name__))
+
+    def _at_check(self, at):
+        """The refusals of at=, before anything is computed."""
+        if not isinstance(at, str) or at not in POINT_AT:
+            raise ValueError("at must be one of %s (got %r)" % (", ".join(repr(k) for k in POINT_AT), at))
+        if at != "eap":
+            self._point_refusals(at)
+
+    def _estimate_at(self, call, post, key, at):
+        """The point estimates a diagnostic takes its residuals at: at="eap", the posterior kernel's own (`post[key]`, today's
+        path and bits); "wle" | "ml" | "map", the theta_hat of point_estimates() with its defaults (_point_run), the EAP in its
+        place for a person whose status is `empty` or `singular` -- returns (estimates, that mask or None)."""
+        if at == "eap":
+            return post[key], None
+        pt = self._point_run(call, post["mean"], at)
+        bad = (pt["status"] == POINT_EMPTY) | (pt["status"] == POINT_SINGULAR)
+        return torch.where(bad[:, None], post["mean"], pt["theta_hat"]).contiguous(), bad
+
+    def residual_sums(self, y_u8=None, rows=None, at="eap", **grid_kw):
         """The pairwise-complete residual sums of the scored rows (vx_grid_pairs_*): with r_ij = y_ij - P_ij the residual of an
         observed cell AT THE PERSON'S POINT ESTIMATE -- the grid EAP of score() for IrtEngine (all four models), the MAP pattern
         for CcdmEngine -- under the item parameters as they stand, and I_jk the persons who answered both j and k: float32
         device tensors [J][J] `n` = |I_jk|, `s` = sum of r_ij, `ss` = sum of r_ij^2 (the ROW item's, over I_jk: not symmetric) and
         `sp` = sum of r_ij r_ik (symmetric bit for bit, as is n), beside `theta_hat` (n, D) or `pattern` (n,), the estimates the
         residuals were taken at.  Inputs, grid and refusals as score(); one rank only.  Works in buffers of its own.
-        Deterministic: the same call gives the same bits.  n is exact up to 2**24 scored persons."""
+        Deterministic: the same call gives the same bits.  n is exact up to 2**24 scored persons.
+        at (IrtEngine): "eap" (the default: the path and the bits above), or "wle" | "ml" | "map": the residuals at the theta_hat
+        of point_estimates(method=at) with its defaults.  A person whose estimate has status `empty` or `singular` is passed
+        with its EAP instead (an empty person adds nothing to any pair); CcdmEngine raises ValueError for anything but "eap"."""
         self._one_rank_only("residual_sums / local_dependence over a process group: the tables are the sums over the local shard's "
                             "persons and the cross-rank sum is not built")
+        self._at_check(at)
         call, name, key, run = self._pairs_call(y_u8, rows, **grid_kw)
         post = self._grid_posterior(call)
+        est, _ = self._estimate_at(call, post, key, at)
         f32 = dict(dtype=torch.float32, device=self.dev)
         out = {k: torch.empty(call.J, call.J, **f32) for k in ("n", "s", "ss", "sp")}
         ws_floats = self.be.grid_pairs_workspace(call.n, call.J)
         ws = torch.empty(ws_floats, **f32)
-        run(post[key], out, ws, ws_floats)
-        out[name] = post[key]
+        run(est, out, ws, ws_floats)
+        out[name] = est
         return out
 
-    def local_dependence(self, y_u8=None, rows=None, min_pairs=8, top=20, **grid_kw):
+    def local_dependence(self, y_u8=None, rows=None, min_pairs=8, top=20, at="eap", **grid_kw):
         """Yen's Q3 of every item pair (pair_q3_host over residual_sums): the correlation, over the persons who answered both
         items, of the residuals y - P taken at the EAP (IrtEngine) or the MAP pattern (CcdmEngine) under the item parameters as
         they stand.  Pairs are pairwise-complete: a 255 cell takes its person out of the pairs of that item only.  Returns numpy:
@@ -908,17 +975,18 @@ class GridMixin(object):
         spread over them; the diagonal is 1 where defined), `n_pairs` int64 [J][J], `mean` = the mean of the finite off-diagonal
         entries (about -1 / (J - 1) under local independence, which is why it is reported), `max` = the largest off-diagonal
         q3 - mean, and `item_j`, `item_k`, `value`: the `top` pairs j < k by descending |q3 - mean| with their q3.
-        min_pairs: an integer >= 2; below the default 8 the statistic's own cancellation magnifies float32 rounding."""
+        min_pairs: an integer >= 2; below the default 8 the statistic's own cancellation magnifies float32 rounding.
+        at: "eap" (default) or "wle" | "ml" | "map" (IrtEngine): where the residuals are taken, as residual_sums() has it."""
         min_pairs = self._int_in("min_pairs", min_pairs, 2)
         top = self._int_in("top", top, 0)
-        t = self.residual_sums(y_u8, rows, **grid_kw)
+        t = self.residual_sums(y_u8, rows, at=at, **grid_kw)
         n = t["n"].cpu().numpy()
         q3 = pair_q3_host(n, t["s"].cpu().numpy(), t["ss"].cpu().numpy(), t["sp"].cpu().numpy(), min_pairs)
         out = pair_q3_summary(q3, top)
         out["q3"], out["n_pairs"] = q3, np.rint(n).astype(np.int64)
         return out
 
-    def fit_sums(self, y_u8=None, rows=None, **grid_kw):
+    def fit_sums(self, y_u8=None, rows=None, at="eap", **grid_kw):
         """The sums behind person_fit() and item_msq() (vx_grid_fit_*), over the observed cells of the scored rows.  With P the
         model probability AT THE PERSON'S POINT ESTIMATE -- the grid EAP of score() for IrtEngine (all four models), the MAP
         pattern for CcdmEngine -- under the item parameters as they stand, Q = 1 - P and lambda = log(P / Q): float32 device
@@ -927,36 +995,52 @@ class GridMixin(object):
         sw, sz2}, each (J,), over the persons who answered an item, beside `theta_hat` (n, D) or `pattern` (n,), the estimates
         they were taken at.  A person or item without answers has exact zeros.  Inputs, grid and refusals as score(); with a
         process group the sums are this rank's shard's (the person sums are complete, the item sums are not).  Works in buffers
-        of its own.  Deterministic: the same call gives the same bits.  The counts are exact up to 2**24 scored persons."""
+        of its own.  Deterministic: the same call gives the same bits.  The counts are exact up to 2**24 scored persons.
+        at (IrtEngine): "eap" (the default: the path and the bits above), or "wle" | "ml" | "map": the sums at the theta_hat of
+        point_estimates(method=at) with its defaults; then also `no_estimate` (bool (n,)): the persons whose estimate has
+        status `empty` or `singular` -- their sums are taken at the EAP, and person_fit() reports NaN for them.  CcdmEngine
+        raises ValueError for anything but "eap"."""
+        self._at_check(at)
         call, name, key, run = self._fit_call(y_u8, rows, **grid_kw)
         post = self._grid_posterior(call)
+        est, bad = self._estimate_at(call, post, key, at)
         f32 = dict(dtype=torch.float32, device=self.dev)
         person, item = torch.empty(len(PERSON_SUMS), call.n, **f32), torch.empty(len(ITEM_SUMS), call.J, **f32)
         ws_floats = self.be.grid_fit_workspace(call.n, call.J)
         ws = torch.empty(ws_floats, **f32)
-        run(post[key], person, item, ws, ws_floats)
-        return {"person": dict(zip(PERSON_SUMS, person.unbind(0))), "item": dict(zip(ITEM_SUMS, item.unbind(0))), name: post[key]}
+        run(est, person, item, ws, ws_floats)
+        out = {"person": dict(zip(PERSON_SUMS, person.unbind(0))), "item": dict(zip(ITEM_SUMS, item.unbind(0))), name: est}
+        if bad is not None:
+            out["no_estimate"] = bad
+        return out
 
-    def person_fit(self, y_u8=None, rows=None, **grid_kw):
+    def person_fit(self, y_u8=None, rows=None, at="eap", **grid_kw):
         """Person fit of the scored rows (person_fit_host over fit_sums), numpy: `lz`, `infit`, `outfit` float64 (n,), `n_obs`
         int64, `loglik0`, `expected`, `variance` (the l0, e, v of lz) and `theta_hat` or `pattern`.  lz is taken at the estimate
         without Snijders' correction: on short tests its null distribution is somewhat narrower than N(0, 1).  NaN where a
-        person answered nothing.  With a process group: this rank's shard, as score()."""
-        t = self.fit_sums(y_u8, rows, **grid_kw)
+        person answered nothing.  With a process group: this rank's shard, as score().
+        at: "eap" (default) or "wle" | "ml" | "map" (IrtEngine): the statistics at the theta_hat of point_estimates(method=at) --
+        the estimate lz and the mean squares are defined at; a person whose estimate has status `empty` or `singular` gets NaN
+        in lz, infit, outfit and theta_hat."""
+        t = self.fit_sums(y_u8, rows, at=at, **grid_kw)
         s = {k: v.cpu().numpy() for k, v in t["person"].items()}
         out = person_fit_host(s)
         out["n_obs"] = np.rint(s["n"]).astype(np.int64)
         out["loglik0"], out["expected"], out["variance"] = (s[k].astype(np.float64) for k in ("l0", "e", "v"))
         name = "theta_hat" if "theta_hat" in t else "pattern"
         out[name] = t[name].cpu().numpy()
+        if "no_estimate" in t:
+            bad = t["no_estimate"].cpu().numpy()
+            for k in ("lz", "infit", "outfit", "theta_hat"):
+                out[k][bad] = np.nan
         return out
 
-    def item_msq(self, y_u8=None, rows=None, **grid_kw):
+    def item_msq(self, y_u8=None, rows=None, at="eap", **grid_kw):
         """The residual mean squares of every item over the scored rows (item_msq_host over fit_sums), numpy: `infit`, `outfit`
-        float64 (J,) and `n_obs` int64; NaN for an item nobody answered.  One rank only."""
+        float64 (J,) and `n_obs` int64; NaN for an item nobody answered.  One rank only.  at: as fit_sums() has it."""
         self._one_rank_only("item_msq over a process group: fit_sums() gives the local shard's sums; the cross-rank sum is not "
                             "built")
-        s = {k: v.cpu().numpy() for k, v in self.fit_sums(y_u8, rows, **grid_kw)["item"].items()}
+        s = {k: v.cpu().numpy() for k, v in self.fit_sums(y_u8, rows, at=at, **grid_kw)["item"].items()}
         out = item_msq_host(s)
         out["n_obs"] = np.rint(s["n"]).astype(np.int64)
         return out

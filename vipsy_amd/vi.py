@@ -210,6 +210,19 @@ class BasePsy(object):
         VCCDM: attr_prob, pattern, loglik (CcdmEngine.score).  The other classes refuse."""
         return self.engine.score(self._score_data(data), **kw)
 
+    def point_estimates(self, data=None, **kw):
+        """Likelihood-based person scores of the persons in `data` (None: the training data; with a `group` this rank's shard, as
+        score()), ready to print: Warm's weighted likelihood estimate (method="wle", the default: what PISA, TIMSS, ConQuest and
+        TAM report), the maximum-likelihood ("ml") or the MAP ("map") estimate, by Fisher scoring from the EAP of score() under
+        the item parameters as they stand.  A dict of numpy arrays: theta_hat, se [persons, x_feature], cov, info [persons,
+        x_feature, x_feature], status (0 converged, 1 at_bound, 2 max_iter, 3 singular, 4 empty: vipsy_amd.grid.POINT_STATUS),
+        iterations, n_converged and reliability [x_feature], the person separation reliability 1 - mean(se^2) / var(theta_hat)
+        (IrtEngine.point_estimates: method, max_iter=32, tol=1e-6, bound=None (= span), nodes=61, span=6.0).  An all-correct or
+        all-wrong row has no finite ML estimate: it ends at_bound, on +-bound; the WLE and the MAP of such a row are finite.
+        VIRT / VaeIRT, every IRT model: x_feature <= 3 for "ml" and "map", x_feature = 1 for "wle"; covariates= is not built.
+        VCCDM refuses: its point estimate is the MAP pattern of score().  The other classes refuse as for score()."""
+        return self.engine.point_estimates(self._score_data(data), **kw)
+
     def plausible_values(self, data=None, **kw):
         """Plausible values: draws of each person's latent from the exact grid posterior of score() (`data` None: the training
         data; with a `group` this rank's shard, keyed by global person id) -- VIRT / VaeIRT with x_feature <= 3: theta
@@ -331,7 +344,8 @@ class BasePsy(object):
         and `sp` (the sum of the products of the two items' residuals), beside `theta_hat` or `pattern`.  The residuals y - P are
         taken at each person's point estimate -- the EAP of score() for VIRT / VaeIRT (every model, x_feature <= 3), the MAP
         pattern for VCCDM -- under the item parameters as they stand; pairs are pairwise-complete: a missing cell takes its person
-        out of that item's pairs only.  `data`: None = the training data.  The other classes refuse.  One rank only."""
+        out of that item's pairs only.  `data`: None = the training data.  The other classes refuse.  One rank only.
+        at="wle" | "ml" | "map" (VIRT / VaeIRT): the residuals at that point_estimates() score instead of the EAP."""
         if self.world > 1:
             raise NotImplementedError("residual_sums with a group of %d ranks: the tables are the sums over the local shard's "
                                       "persons; the cross-rank sum is not built" % self.world)
@@ -346,7 +360,8 @@ class BasePsy(object):
         the diagonal) and `item_j`, `item_k`, `value`, the `top` (20) pairs by |q3 - mean| (GridMixin.local_dependence).  NaN in
         `q3` means no statistic: fewer than `min_pairs` (8) persons answered both items, or one item's residuals have no spread
         over them (an item nobody answered among them).  `data`: None = the training data.  The other classes refuse.  One
-        rank only."""
+        rank only.  at="wle" | "ml" | "map" (VIRT / VaeIRT): Q3 at that point_estimates() score instead of the EAP (the default,
+        at="eap"); a person without such an estimate (status empty or singular) enters with its EAP."""
         if self.world > 1:
             raise NotImplementedError("local_dependence with a group of %d ranks: the tables are the sums over the local shard's "
                                       "persons; the cross-rank sum is not built" % self.world)
@@ -368,7 +383,10 @@ class BasePsy(object):
         1 under the model), `n_obs` (int64, the answered items), `loglik0`, `expected`, `variance` (the log-likelihood at the
         estimate, its mean and its variance under the model: lz = (loglik0 - expected) / sqrt(variance)) and `theta_hat` or
         `pattern`.  lz is taken at the estimate WITHOUT Snijders' correction: its null distribution is somewhat narrower than
-        N(0, 1) on short tests.  NaN for a person who answered nothing.  The other classes refuse."""
+        N(0, 1) on short tests.  NaN for a person who answered nothing.  The other classes refuse.
+        at="wle" | "ml" | "map" (VIRT / VaeIRT): the statistics at that point_estimates() score -- the likelihood-based estimate
+        lz and the mean squares are defined at -- instead of the EAP (the default, at="eap", whose shrinkage biases the residuals
+        of extreme persons); NaN then also for a person without such an estimate (status empty or singular)."""
         return self.engine.person_fit(self._score_data(data), **grid_kw)
 
     def item_msq(self, data=None, **grid_kw):
