@@ -40,7 +40,7 @@ SE_IDS = [c[0][0] for c in SE_CASES]
 INFO_CASES = [c for c in sc.IRT_CASES if c[3] in ("irt_1pl", "irt_2pl")] + list(sc.CDM_CASES) + [cc.COUNT_WIDE]
 INFO_IDS = [c[0] for c in INFO_CASES]
 CONDITION_MAX = 1e3
-SLAB = 256                       # GI_SLAB (vipsy_amd/csrc/k_grid_info.hip)
+SLAB = 256                       # GRID_SLAB (vipsy_amd/csrc/grid_plan.h)
 
 
 def case_of(case):

@@ -213,7 +213,7 @@ def test_one_node():
 
 @pytest.mark.parametrize("idx", [0, 5], ids=[se.SE_IDS[0], se.SE_IDS[5]])
 def test_info_workspace_between_the_smallest_and_the_preferred(idx):
-    """vx_grid_info with the workspace that is the preferred one of 1 024 persons.  By gi_plan (k_grid_info.hip) a slab then holds
+    """vx_grid_info with the workspace that is the preferred one of 1 024 persons.  By gi_slab_plan (grid_plan.h) a slab then holds
     1 024 persons = 32 units of 32 in four chunks of eight units: the 2 500 persons (P 74, PT 3, one workgroup block) go as
     slabs of 1 024, 1 024 and 452, the 1 500 of se_dina_k3 (P 40, PT 2) as 1 024 and 476.  The last slab has 16 units (eight of 64
     persons from k_grid_pscores), so its chunks 2 and 3 run k_grid_xprod over an empty unit range and must leave exact zero tiles

@@ -29,36 +29,10 @@
 #pragma once
 #include "k_grid_post.hip"
 
-#define GC_THREADS 512
-#define GC_WAVES (GC_THREADS / 64)
-#define GC_ROUND (32 * GC_WAVES)        // persons a workgroup takes at a time
+// GC_THREADS, GC_WAVES, GC_ROUND and the launch for (nb, J, G) -- GcPlan, gc_plan -- are in grid_plan.h
 #define GC_PSCALE 16384.0f              // 2^14 into the fp16 split of p ...
 #define GC_PUNSCALE 6.103515625e-05f    // ... and off the fp32 accumulators (exact)
-#define GC_MAX_BLOCKS 256               // workgroups of a launch, about (the plan is the same on every device)
-#define GC_MIN_ROUNDS 4                 // rounds a chunk has before the persons are split further
 
-// The launch for (nb, J, G): template instance, grid and slab layout -- host arithmetic only, in int64.
-struct GcPlan {
-    int it, ntg;                        // item tiles a wave (1, 2, 4), node tiles a workgroup (2; 1 beyond 512 items)
-    int n_groups;                       // node groups
-    int64_t rounds_per_chunk, n_chunks; // persons: chunks of rounds_per_chunk * GC_ROUND
-    int64_t slab_len;                   // 2 J G + G
-};
-inline GcPlan gc_plan(int64_t nb, int J, int G) {
-    GcPlan p;
-    const int nit = (J + 31) / 32;
-    p.it = nit <= GC_WAVES ? 1 : (nit <= 2 * GC_WAVES ? 2 : 4);
-    p.ntg = p.it == 4 ? 1 : 2;
-    p.n_groups = (gp_nt(G) + p.ntg - 1) / p.ntg;
-    const int64_t rounds = (nb + GC_ROUND - 1) / GC_ROUND;
-    int64_t chunks = (rounds + GC_MIN_ROUNDS - 1) / GC_MIN_ROUNDS;
-    const int64_t cap = GC_MAX_BLOCKS / p.n_groups > 1 ? GC_MAX_BLOCKS / p.n_groups : 1;
-    if (chunks > cap) chunks = cap;
-    p.rounds_per_chunk = (rounds + chunks - 1) / chunks;
-    p.n_chunks = (rounds + p.rounds_per_chunk - 1) / p.rounds_per_chunk;
-    p.slab_len = 2 * (int64_t)J * G + G;
-    return p;
-}
 template <int NTG>
 constexpr size_t gc_lds_bytes() {
     // p fragments [waves][NTG][2 k-steps][head, low][64 lanes] x 16 B; rows int64 [waves][32]; miss, loglik [waves][32];

@@ -44,48 +44,7 @@
 #define GCC_MAXSEG 4096                 // segments of a call
 #define GCC_TAB_VALUES 256              // int64 values a k_gcc_table launch carries in its arguments (2 KiB)
 
-// The launch for (nb, n_seg, J, G): gc_plan(nb, J, G) for the template instance, the node groups and rounds_per_chunk.
-// max_chunks bounds the chunks of ANY cut of nb persons into n_seg segments: a cut adds at most one round, and the rounding up
-// of every segment's rounds to chunks at most one chunk a segment -- n_chunks(nb) + 2 (n_seg - 1), n_chunks(nb) for one segment.
-struct GccPlan {
-    GcPlan gc;
-    int64_t max_chunks;
-    int64_t tab_floats;                 // the table at the head of the workspace, in floats, padded to 16 bytes
-};
-inline GccPlan gcc_plan(int64_t nb, int n_seg, int J, int G) {
-    GccPlan p;
-    p.gc = gc_plan(nb, J, G);
-    p.max_chunks = p.gc.n_chunks + 2 * (int64_t)(n_seg - 1);
-    p.tab_floats = ((2 * ((int64_t)n_seg + 1) * 2 + 3) / 4) * 4;
-    return p;
-}
-// chunks of a segment of `len` persons at `rounds_per_chunk` rounds a chunk at most
-inline int64_t gcc_chunks(int64_t len, int64_t rounds_per_chunk) {
-    const int64_t rounds = (len + GC_ROUND - 1) / GC_ROUND;
-    return (rounds + rounds_per_chunk - 1) / rounds_per_chunk;
-}
-inline int64_t gcc_total_chunks(const int64_t* seg_start, int n_seg, int64_t rounds_per_chunk) {
-    int64_t c = 0;
-    for (int s = 0; s < n_seg; ++s) c += gcc_chunks(seg_start[s + 1] - seg_start[s], rounds_per_chunk);
-    return c;
-}
-// The rounds a chunk may have in this cut: gc_plan's, raised (bisection: the total falls as it rises) until the chunks of all
-// segments are no more than gc_plan's cap of workgroups -- many short segments would otherwise leave more workgroups than the
-// chip holds at once, each with a short tail chunk.  One segment: gc_plan's value, its chunks being within the cap already.
-inline int64_t gcc_rounds_per_chunk(const int64_t* seg_start, int n_seg, const GcPlan& gc) {
-    const int64_t cap = GC_MAX_BLOCKS / gc.n_groups > 1 ? GC_MAX_BLOCKS / gc.n_groups : 1;
-    int64_t lo = gc.rounds_per_chunk, hi = lo;
-    if (gcc_total_chunks(seg_start, n_seg, lo) <= cap) return lo;
-    for (int s = 0; s < n_seg; ++s) {
-        const int64_t r = (seg_start[s + 1] - seg_start[s] + GC_ROUND - 1) / GC_ROUND;
-        if (r > hi) hi = r;
-    }
-    while (hi - lo > 1) {                                                         // total(lo) > cap; hi: within it, or the most there is
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (gcc_total_chunks(seg_start, n_seg, mid) <= cap) hi = mid; else lo = mid;
-    }
-    return hi;
-}
+// The launch for (nb, n_seg, J, G) -- GccPlan, gcc_plan, gcc_chunks, gcc_rounds_per_chunk -- is in grid_plan.h
 template <int NTG>
 constexpr size_t gcc_lds_bytes() { return gc_lds_bytes<NTG>() + (size_t)GPC_MAXD * GC_ROUND * 4; }
 

@@ -35,24 +35,9 @@
 #pragma once
 #include "k_grid_pairs.hip"
 
+// the launch of a call -- GfPlan, gf_plan, gf_ws_floats -- is in grid_plan.h, with GF_MAX_BLOCKS and GF_ITEM (n, sr2, sw, sz2)
 #define GF_MAXD PP_MAXD
-#define GF_MAX_BLOCKS 1024              // workgroups of a launch at the most: 32 768 persons before a workgroup takes a second unit
 #define GF_PERSON 7                     // n, l0, e, v, sr2, sw, sz2
-#define GF_ITEM 4                       // n, sr2, sw, sz2
-
-// the launch of a call (host arithmetic): units of 32 persons in contiguous chunks, one chunk a workgroup
-struct GfPlan {
-    int64_t n_units, units_per_block, n_blocks;
-};
-inline GfPlan gf_plan(int64_t nb) {
-    GfPlan p;
-    p.n_units = (nb + 31) / 32;
-    const int64_t cap = p.n_units < GF_MAX_BLOCKS ? p.n_units : GF_MAX_BLOCKS;
-    p.units_per_block = (p.n_units + cap - 1) / cap;
-    p.n_blocks = (p.n_units + p.units_per_block - 1) / p.units_per_block;
-    return p;
-}
-inline int64_t gf_ws_floats(int64_t nb, int J) { return gf_plan(nb).n_blocks * GF_ITEM * (int64_t)J; }
 
 // what a cell adds, for either answer: everything but l, r2 and zeta is the same for both
 struct GfTerms {

@@ -29,72 +29,23 @@
 //             (vx_reduce_slabs), the slabs of a call in person order (k_info_add), no float atomics: the same call gives the same
 //             bits.  k_info_finish takes the scale off, writes the upper triangle and its mirror (a diagonal tile's upper half
 //             only: the matrix is symmetric bit for bit) and the gradient.
+// Persons a slab, chunks a slab and the parts of the workspace are slab_plan's (SlabPlan, grid_plan.h: the one plan this file and
+// k_grid_pairs.hip share), walked by grid_slab_loop (vx_abi.hip).
 #pragma once
 #include "k_grid_counts.hip"
 #include "k_grid_mstep.hip"
 
+// GI_BT, GI_TILE, GI_MAX_BLOCKS, gi_pt, gi_pairs and gi_pair_index are in grid_plan.h, beside gi_slab_plan
 #define GI_MAXP 4096
 #define GI_MAXK 4
-#define GI_BT 4                         // parameter tiles a side of a workgroup's block in k_grid_xprod (one row a wave)
-#define GI_SLAB 256                     // a slab's persons are a multiple of this
-#define GI_TILE 1024                    // floats of a 32 x 32 tile
-#define GI_MAX_BLOCKS 1024              // workgroups of a k_grid_xprod launch, about
 #define GI_LDS_NT 16                    // node tiles up to which the LDS holds p of both person tiles of a unit
 
-__host__ __device__ inline int gi_pt(int P) { return (P + 32) / 32; }              // tiles of P + 1 columns
-__host__ __device__ inline int64_t gi_pairs(int PT) { return (int64_t)PT * (PT + 1) / 2; }
 __host__ __device__ inline int64_t gi_wimage_frag_bytes(int P, int G) { return (int64_t)gp_nt(G) * 2 * gi_pt(P) * 4 * 64 * 16; }
-__host__ __device__ inline int64_t gi_pair_index(int PT, int pa, int pb) { return (int64_t)pa * PT - (int64_t)pa * (pa - 1) / 2 + (pb - pa); }
 inline int gi_nsub(int G) { return gp_nt(G) > GI_LDS_NT ? 2 : 1; }
 inline size_t gi_lds_bytes(int G) {
     const int NT = gp_nt(G);
     // p fragments [person tiles kept][NT][2 k-steps][head, low][64 lanes] x 16 B; logw [NT * 32]; rows int64 [64]
     return (size_t)(GP_MT / gi_nsub(G)) * NT * 4 * 64 * 16 + (size_t)NT * 32 * 4 + 64 * 8;
-}
-
-// The slabs of a call (host arithmetic, int64): persons a slab, chunks of a slab's 32-person units, and where the parts of the
-// workspace start: [S of a slab][chunk partials][their sum][the running sum of the slabs]
-struct GiPlan {
-    int PT, nbb;
-    int64_t n_pairs, n_bp;              // tile pairs; workgroup blocks of the upper triangle
-    int64_t slab_persons, n_chunks, units_per_chunk;
-    int64_t off_part, off_red, off_acc, total;
-};
-inline int64_t gi_chunks_for(int64_t m256, int64_t n_bp) {
-    const int64_t cap = GI_MAX_BLOCKS / n_bp > 1 ? GI_MAX_BLOCKS / n_bp : 1;
-    return m256 < cap ? m256 : cap;
-}
-inline int64_t gi_need(int PT, int64_t m256, int64_t chunks) {
-    return (m256 * 8 * PT + (chunks + 2) * gi_pairs(PT)) * GI_TILE;
-}
-inline int64_t gi_min_floats(int P) { return gi_need(gi_pt(P), 1, 1); }
-// ws_floats < 0: the preferred size (everything in one slab, as far as 512 MB go)
-inline GiPlan gi_plan(int64_t nb, int P, int64_t ws_floats) {
-    GiPlan p;
-    p.PT = gi_pt(P);
-    p.nbb = (p.PT + GI_BT - 1) / GI_BT;
-    p.n_pairs = gi_pairs(p.PT);
-    p.n_bp = (int64_t)p.nbb * (p.nbb + 1) / 2;
-    int64_t m = (nb + GI_SLAB - 1) / GI_SLAB;
-    if (ws_floats < 0) {
-        ws_floats = (int64_t)128 << 20;
-        if (ws_floats < gi_min_floats(P)) ws_floats = gi_min_floats(P);
-    }
-    const int64_t per256 = (int64_t)8 * p.PT * GI_TILE;
-    const int64_t m_cap = (ws_floats - 3 * p.n_pairs * GI_TILE) / per256;      // with one chunk
-    if (m > m_cap) m = m_cap;
-    while (m > 1 && gi_need(p.PT, m, gi_chunks_for(m, p.n_bp)) > ws_floats) --m;
-    if (m < 1) m = 1;
-    int64_t chunks = gi_chunks_for(m, p.n_bp);
-    const int64_t units = m * 8;
-    p.slab_persons = m * GI_SLAB;
-    p.units_per_chunk = (units + chunks - 1) / chunks;
-    p.n_chunks = (units + p.units_per_chunk - 1) / p.units_per_chunk;
-    p.off_part = units * p.PT * GI_TILE;
-    p.off_red = p.off_part + p.n_chunks * p.n_pairs * GI_TILE;
-    p.off_acc = p.off_red + p.n_pairs * GI_TILE;
-    p.total = p.off_acc + p.n_pairs * GI_TILE;
-    return p;
 }
 
 // one cell -> its four fp16 words in the W image (values already scaled)

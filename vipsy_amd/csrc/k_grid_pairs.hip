@@ -24,71 +24,20 @@
 //   sums      the chunks' partial tiles are added in ascending order (vx_reduce_slabs), the slabs of a call in person order
 //             (k_info_add), no atomics: the same call with the same workspace size gives the same bits.  k_pair_finish takes the
 //             scales off (2^-20 for sp, 2^-10 for s and ss) and writes the upper triangle with its mirror (n, sp) or its transpose
-//             partner (s, ss).
+//             partner (s, ss).  Persons a slab, chunks a slab and the parts of the workspace are slab_plan's (SlabPlan,
+//             grid_plan.h: the one plan vx_grid_info shares), walked by the same grid_slab_loop (vx_abi.hip).
 // n is exact while a call scores at most 2^24 persons (fp32 counts).
 #pragma once
 #include "k_grid_info.hip"
 
-#define PP_BT 2                         // item tiles a side of a workgroup's block in k_pair_xprod
+// PP_BT, PP_OPS, PP_ACC, PP_MAX_BLOCKS, PP_UNIT_FLOATS and pp_jt are in grid_plan.h, beside pp_slab_plan
 #ifndef PP_BC
 #define PP_BC 1                         // column tiles of the block a wave holds against its row tile (PP_BT / PP_BC waves a row)
 #endif
 #define PP_XWAVES (PP_BT * (PP_BT / PP_BC))
-#define PP_OPS 5                        // fragments a k-step: r head, r low, r^2 head, r^2 low, m
-#define PP_ACC 6                        // accumulator tiles a tile pair: sp, n, s row, ss row, s column, ss column
-#define PP_SLAB 256                     // a slab's persons are a multiple of this
-#define PP_MAX_BLOCKS 2048              // workgroups of a k_pair_xprod launch, about
 #define PP_MAXD 3
 #define PP_SCALE 1024.0f                // 2^10 into the fp16 split of r and r^2 ...
 #define PP_UNSCALE 0.0009765625f        // ... and off the sums (exact)
-#define PP_UNIT_FLOATS(JT) ((int64_t)(JT) * 2 * PP_OPS * 64 * 4)      // floats of a unit's fragments
-
-__host__ __device__ inline int pp_jt(int J) { return (J + 31) / 32; }
-
-// The slabs of a call (host arithmetic, int64), as GiPlan: [fragments of a slab][chunk partials][their sum][the running sum]
-struct PpPlan {
-    int JT, nbb;
-    int64_t n_pairs, n_bp;
-    int64_t slab_persons, n_chunks, units_per_chunk;
-    int64_t tiles_len, off_part, off_red, off_acc, total;
-};
-inline int64_t pp_chunks_for(int64_t m256, int64_t n_bp) {
-    const int64_t cap = PP_MAX_BLOCKS / n_bp > 1 ? PP_MAX_BLOCKS / n_bp : 1;
-    return m256 < cap ? m256 : cap;
-}
-inline int64_t pp_need(int JT, int64_t m256, int64_t chunks) {
-    return m256 * 8 * PP_UNIT_FLOATS(JT) + (chunks + 2) * gi_pairs(JT) * PP_ACC * GI_TILE;
-}
-inline int64_t pp_min_floats(int J) { return pp_need(pp_jt(J), 1, 1); }
-// ws_floats < 0: the preferred size (everything in one slab, as far as 512 MB go)
-inline PpPlan pp_plan(int64_t nb, int J, int64_t ws_floats) {
-    PpPlan p;
-    p.JT = pp_jt(J);
-    p.nbb = (p.JT + PP_BT - 1) / PP_BT;
-    p.n_pairs = gi_pairs(p.JT);
-    p.n_bp = (int64_t)p.nbb * (p.nbb + 1) / 2;
-    p.tiles_len = p.n_pairs * PP_ACC * GI_TILE;
-    int64_t m = (nb + PP_SLAB - 1) / PP_SLAB;
-    if (ws_floats < 0) {
-        ws_floats = (int64_t)128 << 20;
-        if (ws_floats < pp_min_floats(J)) ws_floats = pp_min_floats(J);
-    }
-    const int64_t per256 = 8 * PP_UNIT_FLOATS(p.JT);
-    const int64_t m_cap = (ws_floats - 3 * p.tiles_len) / per256;            // with one chunk
-    if (m > m_cap) m = m_cap;
-    while (m > 1 && pp_need(p.JT, m, pp_chunks_for(m, p.n_bp)) > ws_floats) --m;
-    if (m < 1) m = 1;
-    const int64_t chunks = pp_chunks_for(m, p.n_bp);
-    const int64_t units = m * 8;
-    p.slab_persons = m * PP_SLAB;
-    p.units_per_chunk = (units + chunks - 1) / chunks;
-    p.n_chunks = (units + p.units_per_chunk - 1) / p.units_per_chunk;
-    p.off_part = units * PP_UNIT_FLOATS(p.JT);
-    p.off_red = p.off_part + p.n_chunks * p.tiles_len;
-    p.off_acc = p.off_red + p.tiles_len;
-    p.total = p.off_acc + p.tiles_len;
-    return p;
-}
 
 // the five fragments of one k-step from a lane's eight cells: rv = the residuals (0 where not observed), ob = observed
 __device__ __forceinline__ void pp_store(uint4* __restrict__ dst, const float (&rv)[8], const bool (&ob)[8]) {

@@ -26,6 +26,7 @@
 #pragma once
 #include "vx_common.h"
 #include "k_hodina.hip"
+#include "grid_plan.h"                   // gp_nt, and the launch plans of the family
 
 #define GP_THREADS 256
 #define GP_WAVES (GP_THREADS / 64)
@@ -39,7 +40,6 @@
 #define GP_NEG (-3.0e38f)        // "no node yet": below every reachable log-weight + log-likelihood (>= -1024 * 16 - 88)
 
 __host__ __device__ inline int gp_kc(int J) { return (J + 15) / 16; }
-__host__ __device__ inline int gp_nt(int G) { return (G + 31) / 32; }
 __host__ __device__ inline int64_t gp_image_bytes(int J, int G) { return (int64_t)gp_nt(G) * gp_kc(J) * 4 * 64 * 16; }
 
 // one table cell -> its four fp16 words in the image

@@ -27,32 +27,15 @@
 // integer atomic when the score changes and at the end of the chunk (integer sums are the same in any order).
 #pragma once
 #include "k_util.hip"
+#include "grid_plan.h"                  // the launch of vx_sumscore_model: SsPlan, ss_plan, ss_ws_floats
 
 #define SS_MAXJ 1023                    // items of a call: the score vector has Js + 1 <= 1024 entries, 16 registers a lane
 #define SS_MAXG 1024                    // nodes (GP_MAXG)
 #define SS_MAXJ_ALL 4096                // columns of y
 #define SS_WAVES 4                      // waves a workgroup
-#define SS_TARGET_WAVES 8192            // waves of the leave-one-out launch where the nodes allow: 8 a SIMD on 256 CUs
 #define SS_OBS_THREADS 256
 #define SS_OBS_TILES 4                  // items a thread of k_sumscore_observed owns at the most: 4 x 256 >= 1023
 #define SS_OBS_MAX_BLOCKS 2048
-
-// the launch of a call (host arithmetic): registers a lane, and the nodes in contiguous chunks
-struct SsPlan {
-    int R, chunk, n_chunks;
-};
-inline SsPlan ss_plan(int Js, int G) {
-    SsPlan p;
-    p.R = 1;
-    while (64 * p.R < Js + 1) p.R *= 2;
-    int want = (SS_TARGET_WAVES + Js - 1) / Js;
-    if (want > G) want = G;
-    p.chunk = (G + want - 1) / want;
-    p.n_chunks = (G + p.chunk - 1) / p.chunk;
-    return p;
-}
-// [e1 slabs: n_chunks x Js (Js + 1) | e0 slabs: the same]
-inline int64_t ss_ws_floats(int Js, int G) { return 2 * (int64_t)ss_plan(Js, G).n_chunks * Js * (Js + 1); }
 
 // the value of lane - 1; lane 0 receives 0
 __device__ __forceinline__ float ss_shift_up(float v) {

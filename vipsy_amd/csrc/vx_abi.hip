@@ -304,6 +304,98 @@ int with_last_round(SideStream* side, hipStream_t st, Tail&& tail, Whole&& whole
     rc = beside ? whole() : tail(st);
     return rc ? rc : fork.join();
 }
+
+// ---- what the entries of the grid family (vx_grid_*, vx_sumscore_*) share: an entry is a gate, a plan (grid_plan.h), a launch ----
+bool hodina_cfg_ok(const vx_hodina_cfg* cfg) { return cfg && cfg->K >= 1 && cfg->K <= 10 && cfg->J >= 1 && cfg->J <= 1024; }
+// The item parameters of an IRT entry: the model within 1 (1PL: D = 1, a = 1) .. max_model (2: 2PL, 3: + c_un, 4: + d_un), D within
+// the entry's limit, and every array the model reads
+bool irt_items_ok(const vx_irt_cfg* cfg, int max_model, int max_D, const float* a, const float* b, const float* c_un, const float* d_un) {
+    if (!cfg || cfg->model < 1 || cfg->model > max_model || cfg->D < 1 || cfg->D > max_D || !b) return false;
+    return !((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un));
+}
+// The item parameters of a DINA / DINO entry
+bool cdm_items_ok(const vx_hodina_cfg* cfg, int dino, const float* q, const float* g_un, const float* s_un) {
+    return hodina_cfg_ok(cfg) && cfg->K <= GP_MAXD && cfg->J <= GP_MAXJ && (dino == 0 || dino == 1) && q && g_un && s_un;
+}
+// The draws [draw0, draw0 + ndraws) of a plausible-value entry, `stride` slots a person
+bool draw_range_ok(int32_t draw0, int32_t ndraws, int64_t stride) {
+    return draw0 >= 0 && draw0 <= PV_MAXDRAWS && ndraws >= 1 && ndraws <= PV_MAXDRAWS && draw0 + ndraws <= PV_MAXDRAWS &&
+           (int64_t)draw0 + ndraws <= stride;
+}
+// cfg->model (1 .. 4, checked) as the MODEL of a kernel template: f(std::integral_constant<int, MODEL>) launches the instance
+template <typename F>
+int with_irt_model(int model, F&& f) {
+    switch (model) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        default: return f(std::integral_constant<int, 4>());
+    }
+}
+// GcPlan::it as the (IT, NTG) of k_grid_counts / k_grid_counts_cond: four item tiles a wave leave registers for one node tile only
+template <typename F>
+int with_counts_tiles(int it, F&& f) {
+    switch (it) {
+        case 1: return f(std::integral_constant<int, 1>(), std::integral_constant<int, 2>());
+        case 2: return f(std::integral_constant<int, 2>(), std::integral_constant<int, 2>());
+        default: return f(std::integral_constant<int, 4>(), std::integral_constant<int, 1>());
+    }
+}
+// The tail of both expected-count entries: reduce(offset, len, out) launches the entry's sum over the chunks' slabs for each of the
+// columns [n1 | n0 | mass]
+template <typename Reduce>
+int counts_reduce(int J, int G, float* n1, float* n0, float* mass, Reduce&& reduce) {
+    const int64_t JG = (int64_t)J * G, offs[3] = {0, JG, 2 * JG}, lens[3] = {JG, JG, (int64_t)G};
+    float* const outs[3] = {n1, n0, mass};
+    for (int k = 0; k < 3; ++k) {
+        reduce(offs[k], lens[k], outs[k]);
+        VX_CHECK_LAUNCH();
+    }
+    return VX_OK;
+}
+// The slab loop of vx_grid_info and vx_grid_pairs_* (SlabPlan, grid_plan.h).  For each slab of persons [i0, i0 + ns): frag(i0, ns)
+// launches the entry's fragment kernel into the head of the workspace and returns the 32-person units it wrote; `xprod` (the
+// cross products of those units, `xthreads` a workgroup) leaves a set of partial tiles a chunk; the chunks are added in ascending
+// order, the slabs in person order.  finish() launches what turns the running sum into the entry's outputs.
+using SlabXprod = void (*)(const uint4*, int, int, int64_t, int64_t, float*, int64_t);
+template <typename Frag, typename Finish>
+int grid_slab_loop(const SlabPlan& p, int64_t nb, float* workspace, void* hs, SlabXprod xprod, int xthreads, Frag&& frag,
+                   Finish&& finish) {
+    hipStream_t st = (hipStream_t)hs;
+    float *part = workspace + p.off_part, *red = workspace + p.off_red, *acc = workspace + p.off_acc;
+    for (int64_t i0 = 0; i0 < nb; i0 += p.slab_persons) {
+        const int64_t ns = nb - i0 < p.slab_persons ? nb - i0 : p.slab_persons;
+        const int64_t n_units = frag(i0, ns);
+        VX_CHECK_LAUNCH();
+        hipLaunchKernelGGL(xprod, dim3((unsigned)(p.n_bp * p.n_chunks)), dim3(xthreads), 0, st, (const uint4*)workspace, p.tiles, p.nbb,
+                           n_units, p.units_per_chunk, part, p.tiles_len);
+        VX_CHECK_LAUNCH();
+        const int rc = vx_reduce_slabs(part, p.n_chunks, p.tiles_len, 1.0f, red, hs);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_info_add, dim3(grid_1d(p.tiles_len, 256)), dim3(256), 0, st, acc, (const float*)red, p.tiles_len,
+                           i0 == 0 ? 1 : 0);
+        VX_CHECK_LAUNCH();
+    }
+    finish();
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+// vx_grid_pairs_irt / vx_grid_pairs_cdm on that loop: launch(i0, ns, n_units, grid) launches the entry's cell kernel (k_pair_frag*)
+// over the n_units = ceil(ns / 32) units of a slab
+template <typename Launch>
+int grid_pairs_run(int64_t nb, int J, float* n, float* s, float* ss, float* sp, float* workspace, int64_t ws_floats, void* hs,
+                   Launch&& launch) {
+    const SlabPlan p = pp_slab_plan(nb, J, ws_floats);
+    auto frag = [&](int64_t i0, int64_t ns) -> int64_t {
+        const int64_t n_units = (ns + 31) / 32, cap = (int64_t)num_cu() * 8;
+        launch(i0, ns, n_units, dim3((unsigned)(n_units < cap ? n_units : cap)));
+        return n_units;
+    };
+    return grid_slab_loop(p, nb, workspace, hs, k_pair_xprod, 64 * PP_XWAVES, frag, [&] {
+        hipLaunchKernelGGL(k_pair_finish, dim3(grid_1d((int64_t)J * J, 256)), dim3(256), 0, (hipStream_t)hs,
+                           (const float*)(workspace + p.off_acc), J, p.tiles, n, s, ss, sp);
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -2045,10 +2137,6 @@ int vx_norm_enc_backward(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t*
 }
 
 // ------------------------------------------------------------------------------------------------
-static bool hodina_cfg_ok(const vx_hodina_cfg* cfg) {
-    return cfg && cfg->K >= 1 && cfg->K <= 10 && cfg->J >= 1 && cfg->J <= 1024;
-}
-
 // per wave a [C] table of 64-bit fixed-point sums (also used as a float table); the block reduce needs [waves][len] floats
 static size_t hodina_lds_bytes(int C, int len) {
     const size_t tab = (size_t)HD_WAVES * C * sizeof(long long), red = (size_t)HD_WAVES * len * sizeof(float);
@@ -2163,10 +2251,14 @@ int vx_ccdm_grad(const vx_hodina_cfg* cfg, int32_t dino, const uint8_t* y, const
 // ------------------------------------------------------------------------------------------------
 // Person scores on a grid of latent nodes (k_grid_post.hip): two table builders and one kernel
 
-// the shape limits every vx_grid_* entry shares (entries without persons pass nb = 1)
+// the persons of a call at the most, and the floats of a workspace it is handed
+static const int64_t GRID_MAX_PERSONS = (int64_t)1 << 48;
+// the shape limits of the entries that score against a node table (entries without persons pass nb = 1) ...
 static bool grid_shape_ok(int64_t J, int64_t G, int64_t nb) {
-    return J >= 1 && J <= GP_MAXJ && G >= 1 && G <= GP_MAXG && nb >= 1 && nb <= ((int64_t)1 << 48);
+    return J >= 1 && J <= GP_MAXJ && G >= 1 && G <= GP_MAXG && nb >= 1 && nb <= GRID_MAX_PERSONS;
 }
+// ... and of those that score at a point a person: vx_grid_pairs_*, vx_grid_fit_*, vx_grid_point_irt
+static bool grid_point_shape_ok(int64_t J, int64_t nb) { return J >= 1 && J <= GP_MAXJ && nb >= 1 && nb <= GRID_MAX_PERSONS; }
 // cells of the operand image, its zero padding included: what a table builder fills
 static int64_t grid_image_cells(int J, int G) { return (int64_t)gp_nt(G) * 32 * gp_kc(J) * 16; }
 // blocks of a person-on-lane launch (k_grid_post, k_grid_draw): a wave takes units of 32 * GP_MT persons, and the launch stops
@@ -2184,28 +2276,20 @@ int64_t vx_grid_image_bytes(int32_t J, int32_t G) {
 
 int vx_grid_table_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* a, const float* b, const float* c_un,
                       const float* d_un, void* img, void* hs) {
-    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GP_MAXD || !grid_shape_ok(cfg->J, G, 1) || !theta || !b ||
-        !img || !aligned16(img))
-        return VX_EINVAL;
-    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
+    if (!irt_items_ok(cfg, 4, GP_MAXD, a, b, c_un, d_un) || !grid_shape_ok(cfg->J, G, 1) || !theta || !img || !aligned16(img))
         return VX_EINVAL;
     const int blocks = grid_1d(grid_image_cells((int)cfg->J, (int)G), 256);
-    hipStream_t st = (hipStream_t)hs;
-#define LAUNCH_GT(M)                                                                                                  \
-    hipLaunchKernelGGL((k_grid_table_irt<M>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, \
-                       a, b, c_un, d_un, (uint16_t*)img)
-    if (cfg->model == 1) { LAUNCH_GT(1); } else if (cfg->model == 2) { LAUNCH_GT(2); } else if (cfg->model == 3) { LAUNCH_GT(3); }
-    else { LAUNCH_GT(4); }
-#undef LAUNCH_GT
-    VX_CHECK_LAUNCH();
-    return VX_OK;
+    return with_irt_model(cfg->model, [&](auto m) -> int {
+        hipLaunchKernelGGL((k_grid_table_irt<decltype(m)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)hs, (int)cfg->D, (int)cfg->J,
+                           (int)G, cfg->Dc, theta, a, b, c_un, d_un, (uint16_t*)img);
+        VX_CHECK_LAUNCH();
+        return VX_OK;
+    });
 }
 
 int vx_grid_table_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* g_un, const float* s_un, void* img,
                       void* hs) {
-    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || cfg->J > GP_MAXJ || (dino != 0 && dino != 1) || !q || !g_un || !s_un || !img ||
-        !aligned16(img))
-        return VX_EINVAL;
+    if (!cdm_items_ok(cfg, dino, q, g_un, s_un) || !img || !aligned16(img)) return VX_EINVAL;
     hipLaunchKernelGGL(k_grid_table_cdm, dim3(grid_1d(grid_image_cells((int)cfg->J, 1 << cfg->K), 256)), dim3(256), 0, (hipStream_t)hs,
                        (int)cfg->K, (int)cfg->J, (int)dino, q, g_un, s_un, (uint16_t*)img);
     VX_CHECK_LAUNCH();
@@ -2234,10 +2318,7 @@ int vx_grid_posterior(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t
 int vx_grid_draw(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, const void* img, const float* logw,
                  uint64_t seed, int64_t row_offset, int32_t draw0, int32_t ndraws, int64_t stride, int32_t* node, void* hs) {
     if (!y || !img || !aligned16(img) || !logw || !node) return VX_EINVAL;
-    if (!grid_shape_ok(J, G, nb)) return VX_EINVAL;
-    if (draw0 < 0 || draw0 > PV_MAXDRAWS || ndraws < 1 || ndraws > PV_MAXDRAWS || draw0 + ndraws > PV_MAXDRAWS ||
-        (int64_t)draw0 + ndraws > stride)
-        return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb) || !draw_range_ok(draw0, ndraws, stride)) return VX_EINVAL;
     const int blocks = grid_unit_blocks(nb);
     const int hi = draw0 + ndraws;
     for (int base = draw0 & ~3; base < hi; base += PV_CAP) {
@@ -2270,10 +2351,7 @@ int vx_grid_draw_cond(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t
                       const float* logw, const float* coord, const float* tilt, uint64_t seed, int64_t row_offset, int32_t draw0,
                       int32_t ndraws, int64_t stride, int32_t* node, void* hs) {
     if (!y || !img || !aligned16(img) || !logw || !coord || !tilt || !node) return VX_EINVAL;
-    if (!grid_shape_ok(J, G, nb) || D < 1 || D > GPC_MAXD) return VX_EINVAL;
-    if (draw0 < 0 || draw0 > PV_MAXDRAWS || ndraws < 1 || ndraws > PV_MAXDRAWS || draw0 + ndraws > PV_MAXDRAWS ||
-        (int64_t)draw0 + ndraws > stride)
-        return VX_EINVAL;
+    if (!grid_shape_ok(J, G, nb) || D < 1 || D > GPC_MAXD || !draw_range_ok(draw0, ndraws, stride)) return VX_EINVAL;
     const int blocks = grid_unit_blocks(nb);
     const int hi = draw0 + ndraws;
     for (int base = draw0 & ~3; base < hi; base += PVC_CAP) {
@@ -2299,26 +2377,17 @@ int vx_grid_counts(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J,
     if (!grid_shape_ok(J, G, nb)) return VX_EINVAL;
     const GcPlan p = gc_plan(nb, J, G);
     hipStream_t st = (hipStream_t)hs;
-    const uint4* im = (const uint4*)img;
-    const dim3 grid((unsigned)(p.n_groups * p.n_chunks));
-    int rc;
-#define LAUNCH_GC(ITV, NTGV)                                                                                          \
-    rc = set_lds(k_grid_counts<ITV, NTGV>, gc_lds_bytes<NTGV>());                                                     \
-    if (rc) return rc;                                                                                                \
-    hipLaunchKernelGGL((k_grid_counts<ITV, NTGV>), grid, dim3(GC_THREADS), gc_lds_bytes<NTGV>(), st, y, rows, nb, (int)J, (int)G, \
-                       im, logw, loglik, p.n_groups, p.rounds_per_chunk, workspace, p.slab_len)
-    if (p.it == 1) { LAUNCH_GC(1, 2); } else if (p.it == 2) { LAUNCH_GC(2, 2); } else { LAUNCH_GC(4, 1); }
-#undef LAUNCH_GC
-    VX_CHECK_LAUNCH();
-    const int64_t JG = (int64_t)J * G;
-    float* const outs[3] = {n1, n0, mass};
-    const int64_t offs[3] = {0, JG, 2 * JG}, lens[3] = {JG, JG, (int64_t)G};
-    for (int k = 0; k < 3; ++k) {
-        hipLaunchKernelGGL(k_reduce_slabs, dim3(grid_1d(lens[k], 64)), dim3(256), 0, st, workspace + offs[k], p.n_chunks,
-                           p.slab_len, lens[k], 1.0f, outs[k]);
-        VX_CHECK_LAUNCH();
-    }
-    return VX_OK;
+    const int rc = with_counts_tiles(p.it, [&](auto it, auto ntg) -> int {
+        constexpr int IT = decltype(it)::value, NTG = decltype(ntg)::value;
+        return launch_lds(k_grid_counts<IT, NTG>, dim3((unsigned)(p.n_groups * p.n_chunks)), dim3(GC_THREADS), gc_lds_bytes<NTG>(), st,
+                          y, rows, nb, (int)J, (int)G, (const uint4*)img, logw, loglik, p.n_groups, p.rounds_per_chunk, workspace,
+                          p.slab_len);
+    });
+    if (rc) return rc;
+    return counts_reduce(J, G, n1, n0, mass, [&](int64_t off, int64_t len, float* out) {
+        hipLaunchKernelGGL(k_reduce_slabs, dim3(grid_1d(len, 64)), dim3(256), 0, st, workspace + off, p.n_chunks, p.slab_len, len, 1.0f,
+                           out);
+    });
 }
 
 // Expected counts under a tilt a person, a table set a segment (k_grid_counts_cond.hip): the plan's table into the head of the
@@ -2361,52 +2430,38 @@ int vx_grid_counts_cond(const uint8_t* y, const int64_t* rows, int64_t nb, int32
         VX_CHECK_LAUNCH();
     }
     float* slabs = workspace + p.tab_floats;
-    const uint4* im = (const uint4*)img;
-    const dim3 grid((unsigned)(p.gc.n_groups * chunks));
-    int rc;
-#define LAUNCH_GCC(ITV, NTGV)                                                                                         \
-    rc = set_lds(k_grid_counts_cond<ITV, NTGV>, gcc_lds_bytes<NTGV>());                                               \
-    if (rc) return rc;                                                                                                \
-    hipLaunchKernelGGL((k_grid_counts_cond<ITV, NTGV>), grid, dim3(GC_THREADS), gcc_lds_bytes<NTGV>(), st, y, rows, (int)J, (int)G, \
-                       (int)D, im, logw, coord, tilt, logjoint, (const int64_t*)dtab, (int)n_seg, p.gc.n_groups, slabs, \
-                       p.gc.slab_len)
-    if (p.gc.it == 1) { LAUNCH_GCC(1, 2); } else if (p.gc.it == 2) { LAUNCH_GCC(2, 2); } else { LAUNCH_GCC(4, 1); }
-#undef LAUNCH_GCC
-    VX_CHECK_LAUNCH();
-    const int64_t JG = (int64_t)J * G;
-    float* const outs[3] = {n1, n0, mass};
-    const int64_t offs[3] = {0, JG, 2 * JG}, lens[3] = {JG, JG, (int64_t)G};
-    for (int k = 0; k < 3; ++k) {
-        hipLaunchKernelGGL(k_reduce_segments, dim3(grid_1d(lens[k], 64), (unsigned)n_seg), dim3(256), 0, st, slabs + offs[k],
-                           (const int64_t*)dtab, (int)n_seg, p.gc.slab_len, lens[k], outs[k]);
-        VX_CHECK_LAUNCH();
-    }
-    return VX_OK;
+    const int rc = with_counts_tiles(p.gc.it, [&](auto it, auto ntg) -> int {
+        constexpr int IT = decltype(it)::value, NTG = decltype(ntg)::value;
+        return launch_lds(k_grid_counts_cond<IT, NTG>, dim3((unsigned)(p.gc.n_groups * chunks)), dim3(GC_THREADS), gcc_lds_bytes<NTG>(),
+                          st, y, rows, (int)J, (int)G, (int)D, (const uint4*)img, logw, coord, tilt, logjoint, (const int64_t*)dtab,
+                          (int)n_seg, p.gc.n_groups, slabs, p.gc.slab_len);
+    });
+    if (rc) return rc;
+    return counts_reduce(J, G, n1, n0, mass, [&](int64_t off, int64_t len, float* out) {
+        hipLaunchKernelGGL(k_reduce_segments, dim3(grid_1d(len, 64), (unsigned)n_seg), dim3(256), 0, st, slabs + off, (const int64_t*)dtab,
+                           (int)n_seg, p.gc.slab_len, len, out);
+    });
 }
 
 // The M-step on the expected-count tables (k_grid_mstep.hip): one wave an item, every Newton step inside the one launch
 int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0, const float* a_free,
                       float* a, float* b, int32_t newton, void* hs) {
-    if (!cfg || (cfg->model != 1 && cfg->model != 2) || cfg->D < 1 || cfg->D > GM_MAXD || !grid_shape_ok(cfg->J, G, 1) ||
-        newton < 1 || newton > GM_MAX_NEWTON || !theta || !n1 || !n0 || !b)
+    if (!irt_items_ok(cfg, 2, GM_MAXD, a, b, nullptr, nullptr) || !grid_shape_ok(cfg->J, G, 1) || newton < 1 || newton > GM_MAX_NEWTON ||
+        !theta || !n1 || !n0)
         return VX_EINVAL;
-    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model == 2 && !a)) return VX_EINVAL;
     const dim3 grid((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES));
-    hipStream_t st = (hipStream_t)hs;
-    if (cfg->model == 1)
-        hipLaunchKernelGGL((k_grid_mstep_irt<1>), grid, dim3(GM_THREADS), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, n1,
-                           n0, a_free, a, b, (int)newton);
-    else
-        hipLaunchKernelGGL((k_grid_mstep_irt<2>), grid, dim3(GM_THREADS), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, n1,
-                           n0, a_free, a, b, (int)newton);
-    VX_CHECK_LAUNCH();
-    return VX_OK;
+    return with_irt_model(cfg->model, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value < 2 ? 1 : 2;                               // (the gate admits 1PL and 2PL only)
+        hipLaunchKernelGGL((k_grid_mstep_irt<M>), grid, dim3(GM_THREADS), 0, (hipStream_t)hs, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc,
+                           theta, n1, n0, a_free, a, b, (int)newton);
+        VX_CHECK_LAUNCH();
+        return VX_OK;
+    });
 }
 
 int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* n1, const float* n0, float* g_un,
                       float* s_un, void* hs) {
-    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || cfg->J > GP_MAXJ || (dino != 0 && dino != 1) || !q || !n1 || !n0 || !g_un || !s_un)
-        return VX_EINVAL;
+    if (!cdm_items_ok(cfg, dino, q, g_un, s_un) || !n1 || !n0) return VX_EINVAL;
     hipLaunchKernelGGL(k_grid_mstep_cdm, dim3((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES)), dim3(GM_THREADS), 0, (hipStream_t)hs,
                        (int)cfg->K, (int)cfg->J, (int)dino, q, n1, n0, g_un, s_un);
     VX_CHECK_LAUNCH();
@@ -2417,36 +2472,31 @@ int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, co
 static bool grid_info_shape_ok(int64_t J, int64_t G, int64_t K, int64_t nb) {
     return grid_shape_ok(J, G, nb) && K >= 1 && K <= GI_MAXK && J * K <= GI_MAXP;
 }
+static bool grid_wimage_shape_ok(int64_t P, int64_t G) { return P >= 1 && P <= GI_MAXP && G >= 1 && G <= GP_MAXG; }
 
 int64_t vx_grid_wimage_bytes(int32_t P, int32_t G) {
-    if (P < 1 || P > GI_MAXP || G < 1 || G > GP_MAXG) return VX_EINVAL;
+    if (!grid_wimage_shape_ok(P, G)) return VX_EINVAL;
     return gi_wimage_frag_bytes(P, G) + 16;
 }
 
 int vx_grid_wtable_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* a, const float* b, void* wimg, void* hs) {
-    if (!cfg || (cfg->model != 1 && cfg->model != 2) || cfg->D < 1 || cfg->D > GM_MAXD || !grid_shape_ok(cfg->J, G, 1) || !theta ||
-        !b || !wimg || !aligned16(wimg))
+    if (!irt_items_ok(cfg, 2, GM_MAXD, a, b, nullptr, nullptr) || !grid_shape_ok(cfg->J, G, 1) || !theta || !wimg || !aligned16(wimg))
         return VX_EINVAL;
-    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model == 2 && !a)) return VX_EINVAL;
     const int P = (int)cfg->J * (cfg->model == 1 ? 1 : (int)cfg->D + 1);
     const int blocks = grid_1d((int64_t)gp_nt(G) * 32 * gi_pt(P) * 32, 256);
     float* trailer = (float*)((uint8_t*)wimg + gi_wimage_frag_bytes(P, G));
-    hipStream_t st = (hipStream_t)hs;
-    if (cfg->model == 1)
-        hipLaunchKernelGGL((k_grid_wtable_irt<1>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, a, b,
-                           (uint16_t*)wimg, trailer);
-    else
-        hipLaunchKernelGGL((k_grid_wtable_irt<2>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc, theta, a, b,
-                           (uint16_t*)wimg, trailer);
-    VX_CHECK_LAUNCH();
-    return VX_OK;
+    return with_irt_model(cfg->model, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value < 2 ? 1 : 2;                               // (the gate admits 1PL and 2PL only)
+        hipLaunchKernelGGL((k_grid_wtable_irt<M>), dim3(blocks), dim3(256), 0, (hipStream_t)hs, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc,
+                           theta, a, b, (uint16_t*)wimg, trailer);
+        VX_CHECK_LAUNCH();
+        return VX_OK;
+    });
 }
 
 int vx_grid_wtable_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* g_un, const float* s_un, void* wimg,
                        void* hs) {
-    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || cfg->J > GP_MAXJ || (dino != 0 && dino != 1) || !q || !g_un || !s_un || !wimg ||
-        !aligned16(wimg))
-        return VX_EINVAL;
+    if (!cdm_items_ok(cfg, dino, q, g_un, s_un) || !wimg || !aligned16(wimg)) return VX_EINVAL;
     const int P = 2 * (int)cfg->J, G = 1 << cfg->K;
     float* trailer = (float*)((uint8_t*)wimg + gi_wimage_frag_bytes(P, G));
     hipLaunchKernelGGL(k_grid_wtable_cdm, dim3(grid_1d((int64_t)gp_nt(G) * 32 * gi_pt(P) * 32, 256)), dim3(256), 0, (hipStream_t)hs,
@@ -2456,13 +2506,13 @@ int vx_grid_wtable_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, c
 }
 
 int64_t vx_grid_info_workspace_floats(int64_t nb, int32_t P, int32_t G) {
-    if (P < 1 || P > GI_MAXP || G < 1 || G > GP_MAXG || nb < 1 || nb > ((int64_t)1 << 48)) return VX_EINVAL;
-    return gi_plan(nb, P, -1).total;
+    if (!grid_wimage_shape_ok(P, G) || nb < 1 || nb > GRID_MAX_PERSONS) return VX_EINVAL;
+    return gi_slab_plan(nb, P, -1).total;
 }
 
 int64_t vx_grid_info_workspace_min_floats(int32_t P, int32_t G) {
-    if (P < 1 || P > GI_MAXP || G < 1 || G > GP_MAXG) return VX_EINVAL;
-    return gi_min_floats(P);
+    if (!grid_wimage_shape_ok(P, G)) return VX_EINVAL;
+    return gi_slab_min_floats(P);
 }
 
 int vx_grid_info(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t G, int32_t K, const void* img, const void* wimg,
@@ -2472,125 +2522,72 @@ int vx_grid_info(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, i
         return VX_EINVAL;
     if (!grid_info_shape_ok(J, G, K, nb)) return VX_EINVAL;
     const int P = (int)J * (int)K;
-    if (ws_floats < gi_min_floats(P) || ws_floats > ((int64_t)1 << 48)) return VX_EINVAL;
-    const GiPlan p = gi_plan(nb, P, ws_floats);
+    if (ws_floats < gi_slab_min_floats(P) || ws_floats > GRID_MAX_PERSONS) return VX_EINVAL;
+    const SlabPlan p = gi_slab_plan(nb, P, ws_floats);
     hipStream_t st = (hipStream_t)hs;
     const float* trailer = (const float*)((const uint8_t*)wimg + gi_wimage_frag_bytes(P, G));
     const size_t lds = gi_lds_bytes(G);
-    int rc = set_lds(k_grid_pscores, lds);
+    const int rc = set_lds(k_grid_pscores, lds);
     if (rc) return rc;
-    uint4* S = (uint4*)workspace;
-    float* part = workspace + p.off_part;
-    float* red = workspace + p.off_red;
-    float* acc = workspace + p.off_acc;
-    const int64_t tiles_len = p.n_pairs * GI_TILE;
-    for (int64_t i0 = 0; i0 < nb; i0 += p.slab_persons) {
-        const int64_t ns = nb - i0 < p.slab_persons ? nb - i0 : p.slab_persons;
-        const int64_t units64 = (ns + 32 * GP_MT - 1) / (32 * GP_MT);
-        const int64_t cap = (int64_t)num_cu() * 2;
+    // k_grid_pscores writes whole units of 64 persons: GP_MT units of 32 each
+    auto frag = [&](int64_t i0, int64_t ns) -> int64_t {
+        const int64_t units64 = (ns + 32 * GP_MT - 1) / (32 * GP_MT), cap = (int64_t)num_cu() * 2;
         hipLaunchKernelGGL(k_grid_pscores, dim3((unsigned)(units64 < cap ? units64 : cap)), dim3(GP_THREADS), lds, st,
                            rows ? y : y + i0 * J, rows ? rows + i0 : rows, ns, (int)J, (int)G, (int)K, P, (const uint4*)img,
-                           (const uint4*)wimg, trailer, logw, loglik + i0, S, gi_nsub(G));
-        VX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_grid_xprod, dim3((unsigned)(p.n_bp * p.n_chunks)), dim3(256), 0, st, (const uint4*)S, p.PT, p.nbb,
-                           units64 * GP_MT, p.units_per_chunk, part, tiles_len);
-        VX_CHECK_LAUNCH();
-        rc = vx_reduce_slabs(part, p.n_chunks, tiles_len, 1.0f, red, hs);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_info_add, dim3(grid_1d(tiles_len, 256)), dim3(256), 0, st, acc, (const float*)red, tiles_len,
-                           i0 == 0 ? 1 : 0);
-        VX_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_info_finish, dim3(grid_1d((int64_t)P * (P + 1), 256)), dim3(256), 0, st, (const float*)acc, P, p.PT, trailer,
-                       info, gradient);
-    VX_CHECK_LAUNCH();
-    return VX_OK;
+                           (const uint4*)wimg, trailer, logw, loglik + i0, (uint4*)workspace, gi_nsub(G));
+        return units64 * GP_MT;
+    };
+    return grid_slab_loop(p, nb, workspace, hs, k_grid_xprod, 256, frag, [&] {
+        hipLaunchKernelGGL(k_info_finish, dim3(grid_1d((int64_t)P * (P + 1), 256)), dim3(256), 0, st,
+                           (const float*)(workspace + p.off_acc), P, p.tiles, trailer, info, gradient);
+    });
 }
 
 // Local dependence (k_grid_pairs.hip): the residual cell as operand fragments, the masked cross products over persons, the sums
-static bool grid_pairs_shape_ok(int64_t J, int64_t nb) { return J >= 1 && J <= GP_MAXJ && nb >= 1 && nb <= ((int64_t)1 << 48); }
-
 int64_t vx_grid_pairs_workspace_floats(int64_t nb, int32_t J) {
-    if (!grid_pairs_shape_ok(J, nb)) return VX_EINVAL;
-    return pp_plan(nb, J, -1).total;
+    if (!grid_point_shape_ok(J, nb)) return VX_EINVAL;
+    return pp_slab_plan(nb, J, -1).total;
 }
 
 int64_t vx_grid_pairs_workspace_min_floats(int32_t J) {
-    if (!grid_pairs_shape_ok(J, 1)) return VX_EINVAL;
-    return pp_min_floats(J);
-}
-
-// the slab loop both entries share: frag(i0, ns, n_units) launches the cell kernel of a slab
-extern "C++" template <typename Frag>
-static int grid_pairs_run(int64_t nb, int J, float* n, float* s, float* ss, float* sp, float* workspace, int64_t ws_floats,
-                          void* hs, Frag frag) {
-    const PpPlan p = pp_plan(nb, J, ws_floats);
-    hipStream_t st = (hipStream_t)hs;
-    float* part = workspace + p.off_part;
-    float* red = workspace + p.off_red;
-    float* acc = workspace + p.off_acc;
-    for (int64_t i0 = 0; i0 < nb; i0 += p.slab_persons) {
-        const int64_t ns = nb - i0 < p.slab_persons ? nb - i0 : p.slab_persons;
-        const int64_t n_units = (ns + 31) / 32;
-        const int64_t cap = (int64_t)num_cu() * 8;
-        frag(i0, ns, n_units, dim3((unsigned)(n_units < cap ? n_units : cap)));
-        VX_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_pair_xprod, dim3((unsigned)(p.n_bp * p.n_chunks)), dim3(64 * PP_XWAVES), 0, st, (const uint4*)workspace, p.JT,
-                           p.nbb, n_units, p.units_per_chunk, part, p.tiles_len);
-        VX_CHECK_LAUNCH();
-        int rc = vx_reduce_slabs(part, p.n_chunks, p.tiles_len, 1.0f, red, hs);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_info_add, dim3(grid_1d(p.tiles_len, 256)), dim3(256), 0, st, acc, (const float*)red, p.tiles_len,
-                           i0 == 0 ? 1 : 0);
-        VX_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_pair_finish, dim3(grid_1d((int64_t)J * J, 256)), dim3(256), 0, st, (const float*)acc, J, p.JT, n, s, ss, sp);
-    VX_CHECK_LAUNCH();
-    return VX_OK;
+    if (!grid_point_shape_ok(J, 1)) return VX_EINVAL;
+    return pp_slab_min_floats(J);
 }
 
 int vx_grid_pairs_irt(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* theta_hat, const float* a,
                       const float* b, const float* c_un, const float* d_un, float* n, float* s, float* ss, float* sp, float* workspace,
                       int64_t ws_floats, void* hs) {
-    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > PP_MAXD || !grid_pairs_shape_ok(cfg->J, nb)) return VX_EINVAL;
-    if (!y || !theta_hat || !b || !n || !s || !ss || !sp || !workspace || !aligned16(workspace)) return VX_EINVAL;
-    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
-        return VX_EINVAL;
-    if (ws_floats < pp_min_floats((int)cfg->J) || ws_floats > ((int64_t)1 << 48)) return VX_EINVAL;
+    if (!irt_items_ok(cfg, 4, PP_MAXD, a, b, c_un, d_un) || !grid_point_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (!y || !theta_hat || !n || !s || !ss || !sp || !workspace || !aligned16(workspace)) return VX_EINVAL;
+    if (ws_floats < pp_slab_min_floats((int)cfg->J) || ws_floats > GRID_MAX_PERSONS) return VX_EINVAL;
     hipStream_t st = (hipStream_t)hs;
-    const int D = (int)cfg->D, J = (int)cfg->J, model = (int)cfg->model;
-    const float Dc = cfg->Dc;
-    auto frag = [=](int64_t i0, int64_t ns, int64_t n_units, dim3 grid) {
-        const uint8_t* ys = rows ? y : y + i0 * J;
-        const int64_t* rs = rows ? rows + i0 : rows;
-        const float* th = theta_hat + i0 * D;
-#define LAUNCH_PF(M)                                                                                                  \
-        hipLaunchKernelGGL((k_pair_frag<M>), grid, dim3(256), 0, st, ys, rs, ns, D, J, Dc, th, a, b, c_un, d_un, (uint4*)workspace, n_units)
-        if (model == 1) { LAUNCH_PF(1); } else if (model == 2) { LAUNCH_PF(2); } else if (model == 3) { LAUNCH_PF(3); }
-        else { LAUNCH_PF(4); }
-#undef LAUNCH_PF
-    };
-    return grid_pairs_run(nb, J, n, s, ss, sp, workspace, ws_floats, hs, frag);
+    const int D = (int)cfg->D, J = (int)cfg->J;
+    return grid_pairs_run(nb, J, n, s, ss, sp, workspace, ws_floats, hs, [&](int64_t i0, int64_t ns, int64_t n_units, dim3 grid) {
+        with_irt_model(cfg->model, [&](auto m) -> int {
+            hipLaunchKernelGGL((k_pair_frag<decltype(m)::value>), grid, dim3(256), 0, st, rows ? y : y + i0 * J, rows ? rows + i0 : rows, ns,
+                               D, J, cfg->Dc, theta_hat + i0 * D, a, b, c_un, d_un, (uint4*)workspace, n_units);
+            return VX_OK;
+        });
+    });
 }
 
 int vx_grid_pairs_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const uint8_t* y, const int64_t* rows, int64_t nb,
                       const int32_t* pattern, const float* g_un, const float* s_un, float* n, float* s, float* ss, float* sp,
                       float* workspace, int64_t ws_floats, void* hs) {
-    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || !grid_pairs_shape_ok(cfg->J, nb) || (dino != 0 && dino != 1)) return VX_EINVAL;
-    if (!q || !y || !pattern || !g_un || !s_un || !n || !s || !ss || !sp || !workspace || !aligned16(workspace)) return VX_EINVAL;
-    if (ws_floats < pp_min_floats((int)cfg->J) || ws_floats > ((int64_t)1 << 48)) return VX_EINVAL;
+    if (!cdm_items_ok(cfg, dino, q, g_un, s_un) || !grid_point_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (!y || !pattern || !n || !s || !ss || !sp || !workspace || !aligned16(workspace)) return VX_EINVAL;
+    if (ws_floats < pp_slab_min_floats((int)cfg->J) || ws_floats > GRID_MAX_PERSONS) return VX_EINVAL;
     hipStream_t st = (hipStream_t)hs;
     const int K = (int)cfg->K, J = (int)cfg->J;
-    auto frag = [=](int64_t i0, int64_t ns, int64_t n_units, dim3 grid) {
+    return grid_pairs_run(nb, J, n, s, ss, sp, workspace, ws_floats, hs, [&](int64_t i0, int64_t ns, int64_t n_units, dim3 grid) {
         hipLaunchKernelGGL(k_pair_frag_cdm, grid, dim3(256), 0, st, rows ? y : y + i0 * J, rows ? rows + i0 : rows, ns, K, J, (int)dino, q,
                            pattern + i0, g_un, s_un, (uint4*)workspace, n_units);
-    };
-    return grid_pairs_run(nb, J, n, s, ss, sp, workspace, ws_floats, hs, frag);
+    });
 }
 
 // Person fit (k_grid_fit.hip): the sums behind lz and infit / outfit per person and per item, one pass over persons x items
 int64_t vx_grid_fit_workspace_floats(int64_t nb, int32_t J) {
-    if (!grid_pairs_shape_ok(J, nb)) return VX_EINVAL;
+    if (!grid_point_shape_ok(J, nb)) return VX_EINVAL;
     return gf_ws_floats(nb, J);
 }
 
@@ -2606,28 +2603,24 @@ static int grid_fit_finish(const GfPlan& p, int J, const float* workspace, float
 int vx_grid_fit_irt(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* theta_hat, const float* a,
                     const float* b, const float* c_un, const float* d_un, float* person, float* item, float* workspace,
                     int64_t ws_floats, void* hs) {
-    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GF_MAXD || !grid_pairs_shape_ok(cfg->J, nb)) return VX_EINVAL;
-    if (!y || !theta_hat || !b || !person || !item || !workspace) return VX_EINVAL;
-    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
-        return VX_EINVAL;
+    if (!irt_items_ok(cfg, 4, GF_MAXD, a, b, c_un, d_un) || !grid_point_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (!y || !theta_hat || !person || !item || !workspace) return VX_EINVAL;
     if (ws_floats < gf_ws_floats(nb, (int)cfg->J)) return VX_EINVAL;
-    hipStream_t st = (hipStream_t)hs;
-    const int D = (int)cfg->D, J = (int)cfg->J, model = (int)cfg->model;
+    const int D = (int)cfg->D, J = (int)cfg->J;
     const GfPlan p = gf_plan(nb);
-#define LAUNCH_GF(M)                                                                                                  \
-    hipLaunchKernelGGL((k_fit_irt<M>), dim3((unsigned)p.n_blocks), dim3(256), 0, st, y, rows, nb, D, J, cfg->Dc, theta_hat, a, b, c_un, \
-                       d_un, person, workspace, p.n_units, p.units_per_block)
-    if (model == 1) { LAUNCH_GF(1); } else if (model == 2) { LAUNCH_GF(2); } else if (model == 3) { LAUNCH_GF(3); }
-    else { LAUNCH_GF(4); }
-#undef LAUNCH_GF
+    with_irt_model(cfg->model, [&](auto m) -> int {
+        hipLaunchKernelGGL((k_fit_irt<decltype(m)::value>), dim3((unsigned)p.n_blocks), dim3(256), 0, (hipStream_t)hs, y, rows, nb, D, J,
+                           cfg->Dc, theta_hat, a, b, c_un, d_un, person, workspace, p.n_units, p.units_per_block);
+        return VX_OK;
+    });
     return grid_fit_finish(p, J, workspace, item, hs);
 }
 
 int vx_grid_fit_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const uint8_t* y, const int64_t* rows, int64_t nb,
                     const int32_t* pattern, const float* g_un, const float* s_un, float* person, float* item, float* workspace,
                     int64_t ws_floats, void* hs) {
-    if (!hodina_cfg_ok(cfg) || cfg->K > GP_MAXD || !grid_pairs_shape_ok(cfg->J, nb) || (dino != 0 && dino != 1)) return VX_EINVAL;
-    if (!q || !y || !pattern || !g_un || !s_un || !person || !item || !workspace) return VX_EINVAL;
+    if (!cdm_items_ok(cfg, dino, q, g_un, s_un) || !grid_point_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (!y || !pattern || !person || !item || !workspace) return VX_EINVAL;
     if (ws_floats < gf_ws_floats(nb, (int)cfg->J)) return VX_EINVAL;
     const int K = (int)cfg->K, J = (int)cfg->J;
     const GfPlan p = gf_plan(nb);
@@ -2642,32 +2635,27 @@ static bool point_number_ok(float v) { return v > 0.f && v < INFINITY; }
 int vx_grid_point_irt(const vx_irt_cfg* cfg, const uint8_t* y, const int64_t* rows, int64_t nb, const float* theta0, const float* a,
                       const float* b, const float* c_un, const float* d_un, int32_t method, int32_t max_iter, float tol, float bound,
                       float step_cap, float* theta_hat, float* info, int32_t* status, int32_t* iters, void* hs) {
-    if (!cfg || cfg->model < 1 || cfg->model > 4 || cfg->D < 1 || cfg->D > GF_MAXD || !grid_pairs_shape_ok(cfg->J, nb)) return VX_EINVAL;
+    if (!irt_items_ok(cfg, 4, GF_MAXD, a, b, c_un, d_un) || !grid_point_shape_ok(cfg->J, nb)) return VX_EINVAL;
     if (method != GPT_ML && method != GPT_MAP && method != GPT_WLE) return VX_EINVAL;
     if ((method == GPT_WLE && cfg->D != 1) || max_iter < 1 || max_iter > GPT_MAX_ITERS) return VX_EINVAL;
     if (!point_number_ok(tol) || !point_number_ok(bound) || !point_number_ok(step_cap)) return VX_EINVAL;
-    if (!y || !theta0 || !b || !theta_hat || !info || !status || !iters) return VX_EINVAL;
-    if ((cfg->model == 1 && cfg->D != 1) || (cfg->model >= 2 && !a) || (cfg->model >= 3 && !c_un) || (cfg->model == 4 && !d_un))
-        return VX_EINVAL;
-    hipStream_t st = (hipStream_t)hs;
-    const int D = (int)cfg->D, J = (int)cfg->J, model = (int)cfg->model, map = method == GPT_MAP ? 1 : 0;
+    if (!y || !theta0 || !theta_hat || !info || !status || !iters) return VX_EINVAL;
+    const int D = (int)cfg->D, J = (int)cfg->J, map = method == GPT_MAP ? 1 : 0;
     const GfPlan p = gf_plan(nb);
-#define LAUNCH_GPT(M, DD, W)                                                                                                        \
-    hipLaunchKernelGGL((k_point_irt<M, DD, W>), dim3((unsigned)p.n_blocks), dim3(256), 0, st, y, rows, nb, D, J, cfg->Dc, theta0, a, b, \
-                       c_un, d_un, map, (int)max_iter, tol, bound, step_cap, theta_hat, info, status, iters, p.n_units,             \
-                       p.units_per_block)
-#define LAUNCH_GPT_MODEL(M)                                                                                           \
-    do {                                                                                                              \
-        if (method == GPT_WLE) { LAUNCH_GPT(M, 1, true); }                                                            \
-        else if (D == 1) { LAUNCH_GPT(M, 1, false); }                                                                 \
-        else { LAUNCH_GPT(M == 1 ? 2 : M, 3, false); }                                                                \
-    } while (0)
-    if (model == 1) { LAUNCH_GPT_MODEL(1); } else if (model == 2) { LAUNCH_GPT_MODEL(2); } else if (model == 3) { LAUNCH_GPT_MODEL(3); }
-    else { LAUNCH_GPT_MODEL(4); }
-#undef LAUNCH_GPT_MODEL
-#undef LAUNCH_GPT
-    VX_CHECK_LAUNCH();
-    return VX_OK;
+    // the instances: (MODEL, 1, WLE) and (MODEL, 1, plain) for D = 1; (MODEL, 3, plain) beyond, where a 1PL cannot be
+    return with_irt_model(cfg->model, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)p.n_blocks), dim3(256), 0, (hipStream_t)hs, y, rows, nb, D, J, cfg->Dc, theta0, a, b,
+                               c_un, d_un, map, (int)max_iter, tol, bound, step_cap, theta_hat, info, status, iters, p.n_units,
+                               p.units_per_block);
+        };
+        if (method == GPT_WLE) launch(k_point_irt<M, 1, true>);
+        else if (D == 1) launch(k_point_irt<M, 1, false>);
+        else launch(k_point_irt<(M == 1 ? 2 : M), 3, false>);
+        VX_CHECK_LAUNCH();
+        return VX_OK;
+    });
 }
 
 // Summed-score tables (k_sumscore.hip): the Lord-Wingersky recursion behind S-X2 and the score table, and the observed tables
