@@ -253,15 +253,17 @@ def tol_cap(loglik):
 _O = {}
 
 
-def oracle_of(case):
-    """Everything score, counts and draws of a case are held to, computed once:
+def oracle_of(case, made=None):
+    """Everything score, counts and draws of a case are held to, computed once (made: a ready-made (cs, kind) in place of
+    case_of(case) -- tests/steep_cases.py overrides leaves and plants persons; the cache goes by the case's name either way):
 
       cs, kind, coord, logw, T1, T0, f (float64 [N][G]), f_r (restated, float32), post (sc.grid_posterior), counts
       (cc.counts + prob + cc.fit_stats), draws (node, gap), answered (the largest number of answered items),
       d_f, gap_thr, e (the restatement's row errors by output) and tol (the row rule by output)."""
     if case[0] in _O:
+        assert made is None or _O[case[0]]["cs"] is made[0], (case[0], "cached under this name from another case")
         return _O[case[0]]
-    cs, kind = case_of(case)
+    cs, kind = case_of(case) if made is None else made
     y = cs["y"]
     coord, logw = grid_of(cs, kind)
     T1, T0 = item_tables(cs, kind, coord)
@@ -297,11 +299,11 @@ def left_out(o):
     return float((o["post"]["gap"] <= o["gap_thr"]).mean()), float((o["draws"][1] <= o["gap_thr"]).mean())
 
 
-def info_oracle(case):
-    """What item_information() of a case is held to, in the keys of se_cases.oracle that test_gpu_se._hold_info reads (S, info and
+def info_oracle(case, made=None):
+    """What item_information() of a case (made: as oracle_of takes it) is held to, in the keys of se_cases.oracle that test_gpu_se._hold_info reads (S, info and
     gradient in float64), with the restatement's row errors `e` and the row rule `tol` for info and gradient.  Not kept: the
     matrix of 4 096 parameters is 134 MB."""
-    o = oracle_of(case)
+    o = oracle_of(case, made)
     cs, kind, y = o["cs"], o["kind"], o["cs"]["y"]
     K, free = se.layout(cs, kind)
     W1, W0, bound = se.tables(cs, kind, cs["params"])

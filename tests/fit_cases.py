@@ -177,14 +177,18 @@ def msq_ratios(infit, outfit, want_infit, want_outfit):
 
 
 # ---- the sums said again in float32 ----------------------------------------------------------------------------------------
-def restated_f32(kind, case):
+def restated_f32(kind, case, made=None):
     """A plain float32 numpy restatement of what the kernels do: the estimates and the item parameters in float32; z, exp, log and
     every term of a cell in float32, Q formed on its own (sigmoid of the negated argument; (1 - d) + (d - c) sigmoid(-z)); what
     belongs to an ITEM alone -- the asymptotes c, d - c and 1 - d of 3PL / 4PL, the two sets of terms of a DINA / DINO item --
     from float64 (a float's rounding of them is the same in every cell of the item and adds up in its sums instead of averaging
     out); a person's sums by numpy's float32 sum over the items, an item's as float32 partials over 32 persons added in
-    float64 and rounded once.  Returns `person`, `item` (float32) and the statistics in float64 out of them."""
-    cs, o = case_of(kind, case), oracle(kind, case)
+    float64 and rounded once.  Returns `person`, `item` (float32) and the statistics in float64 out of them.  made: a ready-made
+    (cs, estimates) in place of the case's own and its oracle's (tests/steep_cases.py)."""
+    if made is None:
+        cs, o = case_of(kind, case), oracle(kind, case)
+    else:
+        cs, o = made[0], {"theta_hat" if kind == "irt" else "pattern": made[1]}
     f4, f8 = np.float32, np.float64
     y = cs["y"]
     m, one = y < 2, y == 1

@@ -137,6 +137,7 @@ __device__ __forceinline__ GfAsym gf_asymptotes(float c_un, float d_un) {
     return a;
 }
 
+#define GF_FLT_MIN 1.17549435e-38f        // the smallest normal float
 // the 3PL / 4PL cell: P = c + (d - c) sigmoid(z) and Q = (1 - d) + (d - c) sigmoid(-z), each from positive terms
 __device__ __forceinline__ GfCell gf_asymptote_cell(float z, const GfAsym& a, bool one) {
     const bool pos = z >= 0.f;
@@ -145,13 +146,30 @@ __device__ __forceinline__ GfCell gf_asymptote_cell(float z, const GfAsym& a, bo
     const float er = e * r;
     const float sg = pos ? r : er, sn = pos ? er : r;
     const float P = fmaf(a.dmc, sg, a.c) + fmaf(a.dmcl, sg, a.cl), Q = fmaf(a.dmc, sn, a.omd) + fmaf(a.dmcl, sn, a.omdl);
-    const float lp = fast_log(P), lq = fast_log(Q);
-    const float lam = lp - lq;
+    // lambda = log P - log Q as one fma over log2 P: what the compiler's contraction made of `lp - lq` before the branch below
+    // was there, written out so that it does not depend on where the subtraction ends up
+    const float l2p = __builtin_amdgcn_logf(P);
+    const float lp = 0.6931471805599453f * l2p, lq = fast_log(Q);
+    const float lam = fmaf(l2p, 0.6931471805599453f, -lq);
     GfCell o;
     o.l = one ? lp : lq;
     o.eps = fmaf(P, lp, Q * lq);
     o.w = P * Q;
     o.nu = o.w * (lam * lam);
+    // Beyond |z| = 87 sigmoid(-|z|) is no normal float: with c = 0 (z < 0) or 1 - d = 0 (z > 0; every 3PL item) P or Q is zero or
+    // subnormal, the hardware log2 and rcp answer -inf and +inf, and P log P, w lambda^2 above are 0 x inf.  The logarithm takes
+    // its limit log(d - c) - |z| there: P log P -> 0, lambda and nu stay finite, and the odds of an answer on the vanished side
+    // come back as +inf below.  A branch of its own, which the compiler has to keep (the empty asm is not speculated): where P
+    // and Q are normal floats the results are what they were.
+    if (!(P >= GF_FLT_MIN) || !(Q >= GF_FLT_MIN)) {
+        float lim = fast_log(a.dmc) - fabsf(z);
+        asm volatile("" : "+v"(lim));
+        const float lp2 = P >= GF_FLT_MIN ? lp : lim, lq2 = Q >= GF_FLT_MIN ? lq : lim;
+        const float lam2 = lp2 - lq2;
+        o.l = one ? lp2 : lq2;
+        o.eps = fmaf(P, lp2, Q * lq2);
+        o.nu = o.w * (lam2 * lam2);
+    }
     const float num = one ? Q : P, den = one ? P : Q;
     o.r2 = num * num;
     o.z2 = num * fast_rcp(den);

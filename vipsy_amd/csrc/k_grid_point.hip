@@ -62,7 +62,16 @@ __device__ __forceinline__ void gpt_cell(float z, const GfAsym& as, bool one, fl
     } else {
         const float P = fmaf(as.dmc, sg, as.c) + fmaf(as.dmcl, sg, as.cl), Q = fmaf(as.dmc, sn, as.omd) + fmaf(as.dmcl, sn, as.omdl);
         const float pz = as.dmc * (er * r);
-        const float u1 = pz * fast_rcp(P), u0 = pz * fast_rcp(Q);
+        float u1 = pz * fast_rcp(P), u0 = pz * fast_rcp(Q);
+        // P or Q zero or subnormal -- beyond |z| = 87 with c = 0 or 1 - d = 0, see gf_asymptote_cell: P_z / P -> sigmoid(-z) and
+        // P_z / Q -> sigmoid(z), not 0 x inf.  A branch of its own that the compiler keeps (as in gf_asymptote_cell): where both
+        // are normal floats the line above is what it was.
+        if (!(P >= GF_FLT_MIN) || !(Q >= GF_FLT_MIN)) {
+            float l1 = sn, l0 = sg;
+            asm volatile("" : "+v"(l1), "+v"(l0));
+            u1 = P >= GF_FLT_MIN ? u1 : l1;
+            u0 = Q >= GF_FLT_MIN ? u0 : l0;
+        }
         t = one ? u1 : -u0;
         it = u1 * u0;
     }
