@@ -543,6 +543,32 @@ int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int3
 int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const float* n1 /*[J][2^K]*/,
                       const float* n0 /*[J][2^K]*/, float* g_un /*[J] in/out*/, float* s_un /*[J] in/out*/, void* hip_stream);
 
+/* ---- The penalised M-step (Bayes-modal EM; k_grid_mstep_map.hip): vx_grid_mstep_irt for models 1 .. 4 with a normal prior on
+ * every unknown.  Item j maximises, over p = (b, a_0 .. a_{D-1}, c_un, d_un) as far as the model has them,
+ *         Q_j = sum_g n1[j][g] log P_j(g) + n0[j][g] log Q_j(g) - 1/2 sum_k prec_k (p_k - mean_k)^2
+ * by `newton` steps of Fisher scoring inside the one launch, one wave an item.  1PL / 2PL: the cell of vx_grid_mstep_irt.
+ * 3PL / 4PL: P = c + (d - c) s(z), Q = (1 - d) + (d - c) s(-z) in the arithmetic of the tables (c, d and 1 - d from the logits,
+ * capped as vx_grid_table_irt caps them; P and Q clamped to [eps32, 1 - eps32], a clamped node adds its log term and nothing to
+ * gradient or curvature).  d <= c is not excluded by a constraint: the prior keeps the asymptotes apart.
+ * Step control is vx_grid_mstep_irt's, applied to the penalised Q_j (1e-6 |Q_j|, at most 8 halvings, cap 4).  a_free[d][j] == 0:
+ * that loading is not an unknown and is not written.  An item nobody answered keeps its bits; on a pivot that is not positive
+ * or not finite an item stops where it is.  a, b, c_un, d_un are updated in place; nothing else is written but lprior.
+ *   prior   float [2][6][J] on the device: prior[k][j] the mean and prior[6 + k][j] the precision (1 / sd^2) of unknown k of item
+ *           j; k = 0: b, 1 .. 3: a_0 .. a_2, 4: c_un, 5: d_un -- six rows each in every model; rows of unknowns the model, D or
+ *           a_free does not have are not read.  Precision 0 = no prior on that unknown (its mean must still be finite).  The
+ *           precisions must be >= 0 and finite; the call cannot look into device memory, so this is the caller's duty.
+ *   lprior  NULL or float [J]: -1/2 sum_k prec_k (p_k - mean_k)^2 over the item's free unknowns at the parameters the call
+ *           STARTED from (constants dropped); written for every item, answered or not.
+ * Every sum runs in a fixed order, no atomics: the same call gives the same bits, and an item's bits do not depend on the other
+ * items of the launch.
+ * Limits: model 1 .. 4 (c_un from 3, d_un for 4, a from 2), 1 <= D <= 3, 1 <= J <= 1024, 1 <= G <= 1024, 1 <= newton <= 64,
+ * prior not NULL; VX_EINVAL beyond. */
+int vx_grid_mstep_irt_map(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int32_t G, const float* n1 /*[J][G]*/,
+                          const float* n0 /*[J][G]*/, const float* a_free /*[D][J] or NULL = all free*/,
+                          float* a /*[D][J] in/out, NULL for 1PL*/, float* b /*[J] in/out*/, float* c_un /*[J] in/out, model >= 3*/,
+                          float* d_un /*[J] in/out, model 4*/, const float* prior /*[2][6][J]*/, int32_t newton,
+                          float* lprior /*[J] or NULL*/, void* hip_stream);
+
 /* ---- The cross-product (BHHH) information of the item parameters from the grid posteriors: with Fisher's identity the marginal
  * score of person i for parameter k of item j is
  *     s_i[(j,k)] = sum_g p_i(g) ( [y_ij == 1] W1[g][(j,k)] - [y_ij == 0] W0[g][(j,k)] ),   W1 = (1 - P_j(g)) u_jgk,  W0 = P_j(g) u_jgk,

@@ -137,6 +137,7 @@ SIGNATURES = {
     "vx_grid_counts_cond": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 5 + [_P, _I32] + [_P] * 3 + [_P, _P]),
     "vx_grid_mstep_irt": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 3 + [_P, _P, _I32, _P]),
     "vx_grid_mstep_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32] + [_P] * 3 + [_P, _P, _P]),
+    "vx_grid_mstep_irt_map": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 3 + [_P] * 4 + [_P, _I32, _P, _P]),
     "vx_grid_wimage_bytes": (_I64, [_I32, _I32]),
     "vx_grid_wtable_irt": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 2 + [_P, _P]),
     "vx_grid_wtable_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32] + [_P] * 3 + [_P, _P]),

@@ -34,6 +34,7 @@
 #include "k_grid_counts.hip"
 #include "k_grid_draw.hip"
 #include "k_grid_mstep.hip"
+#include "k_grid_mstep_map.hip"
 #include "k_grid_info.hip"
 #include "k_grid_pairs.hip"
 #include "k_grid_fit.hip"
@@ -2454,6 +2455,22 @@ int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, cons
         constexpr int M = decltype(m)::value < 2 ? 1 : 2;                               // (the gate admits 1PL and 2PL only)
         hipLaunchKernelGGL((k_grid_mstep_irt<M>), grid, dim3(GM_THREADS), 0, (hipStream_t)hs, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc,
                            theta, n1, n0, a_free, a, b, (int)newton);
+        VX_CHECK_LAUNCH();
+        return VX_OK;
+    });
+}
+
+// The penalised M-step (k_grid_mstep_map.hip): vx_grid_mstep_irt's launch for all four models, with a normal prior an unknown.
+// The precisions live in device memory: that they are >= 0 and finite is checked where `prior` is made (vipsy_amd/grid.py).
+int vx_grid_mstep_irt_map(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0, const float* a_free,
+                          float* a, float* b, float* c_un, float* d_un, const float* prior, int32_t newton, float* lprior, void* hs) {
+    if (!irt_items_ok(cfg, 4, GM_MAXD, a, b, c_un, d_un) || !grid_shape_ok(cfg->J, G, 1) || newton < 1 || newton > GM_MAX_NEWTON ||
+        !theta || !n1 || !n0 || !prior)
+        return VX_EINVAL;
+    const dim3 grid((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES));
+    return with_irt_model(cfg->model, [&](auto m) -> int {
+        hipLaunchKernelGGL((k_grid_mstep_irt_map<decltype(m)::value>), grid, dim3(GM_THREADS), 0, (hipStream_t)hs, (int)cfg->D,
+                           (int)cfg->J, (int)G, cfg->Dc, theta, n1, n0, a_free, a, b, c_un, d_un, prior, lprior, (int)newton);
         VX_CHECK_LAUNCH();
         return VX_OK;
     });

@@ -16,7 +16,7 @@ import torch
 
 from . import _hip
 from .grid import (EM_MAX_NEWTON, PV_MAX_DRAWS, PV_STREAM, SCORE_MAX_DIMS, SCORE_MAX_NODES, GridCall, GridMixin,  # noqa: F401
-                   design_cholesky, grid_image_prob, item_fit_stats, population_logw, score_grid, tri_to_full)     # (re-exported: the grid family lives in grid.py)
+                   design_cholesky, em_prior, grid_image_prob, item_fit_stats, population_logw, score_grid, tri_to_full)     # (re-exported: the grid family lives in grid.py)
 from .grid import (POINT_AT_BOUND, POINT_CONVERGED, POINT_EMPTY, POINT_MAX_ITER, POINT_MAX_ITERS, POINT_METHODS,  # noqa: F401
                    POINT_SINGULAR, POINT_STATUS, POINT_STEP_CAP, point_estimates_host)
 
@@ -268,6 +268,12 @@ class HipBackend(object):
         rc = self.L.vx_grid_mstep_irt(ctypes.byref(cfg), _hip.ptr(theta), G, _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(a_free),
                                       _hip.ptr(a), _hip.ptr(b), int(newton), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_mstep_irt")
+
+    def grid_mstep_irt_map(self, cfg, theta, G, n1, n0, a_free, a, b, c_un, d_un, prior, newton, lprior=None):
+        rc = self.L.vx_grid_mstep_irt_map(ctypes.byref(cfg), _hip.ptr(theta), G, _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(a_free),
+                                          _hip.ptr(a), _hip.ptr(b), _hip.ptr(c_un), _hip.ptr(d_un), _hip.ptr(prior), newton,
+                                          _hip.ptr(lprior), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_mstep_irt_map")
 
     def grid_mstep_cdm(self, cfg, dino, q, n1, n0, g, s_):
         rc = self.L.vx_grid_mstep_cdm(ctypes.byref(cfg), int(dino), _hip.ptr(q), _hip.ptr(n1), _hip.ptr(n0), _hip.ptr(g),
@@ -1796,10 +1802,14 @@ class IrtEngine(GridMixin, _EngineBase):
         logw = torch.from_numpy(population_logw(call.theta.cpu().numpy(), sigma)).to(self.dev)
         return call._replace(logw=logw), tilt, group_mean, sigma
 
+    # what fit_em() without prior= and dif(refit=True) say to irt_3pl / irt_4pl, in the same words
+    _UNPENALISED_ONLY = ("with a guessing or slipping asymptote the M-step is not concave and wants priors on the items; only irt_1pl "
+                         "and irt_2pl have it without them -- fit_em(prior=...) refits irt_3pl / irt_4pl under item priors "
+                         "(dif(refit=True) takes none)")
+
     def _group_refit_check(self):
         if self.model not in ("irt_1pl", "irt_2pl"):
-            raise NotImplementedError("dif(refit=True) for %s: with a guessing or slipping asymptote the M-step is not concave and "
-                                      "wants priors on the items; only irt_1pl and irt_2pl have it" % self.model)
+            raise NotImplementedError("dif(refit=True) for %s: %s" % (self.model, self._UNPENALISED_ONLY))
 
     def _group_refit(self, call, n1, n0, newton):
         """Every group's items from the pooled values by `newton` steps of vx_grid_mstep_irt on that group's tables."""
@@ -1816,7 +1826,7 @@ class IrtEngine(GridMixin, _EngineBase):
         return {"b_group": b_np, "a_group": a_g.cpu().numpy().astype(np.float64),
                 "delta_b": b_np - b0.cpu().numpy().astype(np.float64)[None, :]}
 
-    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, nodes=61, span=6.0):
+    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, nodes=61, span=6.0, prior=None):
         """Marginal maximum likelihood of a and b by Bock-Aitkin EM over the grid of score(): each iteration scores the training
         responses under the item parameters as they stand (the E-step: vx_grid_posterior, vx_grid_counts) and refits every
         item to its expected counts by `newton` Newton steps (the M-step: vx_grid_mstep_irt), until the marginal log-likelihood
@@ -1828,11 +1838,18 @@ class IrtEngine(GridMixin, _EngineBase):
         the triangular default of x_feature > 1); the phantom items and dimensions of a padded engine are neither read nor
         written.  1PL and 2PL with x_feature <= 3; an item nobody answered keeps its values; an item whose observed answers
         are all equal has no finite maximiser and ends where the clamp of the response function, +-logit(1 - eps32) on z,
-        holds at every node -- there the step kernels' `inside` test fails, so a later fit() sees a zero gradient for it."""
+        holds at every node -- there the step kernels' `inside` test fails, so a later fit() sees a zero gradient for it.
+        prior (Bayes-modal EM; all four models): a dict over "a", "b", "c", "d" of (mean, sd) -- normal priors on the
+        UNCONSTRAINED scale of the leaves (c_un = logit c, d_un = logit d), each a scalar or an array shaped like the leaf;
+        sd = inf or an absent key: no prior (grid.em_prior checks the argument).  The M-step is then the penalised one of
+        vx_grid_mstep_irt_map, for 1PL and 2PL too, and c / d are refitted with a and b.  irt_3pl needs a finite sd on "c" and
+        irt_4pl on "c" and "d": the likelihood alone does not pin an asymptote.  The return gains "logpost": logpost[k] =
+        loglik[k] + the log prior (constants dropped) at the parameters iteration k started from, and convergence is judged
+        on it -- the quantity this EM raises; loglik[0] is still marginal_loglik() before the call.  Without `prior` nothing
+        changes: 1PL / 2PL take vx_grid_mstep_irt, and irt_3pl / irt_4pl refuse."""
         self._em_refusals(max_iter, newton)
-        if self.model not in ("irt_1pl", "irt_2pl"):
-            raise NotImplementedError("fit_em for %s: with a guessing or slipping asymptote the M-step is not concave and wants "
-                                      "priors on the items; only irt_1pl and irt_2pl have it" % self.model)
+        if prior is None and self.model not in ("irt_1pl", "irt_2pl"):
+            raise NotImplementedError("fit_em for %s: %s" % (self.model, self._UNPENALISED_ONLY))
         if self.D_model > SCORE_MAX_DIMS:
             raise NotImplementedError("fit_em needs x_feature <= %d (this model has %d): a tensor-product grid of n nodes a "
                                       "dimension has n**D points" % (SCORE_MAX_DIMS, self.D_model))
@@ -1841,9 +1858,19 @@ class IrtEngine(GridMixin, _EngineBase):
         a = self.unconstrained("a").contiguous().clone() if two else None
         free = self.unconstrained("a", self.free).contiguous().clone() if two else None
         b = self.unconstrained("b").reshape(-1).contiguous().clone()
-        call = self._grid_call(None, None, nodes, span, params=(a, b, None, None))
-        return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_irt(call.cfg, call.theta, call.G, n1, n0, free, a, b, newton),
-                             {"a": a, "b": b} if two else {"b": b}, max_iter, tol, progress)
+        if prior is None:
+            call = self._grid_call(None, None, nodes, span, params=(a, b, None, None))
+            return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_irt(call.cfg, call.theta, call.G, n1, n0, free, a, b, newton),
+                                 {"a": a, "b": b} if two else {"b": b}, max_iter, tol, progress)
+        pr = torch.from_numpy(em_prior(prior, self.model, self.D_model, self.J_items)).to(self.dev)
+        c = self.unconstrained("c").reshape(-1).contiguous().clone() if self.model in ("irt_3pl", "irt_4pl") else None
+        d = self.unconstrained("d").reshape(-1).contiguous().clone() if self.model == "irt_4pl" else None
+        lprior = torch.zeros(self.J_items, dtype=torch.float32, device=self.dev)
+        call = self._grid_call(None, None, nodes, span, params=(a, b, c, d))
+        leaves = {k: v for k, v in (("a", a), ("b", b), ("c", c), ("d", d)) if v is not None}
+        return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_irt_map(call.cfg, call.theta, call.G, n1, n0, free, a, b, c, d,
+                                                                             pr, newton, lprior),
+                             leaves, max_iter, tol, progress, lprior=lprior)
 
     def _info_call(self, y_u8, rows, nodes=61, span=6.0):
         """What GridMixin.item_information needs of this class: the GridCall, K (columns an item: b, then a_0 .. a_{D-1}; 1PL: b),
@@ -2383,14 +2410,17 @@ class CcdmEngine(GridMixin, _EngineBase):
         raise NotImplementedError("dif(refit=True) on %s: the group refit is the Newton M-step of irt_1pl / irt_2pl "
                                   "(vx_grid_mstep_irt); only IrtEngine has it" % type(self).__name__)
 
-    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False):
+    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, prior=None):
         """Marginal maximum likelihood of g and s by EM over the 2^K patterns (IrtEngine.fit_em): the E-step of
         expected_counts(), then the closed-form M-step of vx_grid_mstep_cdm.  The enumerated ELBO of this class with its empty
         guide IS the marginal likelihood: this is a second optimiser of what fit() descends.  The pattern distribution stays the
         uniform prior; Adam's moments and the step count stay as they are.  `newton` is accepted for a common signature and
         unused.  An estimate of exactly 0 or 1 sits at the clamp, +-logit(1 - eps32), where the step kernels give it a zero
-        gradient afterwards."""
+        gradient afterwards.  `prior` (IrtEngine.fit_em's item priors) is refused: the closed form has none."""
         self._em_refusals(max_iter, newton)
+        if prior is not None:
+            raise ValueError("fit_em(prior=) on %s: the priors are those of the IRT item parameters (IrtEngine); the closed-form "
+                             "M-step of DINA / DINO takes none" % type(self).__name__)
         dino = self.cdm == "dino"
         g, s_ = self.view("g").clone(), self.view("s").clone()
         call = self._grid_call(None, None, params=(g, s_))

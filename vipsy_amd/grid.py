@@ -57,6 +57,62 @@ def score_grid(D, nodes=61, span=6.0):
     return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
 
 
+EM_PRIOR_ROWS = 6                # GMM_ROWS (vipsy_amd/csrc/k_grid_mstep_map.hip): b, a_0 .. a_2, c_un, d_un
+EM_PRIOR_KEYS = {"irt_1pl": ("b",), "irt_2pl": ("a", "b"), "irt_3pl": ("a", "b", "c"), "irt_4pl": ("a", "b", "c", "d")}
+
+
+def em_prior(prior, model, D, J):
+    """fit_em's `prior` as vx_grid_mstep_irt_map takes it: float32 numpy [2][6][J], [0][k] the means and [1][k] the precisions
+    1 / sd^2 of unknown k (0: b, 1 + d: a_d, 4: c_un, 5: d_un), zero where there is no prior.  The one place the argument is
+    checked -- the C entry cannot look into device memory, so negative or non-finite precisions are refused HERE.
+    prior: a dict over "a", "b", "c", "d", each (mean, sd) on the unconstrained scale of the leaves (c_un = logit c, d_un =
+    logit d); mean and sd are scalars or arrays shaped like the leaf ([D][J] for a, [1][J] for the others); sd > 0, inf or an
+    absent key meaning no prior.  ValueError: not a dict, an unknown key, a key the model does not have, a value that is no
+    (mean, sd) pair, a wrong shape, a non-finite mean, an sd that is not > 0 -- and a 3PL without a finite sd on every item's c,
+    or a 4PL without one on c and d: the likelihood alone does not identify an asymptote (the M-step is not concave in it and
+    walks its logit to the clamp), so the prior is what the fit rests on."""
+    keys = EM_PRIOR_KEYS[model]
+    if not isinstance(prior, dict):
+        raise ValueError('prior must be a dict over "a", "b", "c", "d" of (mean, sd) pairs')
+    out = np.zeros((2, EM_PRIOR_ROWS, J), np.float64)
+    finite = {}
+    for key, value in prior.items():
+        if key not in ("a", "b", "c", "d"):
+            raise ValueError('prior has the unknown key %r: the keys are "a", "b", "c", "d"' % (key,))
+        if key not in keys:
+            raise ValueError("prior[%r]: %s has no such parameter" % (key, model))
+        if not isinstance(value, (tuple, list)) or len(value) != 2:
+            raise ValueError("prior[%r] must be a pair (mean, sd)" % key)
+        shape = (D, J) if key == "a" else (1, J)
+        pair = []
+        for what, v in zip(("mean", "sd"), value):
+            try:
+                v = np.asarray(v, np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("prior[%r]: %s must be a number or an array shaped like the leaf" % (key, what))
+            if v.shape not in ((), shape):
+                raise ValueError("prior[%r]: %s must be a scalar or shaped like the leaf, %s (got %s)" % (key, what, shape, v.shape))
+            pair.append(np.broadcast_to(v, shape))
+        mean, sd = pair
+        if not np.isfinite(mean).all():
+            raise ValueError("prior[%r]: the mean must be finite" % key)
+        if not (sd > 0).all():                                         # (NaN fails it too)
+            raise ValueError("prior[%r]: sd must be > 0 (inf: no prior)" % key)
+        with np.errstate(over="ignore", divide="ignore"):
+            prec = np.where(np.isinf(sd), 0.0, 1.0 / (sd * sd)).astype(np.float32)      # (as the kernel reads it)
+        if not np.isfinite(prec).all():
+            raise ValueError("prior[%r]: 1 / sd^2 is not a finite float32" % key)
+        lo = 1 if key == "a" else {"b": 0, "c": 4, "d": 5}[key]
+        out[0, lo:lo + shape[0]] = np.where(prec > 0, mean, 0.0)
+        out[1, lo:lo + shape[0]] = prec
+        finite[key] = bool((prec > 0).all())
+    for key, name in (("c", "guessing"), ("d", "slipping")):
+        if key in keys and not finite.get(key, False):
+            raise ValueError("%s needs a prior with a finite sd on %r for every item: the likelihood alone does not pin the %s "
+                             "asymptote -- without a prior its logit walks to the clamp" % (model, key, name))
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
 def population_logw(theta, sigma):
     """The shared log-weights of the nodes under a population N(mu_i, sigma): -1/2 theta_g^T sigma^-1 theta_g, shifted so that the
     largest is 0 (the per-person normaliser is the kernel's lognorm), computed in float64, returned as float32 [G]."""
@@ -833,12 +889,15 @@ class GridMixin(object):
             out.update(self._group_refit(call, c["n1"], c["n0"], newton))
         return out
 
-    def _em_loop(self, call, mstep, leaves, max_iter, tol, progress):
+    def _em_loop(self, call, mstep, leaves, max_iter, tol, progress, lprior=None):
         """The EM iterations of IrtEngine.fit_em and CcdmEngine.fit_em over a call on the caller's compact parameter copies:
         tables, vx_grid_posterior, the sum of its loglik (as marginal_loglik sums it), vx_grid_counts, the M-step (mstep(n1, n0),
         on those copies) and the write-back of the copies into the leaves ({name: copy}).  Every buffer is made once, before the
         loop.  The float of an iteration is fetched after its M-step is queued: one host sync an iteration, behind which the
-        device is never idle for long."""
+        device is never idle for long.
+        lprior (fit_em(prior=)): the [J] tensor into which mstep writes every item's log prior at the parameters it started
+        from.  Its sum (on the device) added to the iteration's loglik is `logpost`, the quantity a penalised EM raises:
+        the history that is returned beside loglik and on which convergence is then judged."""
         be = self.be
         y, J, theta, logw, G, D, n = call.y, call.J, call.theta, call.logw, call.G, call.D, call.n
         f32 = dict(dtype=torch.float32, device=self.dev)
@@ -847,7 +906,7 @@ class GridMixin(object):
         node = torch.empty(n, dtype=torch.int32, device=self.dev)
         n1, n0, mass = torch.empty(J, G, **f32), torch.empty(J, G, **f32), torch.empty(G, **f32)
         ws = torch.empty(be.grid_counts_workspace(n, J, G), **f32)
-        total, sum_ws = torch.empty(1, **f32), torch.empty(1024, **f32)      # vx_sum_workspace_floats(); not the step's
+        total, sum_ws = torch.zeros(2, **f32), torch.empty(1024, **f32)      # vx_sum_workspace_floats(); not the step's
         bar = None
         if progress:
             try:
@@ -855,17 +914,21 @@ class GridMixin(object):
                 bar = trange(max_iter)
             except Exception:  # pragma: no cover
                 bar = None
-        hist, converged = [], False
+        liks, hist, converged = [], [], False
         for _ in range(max_iter):
             call.fill_tables(img)
             be.grid_posterior(y, None, n, J, G, D, img, logw, theta, loglik, mean, sd, node)
-            be.sum_into(loglik, n, 1.0, total, sum_ws)
+            be.sum_into(loglik, n, 1.0, total[:1], sum_ws)
             be.grid_counts(y, None, n, J, G, img, logw, loglik, n1, n0, mass, ws)
             mstep(n1, n0)
+            if lprior is not None:
+                be.sum_into(lprior, J, 1.0, total[1:], sum_ws)
             for name, t in leaves.items():
                 leaf = self.unconstrained(name)
                 leaf.copy_(t.reshape(leaf.shape))
-            hist.append(float(total.item()))
+            lik, lp = total.tolist()
+            liks.append(lik)
+            hist.append(lik + lp if lprior is not None else lik)
             if bar is not None:
                 bar.update(1)
                 bar.set_postfix(loglik="{0:1.4f}".format(hist[-1]))
@@ -874,7 +937,10 @@ class GridMixin(object):
                 break
         if bar is not None:
             bar.close()
-        return {"loglik": hist, "iterations": len(hist), "converged": converged}
+        out = {"loglik": liks, "iterations": len(hist), "converged": converged}
+        if lprior is not None:
+            out["logpost"] = hist
+        return out
 
     def item_information(self, y_u8=None, rows=None, **kw):
         """The cross-product (BHHH, empirical) information of the item parameters over the scored rows, AT THE PARAMETERS

@@ -302,7 +302,7 @@ class BasePsy(object):
                                       "cross-rank sum is not built" % self.world)
         return self.engine.marginal_loglik(self._score_data(data), **kw)
 
-    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, **grid_kw):
+    def fit_em(self, max_iter=100, tol=1e-6, newton=4, progress=False, prior=None, **grid_kw):
         """Refit the item parameters by marginal maximum likelihood: Bock-Aitkin EM on the training data (this object's
         `data`) over the grid of score() (grid_kw: nodes, span), until the marginal log-likelihood rises by no more than
         tol times its size between two iterations or max_iter is reached.  VIRT / VaeIRT with irt_1pl / irt_2pl and
@@ -310,10 +310,17 @@ class BasePsy(object):
         the other classes refuse.  Returns {"loglik": [floats], "iterations": int, "converged": bool}, loglik[k] being the
         marginal log-likelihood under the parameters at the START of iteration k: loglik[0] is marginal_loglik() before the
         call, marginal_loglik() after it gives the value of the final parameters.  The guide, the optimiser's state and the
-        step count are left alone: a later fit() continues from the refitted items.  One rank only."""
+        step count are left alone: a later fit() continues from the refitted items.  One rank only.
+        prior: normal priors on the item parameters (Bayes-modal EM), which opens irt_3pl and irt_4pl -- a dict over "a", "b",
+        "c", "d" of (mean, sd) on the unconstrained scale of the leaves (c, d as logits), scalars or arrays shaped like the
+        leaf, e.g. prior={"c": (-1.4, 1.0), "d": (2.2, 1.0)}; irt_3pl needs a finite sd on "c", irt_4pl on "c" and "d".  The
+        return then has "logpost" (loglik + the log prior, what the iterations raise and convergence is judged on) as well;
+        VCCDM refuses it (IrtEngine.fit_em)."""
         if self.world > 1:
             raise NotImplementedError("fit_em with a group of %d ranks: the expected counts are the local shard's sums; the "
                                       "cross-rank sum is not built" % self.world)
+        if prior is not None:
+            grid_kw["prior"] = prior
         return self.engine.fit_em(max_iter=max_iter, tol=tol, newton=newton, progress=progress, **grid_kw)
 
     def item_information(self, data=None, **grid_kw):
