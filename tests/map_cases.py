@@ -1,5 +1,6 @@
 """The cases, the float64 oracle and the float32 restatement of the penalised M-step (vx_grid_mstep_irt_map,
-vipsy_amd/csrc/k_grid_mstep_map.hip) and of fit_em(prior=): tests/test_map_host.py on the CPU, tests/test_gpu_map.py on the GPU.
+vipsy_amd/csrc/k_grid_mstep_map.hip) and of fit_em(prior=): tests/test_map_host.py on the CPU, tests/test_gpu_map.py and
+tests/test_gpu_map_paths.py on the GPU.
 
 Unknowns of an item, everywhere in this file, as the kernel orders them: p = (b, a_0, a_1, a_2, c_un, d_un) -- six rows whatever
 the model; `free` [6][J] says which of them the item has (b; a_d for d < D where a_free allows; c_un from 3PL; d_un for 4PL).
@@ -10,9 +11,14 @@ terms the one-step rule is scaled by.  map_mstep is the kernel's step control ar
 penalised Q_j).
 
 Cases (CASES): the smallest shapes at which the kernel can go wrong -- J no multiple of 4, G no multiple of 64, sixteen nodes a
-lane, one node, masked loadings, every model -- each with 10 % missing, generating values a in [0.7, 1.8], b in [-1.5, 1.5], c in
+lane, one node, masked loadings, every model (1PL at D = 1; 2PL at D = 1 and 3; 3PL at D = 1 and 2; 4PL at D = 1, 2 and 3: the
+full 6 x 6 system), a Dc other than 1.702 (1.0, on the 4PL D = 3 case) -- each with 10 % missing, generating values a in [0.7, 1.8], b in [-1.5, 1.5], c in
 [0.1, 0.3], d in [0.85, 0.98], the priors c_un ~ N(-1.4, 1), d_un ~ N(2.2, 1), and two more items: one nobody answered (UNANSWERED)
-and one everybody answered correctly (the last), which has a prior on b so that its maximum is finite.
+and one everybody answered correctly (the last), which has a prior on b so that its maximum is finite.  (The 1PL case's responses
+are drawn with the generating loadings all the same: a misfitting model is as good a table as any.)
+
+Far starts (FAR, far_launch): the same tables from p0 + free U(-amp, amp), amp 1.5, 3 and 5 -- where the step is capped, halved,
+both, or halved twice; rule 3 below holds the one step from there, rule 1 the end.
 
 The rules and their constants.  A float32 sum of at most 16 terms a lane and six tree levels carries a relative error of at most
 22 u = 11 eps32 of the sum of its absolute terms (u = eps32 / 2), and the terms themselves (exp, rcp, log of the hardware, a few
@@ -28,7 +34,15 @@ ulp each) about 4 eps32 more: 15 eps32.
   C_STEP = 32 rule 2: the output of one accepted full step equals the float64 step to C_STEP eps32 |H^-1| S, S_l = the sum of the
               absolute terms of gradient entry l: 15 eps32 S for the gradient's own rounding, and as much again for the rounding
               of the matrix (its entries are sums of the same length; the step is at most of size one here), rounded up to 2^5.
-tests/test_map_host.py asserts that the method alone, said in float32 numpy, meets both at HALF the constant."""
+  (no new constant) rule 3: one step from a FAR start, whatever its path -- capped, halved, both -- equals the float64 step
+              t delta unknown by unknown to
+                  C_STEP eps32 ( t (|H^-1| S)_k + [capped] |t delta_k| (|H^-1| S)_m / |delta_m| + |p_k| ),     m = argmax |delta|:
+              rule 2's premise for the direction, scaled by the step length t that was accepted (1, 4 / max |delta|, and a power
+              of 1/2); where the cap applies, t itself is a quotient by a rounded |delta_m|, whose relative error rule 2 bounds by
+              (|H^-1| S)_m / |delta_m|; and the stored parameter is rounded once more at its own size, which no longer is the
+              step's.  The rule follows the float64 PATH, so it is only fair where every accept / reject decision of that path
+              is clear of the threshold by 100 tolerances (tests/test_map_host.py asserts that of every item-start it is held on).
+tests/test_map_host.py asserts that the method alone, said in float32 numpy, meets all three at HALF the constant."""
 import numpy as np
 import torch
 
@@ -57,8 +71,13 @@ CASES = {
     "map5_3pl_j5_g1024": dict(model="irt_3pl", D=1, J=3, nodes=1024, span=6.0, N=400, seed=15, prior={}),
     "map6_3pl_j6_g1": dict(model="irt_3pl", D=1, J=4, nodes="one", span=6.0, N=300, seed=16,
                            prior={"a": (1.0, 0.5), "b": (0.0, 2.0)}),
+    "map7_1pl_j7_g61": dict(model="irt_1pl", D=1, J=5, nodes=61, span=6.0, N=500, seed=21, prior={}),
+    "map8_4pl_d2_j6_g225": dict(model="irt_4pl", D=2, J=4, nodes=15, span=5.0, N=1000, seed=22, prior={"a": (1.0, 0.5)}),
+    "map9_2pl_d3_j7_g343": dict(model="irt_2pl", D=3, J=5, nodes=7, span=4.0, N=800, seed=23, prior={"a": (1.0, 1.0)}),
+    "map10_4pl_d3_j9_g729": dict(model="irt_4pl", D=3, J=7, nodes=9, span=4.0, N=1500, seed=24, prior={"a": (1.0, 0.5)}, Dc=1.0),
 }
-EM_CASES = ("map1_3pl_j14_g41", "map2_4pl_j14_g41")
+EM_CASES = ("map1_3pl_j14_g41", "map2_4pl_j14_g41", "map7_1pl_j7_g61", "map8_4pl_d2_j6_g225", "map9_2pl_d3_j7_g343")
+EM_ENTRY_CASE = "map9_2pl_d3_j7_g343"                            # its end-to-end prior on a is given entry by entry (em_prior_of)
 EM_START = {"a": 1.0, "b": 0.0, "c": -1.4, "d": 2.2}           # the start of the end-to-end runs, every item alike
 
 
@@ -93,7 +112,7 @@ def case(name):
     b = rng.uniform(-1.5, 1.5, size=(1, J))
     c = rng.uniform(0.1, 0.3, size=(1, J))
     d = rng.uniform(0.85, 0.98, size=(1, J))
-    Dc = 1.702
+    Dc = spec.get("Dc", 1.702)
     x = rng.normal(size=(N, D))
     z = Dc * (x @ a + b)
     m = MODEL_NO[model]
@@ -237,10 +256,15 @@ def log_prior(p, fr, prior):
     return -0.5 * (fr * pr[1] * (p - pr[0]) ** 2).sum(0)
 
 
-def map_mstep(cs, n1, n0, p0, prior, newton, dtype=np.float64, stats=None, fr=None, theta=None):
+def map_mstep(cs, n1, n0, p0, prior, newton, dtype=np.float64, stats=None, fr=None, theta=None, trace=None, halving=0.5,
+              cap=STEP_CAP, cap_rescales=True, accept_unpenalised=False):
     """`newton` steps of the kernel's method on every item from p0 [6][J]: the new p [6][J] in `dtype`.  stats (a dict,
     optional) counts halvings, capped steps, stopped items and keeps "margin": the smallest (Q_trial - (Q - 1e-6 |Q|)) / |Q|
-    of any accepted FIRST trial (how clearly the full step was accepted)."""
+    of any accepted FIRST trial (how clearly the full step was accepted).  trace (a dict, optional) gets, an answered item j, the
+    list of its steps: {"capped", "halvings", "t" (the accepted step length), "delta" [6], "margins" (that quantity of EVERY
+    trial, rejected ones first), "stop" (None, "pivot" or "halvings")}.  The last four arguments make a WRONG kernel, for the
+    mutant checks of tests/test_map_host.py: another halving factor, another cap, a cap that clips each component instead of
+    rescaling the step, acceptance on Q_j without its penalty."""
     dt = np.dtype(dtype).type
     fr = free_rows(cs) if fr is None else fr
     U = design(np.asarray(cs["theta"] if theta is None else theta, dtype))
@@ -257,36 +281,55 @@ def map_mstep(cs, n1, n0, p0, prior, newton, dtype=np.float64, stats=None, fr=No
             continue
         pj = p[:, j].copy()
         ev = lambda v: item_eval(cs["model"], U, cs["Dc"], c1, c0, v, f, pr[0, :, j], pr[1, :, j], dtype)    # noqa: E731
+        if accept_unpenalised:                                          # (the mutant: the decision looks at Q_j without its penalty)
+            ev_p = ev
+            ev = lambda v: (item_eval(cs["model"], U, cs["Dc"], c1, c0, v, f, pr[0, :, j], 0 * pr[1, :, j], dtype)[0],) + ev_p(v)[1:]  # noqa: E731
         q, g, H, _ = ev(pj)
+        steps = []
+        if trace is not None:
+            trace[j] = steps
         for _ in range(newton):
+            rec = {"capped": False, "halvings": 0, "t": 0.0, "delta": None, "margins": [], "stop": None}
+            steps.append(rec)
             try:
                 L = np.linalg.cholesky(H[np.ix_(f, f)])
             except np.linalg.LinAlgError:
                 st["stopped"] += 1
+                rec["stop"] = "pivot"
                 break
             d = np.zeros(ROWS, dtype)
             d[f] = np.linalg.solve(L.T, np.linalg.solve(L, g[f])).astype(dtype)
             mx = np.abs(d).max()
             if not np.isfinite(mx):
                 st["stopped"] += 1
+                rec["stop"] = "pivot"
                 break
             t = dt(1)
-            if mx > STEP_CAP:
-                t = dt(STEP_CAP) / mx
+            if mx > cap:
                 st["capped"] += 1
+                rec["capped"] = True
+                if cap_rescales:
+                    t = dt(cap) / mx
+                else:
+                    d = np.clip(d, -dt(cap), dt(cap))
+            rec["delta"] = d.astype(np.float64)
             moved = False
             for h in range(HALVINGS + 1):
                 pt = np.where(f, pj + t * d, pj).astype(dtype)          # (what is not free keeps its bits)
                 qt, gt, Ht, _ = ev(pt)
+                rec["margins"].append(float((qt - (q - dt(QTOL) * abs(q))) / abs(q)))
                 if qt >= q - dt(QTOL) * abs(q):
                     if h == 0:
-                        st["margin"] = min(st["margin"], float((qt - (q - dt(QTOL) * abs(q))) / abs(q)))
+                        st["margin"] = min(st["margin"], rec["margins"][-1])
                     pj, q, g, H, moved = pt, qt, gt, Ht, True
+                    rec["t"] = float(t)
                     break
                 st["halvings"] += 1
-                t = t * dt(0.5)
+                rec["halvings"] += 1
+                t = t * dt(halving)
             if not moved:
                 st["stopped"] += 1
+                rec["stop"] = "halvings"
                 break
         p[:, j] = pj
     return p
@@ -400,9 +443,218 @@ def rule2(cs, L, p_out):
     return np.array(out), p64, st
 
 
+# ---- far starts ----------------------------------------------------------------------------------------------------------------
+# (case, amp, seed): one launch each, every item from p0 + free U(-amp, amp).  The seeds were picked from 1 .. 8 for the PATHS
+# the launch's items walk (tests/test_map_host.py asserts the cover) and, from those, for a float64 run of 64 steps that stops no
+# item; none was passed over for a float32 condition -- every clear item-start of that scan met them (docs/NOTEBOOK.md).
+FAR = [("map1_3pl_j14_g41", 1.5, 2), ("map1_3pl_j14_g41", 3.0, 4), ("map1_3pl_j14_g41", 5.0, 1),
+       ("map7_1pl_j7_g61", 1.5, 4), ("map7_1pl_j7_g61", 3.0, 4), ("map7_1pl_j7_g61", 5.0, 1),
+       ("map8_4pl_d2_j6_g225", 1.5, 7), ("map8_4pl_d2_j6_g225", 3.0, 3), ("map8_4pl_d2_j6_g225", 5.0, 1),
+       ("map9_2pl_d3_j7_g343", 1.5, 4), ("map9_2pl_d3_j7_g343", 3.0, 1), ("map9_2pl_d3_j7_g343", 5.0, 1),
+       ("map10_4pl_d3_j9_g729", 1.5, 5), ("map10_4pl_d3_j9_g729", 3.0, 6), ("map10_4pl_d3_j9_g729", 5.0, 1),
+       # every precision times 64 or 256: under the case's own priors no trial of any launch above is decided by the penalty (a
+       # kernel that accepted on Q_j without it would pass them all); here it decides trials of two to four items a launch
+       ("map1_3pl_j14_g41", 3.0, 2, 256.0), ("map8_4pl_d2_j6_g225", 3.0, 1, 256.0), ("map9_2pl_d3_j7_g343", 1.5, 2, 64.0)]
+# item-starts with clear float64 decisions that the one-step rule is NOT held on, with the reason (tests/test_map_host.py asserts
+# that they are at most one in ten): (case, amp, seed) -> {item: reason}
+FAR_DROPPED = {}
+# launches not held to rule 1 at the end (the rule is about a maximum reached), with the reason; tests/test_map_host.py asserts
+# that each fails a condition, and that they are at most one in ten
+FAR_NOT_TO_THE_END = {
+    ("map1_3pl_j14_g41", 5.0, 1): "item 5 starts at a = -1.7, b = -5.5, on the far side of a ridge: from there Q_j rises towards the plateau "
+                                  "P = c (a, b -> -inf; the case has no prior on either) and has no maximum to reach -- after 64 steps "
+                                  "float64 is still walking (b = -221), float32 has met the all-clamped pivot stop (b = -93)",
+}
+PATHS = ("capped and accepted", "halved once", "capped and halved", "two halvings in a step")
+CLEAR = 100.0                                                    # tolerances a decision must be away from the threshold
+
+
+def far_id(far):
+    return "%s_amp%g_seed%d" % far[:3] + ("_prec_x%g" % far[3] if len(far) > 3 else "")
+
+
+_FAR = {}
+
+
+def far_launch(far):
+    """launch(name) with p0 moved to p0 + free U(-amp, amp) (float32; what is fixed keeps its bits), built once.  A fourth entry
+    of `far` multiplies every precision: a prior that weighs as much as the tables, so that the penalty decides trials."""
+    if far not in _FAR:
+        name, amp, seed = far[:3]
+        L = dict(launch(name))
+        if len(far) > 3:
+            L["prior"] = L["prior"].copy()
+            L["prior"][1] *= np.float32(far[3])
+        rng = np.random.RandomState(seed)
+        L["p0"] = (L["p0"] + L["free"] * rng.uniform(-amp, amp, size=L["p0"].shape)).astype(np.float32)
+        del L["p0_near"]
+        _FAR[far] = L
+    return _FAR[far]
+
+
+def path_of(rec):
+    """The names (of PATHS) of one step's path; none for a full step accepted at once."""
+    out = set()
+    if rec["capped"] and rec["halvings"] == 0:
+        out.add(PATHS[0])
+    if not rec["capped"] and rec["halvings"] == 1:
+        out.add(PATHS[1])
+    if rec["capped"] and rec["halvings"] >= 1:
+        out.add(PATHS[2])
+    if rec["halvings"] >= 2:
+        out.add(PATHS[3])
+    return out
+
+
+def is_clear(rec):
+    """No stop, and every trial's decision CLEAR tolerances from the threshold: the rejected ones below, the accepted one above."""
+    m = rec["margins"]
+    return rec["stop"] is None and all(x <= -CLEAR * QTOL for x in m[:-1]) and m[-1] >= CLEAR * QTOL
+
+
+_FAR_STEP = {}
+
+
+def far_step(far):
+    """The float64 one-step result of a far launch and its trace, computed once: (p64 [6][J], trace)."""
+    if far not in _FAR_STEP:
+        cs, L = case(far[0]), far_launch(far)
+        tr = {}
+        p64 = map_mstep(cs, L["n1"], L["n0"], L["p0"].astype(np.float64), L["prior"].astype(np.float64), 1, trace=tr)
+        _FAR_STEP[far] = (p64, tr)
+    return _FAR_STEP[far]
+
+
+def far_candidates(far):
+    """The answered items of a far launch whose float64 step has clear decisions."""
+    return [j for j, steps in sorted(far_step(far)[1].items()) if is_clear(steps[0])]
+
+
+def far_items(far):
+    """The item-starts rule 3 is held on: the candidates but for FAR_DROPPED."""
+    return [j for j in far_candidates(far) if j not in FAR_DROPPED.get(far, {})]
+
+
+def rule3(far, p_out, items=None):
+    """Rule 3 for the output p_out [6][J] of ONE step from a far launch's p0: {item: max_k |p_out - p64|_k / (eps32 (t (|H^-1| S)_k
+    + [capped] |t delta_k| (|H^-1| S)_m / |delta_m| + |p64_k|))} over the free unknowns (against C_STEP), on `items` (default
+    far_items)."""
+    cs, L = case(far[0]), far_launch(far)
+    p64, tr = far_step(far)
+    pr = np.asarray(L["prior"], np.float64)
+    U = design(np.asarray(cs["theta"], np.float64))
+    p0 = L["p0"].astype(np.float64)
+    out = {}
+    for j in far_items(far) if items is None else items:
+        f, rec = L["free"][:, j], tr[j][0]
+        _, _, H, S = item_eval(cs["model"], U, cs["Dc"], L["n1"][j], L["n0"][j], p0[:, j], f, pr[0, :, j], pr[1, :, j])
+        hs = np.abs(np.linalg.inv(H[np.ix_(f, f)])) @ S[f]
+        dl, t = rec["delta"][f], rec["t"]
+        m = int(np.argmax(np.abs(dl)))
+        scale = t * hs + np.abs(p64[f, j])
+        if rec["capped"]:
+            scale = scale + np.abs(t * dl) * hs[m] / abs(dl[m])
+        out[j] = float((np.abs(np.asarray(p_out, np.float64)[f, j] - p64[f, j]) / (EPS32 * scale)).max())
+    return out
+
+
+# ---- the launches of the header's promises ---------------------------------------------------------------------------------------
+PIVOT_CASE, PIVOT_ITEM = "map9_2pl_d3_j7_g343", 0
+STEEP_CASE, STEEP_A = "map1_3pl_j14_g41", 4.5
+FALLING_CASE, FALLING_ITEM = "map2_4pl_j14_g41", 3
+
+
+def pivot_launch():
+    """The 2PL D = 3 launch with PIVOT_ITEM at b = 20, its loadings 0.01, and a prior on its b alone: every node is clamped
+    (|Dc (b + theta . a)| > logit(1 - eps32)), so its matrix is diag(prec_b, 0, 0, 0) -- a zero pivot for a_0."""
+    L = dict(launch(PIVOT_CASE))
+    j = PIVOT_ITEM
+    p0, pr = L["p0"].copy(), L["prior"].copy()
+    p0[0, j] = 20.0
+    p0[1:4, j] = np.float32(0.01) * L["free"][1:4, j]
+    pr[:, :, j] = 0
+    pr[1, 0, j] = 0.25
+    L["p0"], L["prior"] = p0, pr
+    del L["p0_near"]
+    return L
+
+
+def steep_launch():
+    """The 3PL D = 1 launch with every loading at STEEP_A on span 6: z reaches Dc 4.5 6 = 46, where Q = (1 - c) s(-z) < eps32."""
+    L = dict(launch(STEEP_CASE))
+    p0 = L["p0"].copy()
+    p0[1] = STEEP_A
+    L["p0"] = p0
+    del L["p0_near"]
+    return L
+
+
+def falling_launch():
+    """The 4PL D = 1 launch with FALLING_ITEM started at c_un = 0.5 > d_un = -0.5: a falling curve."""
+    L = dict(launch(FALLING_CASE))
+    p0 = L["p0"].copy()
+    p0[4, FALLING_ITEM], p0[5, FALLING_ITEM] = 0.5, -0.5
+    L["p0"] = p0
+    del L["p0_near"]
+    return L
+
+
+def node_masks(cs, p, dtype):
+    """(z [G], inside [G]) of one item at p [6] in `dtype`, as item_eval forms them: 1PL / 2PL inside = the clamp of z is not
+    active; 3PL / 4PL inside = P >= eps32 and Q >= eps32."""
+    dt = np.dtype(dtype).type
+    m = MODEL_NO[cs["model"]]
+    p = np.asarray(p, dtype)
+    z = dt(cs["Dc"]) * (design(np.asarray(cs["theta"], dtype)) @ p[:4])
+    if m <= 2:
+        return z, np.abs(z) <= dt(ZL)
+    eps = dt(EPS32)
+    c = min(dt(_sig(p[4])), dt(1) - eps)
+    d = min(dt(_sig(p[5])), dt(1) - eps) if m == 4 else dt(1)
+    omd = max(dt(_sig(-p[5])), eps) if m == 4 else dt(0)
+    e = np.exp(-np.abs(z))
+    sg = np.where(z >= 0, 1 / (1 + e), e / (1 + e)).astype(dtype)
+    sn = np.where(z >= 0, e / (1 + e), 1 / (1 + e)).astype(dtype)
+    return z, (c + (d - c) * sg >= eps) & (omd + (d - c) * sn >= eps)
+
+
+def unread_nan(cs, L):
+    """L's prior with NaN in every entry the call must not read: mean and precision of the masked loadings, the a rows at or
+    beyond D (all of them for 1PL), the c / d rows the model does not have."""
+    pr = L["prior"].copy()
+    pr[:, ~L["free"]] = np.nan
+    return pr
+
+
+def scaled4(L):
+    """L with n1, n0 and every precision times 4 (exact in float32)."""
+    out = dict(L)
+    pr = L["prior"].copy()
+    pr[1] *= 4
+    out.update(n1=L["n1"] * np.float32(4), n0=L["n0"] * np.float32(4), prior=pr)
+    return out
+
+
 # ---- EM ----------------------------------------------------------------------------------------------------------------------
 def em_start(cs):
-    return {k: np.full(v.shape, EM_START[k], np.float32) for k, v in cs["start"].items()}
+    """Every item alike (EM_START), the masked loadings zero."""
+    out = {k: np.full(v.shape, EM_START[k], np.float32) for k, v in cs["start"].items()}
+    if "a" in out:
+        out["a"] = (out["a"] * cs["a_free"]).astype(np.float32)
+    return out
+
+
+def em_prior_of(cs):
+    """The `prior` of the end-to-end runs: the case's own, but for EM_ENTRY_CASE, whose prior on a is given as full [D][J] arrays
+    (grid.em_prior's per-entry path) -- the case's mean and sd at every loading, sd = inf (no prior) at the masked loadings and
+    at two free ones, a_0 of item 2 and a_1 of item 3."""
+    if cs["name"] != EM_ENTRY_CASE:
+        return cs["prior"]
+    mean, sd = cs["prior"]["a"]
+    mean, sd = np.full((cs["D"], cs["J"]), float(mean)), np.full((cs["D"], cs["J"]), float(sd))
+    sd[~cs["a_free"]] = np.inf
+    sd[0, 2] = sd[1, 3] = np.inf
+    return dict(cs["prior"], a=(mean, sd))
 
 
 def em_iteration(cs, params, prior, newton=4, dtype=np.float64, stats=None):
@@ -424,7 +676,7 @@ def trajectory(name, iters, newton=4, dtype=np.float64):
     if key not in _TRAJ:
         _TRAJ[key] = ([{k: v.astype(np.float64) for k, v in em_start(cs).items()}], [], [], {})
     ps, lks, lps, stats = _TRAJ[key]
-    prior = prior_rows(cs)
+    prior = prior_rows(cs, em_prior_of(cs))
     while len(lks) < iters:
         p, lk, lp = em_iteration(cs, ps[-1], prior, newton, dtype, stats)
         ps.append(p)
@@ -437,7 +689,7 @@ def posterior_sd(cs, params):
     """sqrt((H^-1)_kk) of every free unknown at `params` on the tables of `params`, as leaves (NaN where fixed or unanswered),
     and |Q_j| [J]: the scales of the end-to-end comparisons."""
     n1, n0, _ = tables(cs, params)
-    pr = np.asarray(prior_rows(cs), np.float64)
+    pr = np.asarray(prior_rows(cs, em_prior_of(cs)), np.float64)
     fr, p = free_rows(cs), pack(cs, params)
     U = design(np.asarray(cs["theta"], np.float64))
     sd, qs = np.full((ROWS, cs["J"]), np.nan), np.zeros(cs["J"])

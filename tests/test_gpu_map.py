@@ -8,7 +8,9 @@ Every rule is path-independent: none follows the kernel's accept / reject decisi
   3. Exact statements: the same bits twice, item j alone gives its bits of the full launch, what is fixed keeps its bits,
      lprior is the float64 log prior at the incoming parameters to float32 rounding, and precision 0 everywhere on the 2PL
      case agrees with vx_grid_mstep_irt.
-  4. End to end: fit_em(prior=) on the 3PL and the 4PL case.
+  4. End to end: fit_em(prior=) on the 3PL and the 4PL case, on the 1PL case, and at x_feature = 2 (4PL) and 3 (2PL, its prior
+     on a given entry by entry) with the engine's own triangular mask.
+The step control from far starts and the exact promises of the kernel's header: tests/test_gpu_map_paths.py.
 C_Q = 16 and C_STEP = 32 are reasoned in tests/map_cases.py; the method alone (float32 numpy) meets both at half.  Largest
 ratios on an MI355X are printed by the tests and recorded in DESIGN.md section 6."""
 import numpy as np
@@ -32,8 +34,9 @@ def _t(v, dtype=torch.float32):
     return torch.from_numpy(np.ascontiguousarray(v)).to(device=_dev(), dtype=dtype).contiguous()
 
 
-def _launch(cs, L, p0, newton, prior=None, items=None, lprior=False):
-    """One launch on the items `items` (default all) of a case from p0 [6][J]: (p [6][J'] float32, lprior [J'] or None)."""
+def _launch(cs, L, p0, newton, prior=None, items=None, lprior=False, a_free="case"):
+    """One launch on the items `items` (default all) of a case from p0 [6][J]: (p [6][J'] float32, lprior [J'] or None).
+    a_free: the case's mask, or a [D][J] array, or None (the NULL pointer: every loading free)."""
     from vipsy_amd.engine import HipBackend
     be = HipBackend()
     sel = np.arange(cs["J"]) if items is None else np.asarray(items)
@@ -41,7 +44,8 @@ def _launch(cs, L, p0, newton, prior=None, items=None, lprior=False):
     p0 = np.asarray(p0, np.float32)[:, sel]
     pr = np.ascontiguousarray(np.asarray(L["prior"] if prior is None else prior, np.float32)[:, :, sel])
     a = _t(p0[1:1 + D]) if m >= 2 else None
-    fr = _t(cs["a_free"][:, sel].astype(np.float32)) if m >= 2 else None
+    mask = cs["a_free"] if isinstance(a_free, str) else a_free
+    fr = _t(np.asarray(mask)[:, sel].astype(np.float32)) if m >= 2 and mask is not None else None
     b, c, d = _t(p0[0]), (_t(p0[4]) if m >= 3 else None), (_t(p0[5]) if m == 4 else None)
     lp = torch.full((J,), float("nan"), device=_dev()) if lprior else None
     cfg = be.cfg(cs["model"], D, J, 0, cs["Dc"], 1.0, 0, 0, 0)
@@ -156,14 +160,16 @@ def _model(name, cls=None, items=None):
     cs = mc.case(name)
     vi.clear_param_store()
     y = cs["y"] if items is None else np.ascontiguousarray(cs["y"][:, :items])
-    m = (cls or vi.VIRT)(data=torch.from_numpy(y).to(_dev()), model=cs["model"], x_feature=1, D=cs["Dc"], seed=3)
+    m = (cls or vi.VIRT)(data=torch.from_numpy(y).to(_dev()), model=cs["model"], x_feature=cs["D"], D=cs["Dc"], seed=3)
+    if cs["a_free"] is not None and items is None:                       # (the engine's own mask is the case's)
+        assert np.array_equal(_np(m.engine.unconstrained("a", m.engine.free)) != 0, cs["a_free"])
     for k, v in mc.em_start(cs).items():
         m.engine.unconstrained(k).copy_(_t(v[:, :y.shape[1]]))
     return m, cs
 
 
 def _kw(cs):
-    return dict(prior=cs["prior"], nodes=cs["nodes"], span=cs["span"])
+    return dict(prior=mc.em_prior_of(cs), nodes=cs["nodes"], span=cs["span"])
 
 
 _FIT = {}
@@ -231,19 +237,42 @@ def test_fit_em_ends_where_the_oracle_ends(name):
     assert np.all(np.isfinite(np.concatenate([v.reshape(-1) for v in got.values()])))
 
 
-@pytest.mark.parametrize("amortized", [True, False], ids=["VaeIRT_padded_J13", "VIRT"])
-def test_nothing_else_moved(amortized):
-    """Thirteen items of the 4PL case: VaeIRT pads them to sixteen.  The guide, Adam's moments, the step count and the phantom
-    items keep their bits; the four leaves of the own items move."""
+def _model_2pl_d2():
+    """Thirteen items of the 3PL case's responses under a VaeIRT 2PL with x_feature = 2: a padded engine, in whose `a` segment
+    phantom items lie between the two rows of own loadings: the own items do NOT lead it."""
     from vipsy_amd import vi
-    m, cs = _model("map2_4pl_j14_g41", cls=vi.VaeIRT if amortized else vi.VIRT, items=13)
+    cs = mc.case("map1_3pl_j14_g41")
+    vi.clear_param_store()
+    y = np.ascontiguousarray(cs["y"][:, :13])
+    m = vi.VaeIRT(data=torch.from_numpy(y).to(_dev()), model="irt_2pl", x_feature=2, D=cs["Dc"], seed=3)
+    free = _np(m.engine.unconstrained("a", m.engine.free)) != 0
+    assert free.shape == (2, 13) and not free.all()                     # (the triangular default: a masked loading)
+    m.engine.unconstrained("a").copy_(_t(np.where(free, 1.0, 0.0)))
+    m.engine.unconstrained("b").copy_(_t(np.zeros((1, 13))))
+    return m, dict(cs, model="irt_2pl", prior={"a": (1.0, 0.5)}, nodes=15, span=5.0)
+
+
+@pytest.mark.parametrize("kind", ["VaeIRT_padded_J13", "VIRT", "VaeIRT_2pl_d2_padded_J13"])
+def test_nothing_else_moved(kind):
+    """Thirteen items of the 4PL case: VaeIRT pads them to sixteen.  The guide, Adam's moments, the step count and the phantom
+    items keep their bits; the four leaves of the own items move.  And thirteen items under a VaeIRT 2PL with x_feature = 2:
+    the masked loadings keep their bits too, the own free loadings and b move."""
+    from vipsy_amd import vi
+    amortized, d2 = kind != "VIRT", kind == "VaeIRT_2pl_d2_padded_J13"
+    m, cs = _model_2pl_d2() if d2 else _model("map2_4pl_j14_g41", cls=vi.VaeIRT if amortized else vi.VIRT, items=13)
     eng = m.engine
+    leaves = ("a", "b") if d2 else ("a", "b", "c", "d")
     if amortized:
         assert eng.J > eng.J_items == 13                                # the padded engine: phantom items
     keep = torch.ones(eng.n_params, dtype=torch.bool, device=eng.dev)
-    for name in ("a", "b", "c", "d"):
-        o = eng.off[name]
-        keep[o:o + eng.J_items] = False                                # (D = 1: the own items lead each segment)
+    for name in leaves:
+        eng.unconstrained(name, keep)[...] = False                     # (a view of `keep`: the own items, wherever they lie)
+    if d2:
+        o = eng.off["a"]
+        J = eng.J                                                      # phantom items part the two rows of the own loadings
+        assert not keep[o:o + 13].any() and keep[o + 13:o + J].all() and not keep[o + J:o + J + 13].any() and keep[o + J + 13:o + 2 * J].all()
+        free = eng.unconstrained("a", eng.free) != 0
+        eng.unconstrained("a", keep)[~free] = True                     # the masked loadings are to keep their bits as well
     state = {"P": eng.P.clone(), "M": eng.M.clone(), "V": eng.V.clone(), "G": eng.G.clone()}
     if eng.per_person:
         state.update({"PP": eng.PP.clone(), "MP": eng.MP.clone(), "VP": eng.VP.clone()})
@@ -253,13 +282,13 @@ def test_nothing_else_moved(amortized):
     torch.cuda.synchronize()
     assert eng.t == t0 and len(out["logpost"]) == 2
     assert torch.equal(eng.P[keep], state["P"][keep])
-    for name in ("a", "b", "c", "d"):
-        o = eng.off[name]
-        own = slice(o, o + eng.J_items)
-        answered = torch.ones(eng.J_items, dtype=torch.bool, device=eng.dev)
-        answered[mc.UNANSWERED] = False
-        assert (eng.P[own][answered] != state["P"][own][answered]).all(), name
-        assert torch.equal(eng.P[own][~answered], state["P"][own][~answered]), name
+    answered = torch.ones(eng.J_items, dtype=torch.bool, device=eng.dev)
+    answered[mc.UNANSWERED] = False
+    for name in leaves:
+        now, was = eng.unconstrained(name), eng.unconstrained(name, state["P"])
+        moves = answered[None, :] & (eng.unconstrained(name, eng.free) != 0)
+        assert (now[moves] != was[moves]).all(), name
+        assert torch.equal(now[~moves], was[~moves]), name
     for k in state:
         if k != "P":
             assert torch.equal(getattr(eng, k), state[k]), k
