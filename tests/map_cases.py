@@ -1,5 +1,5 @@
 """The cases, the float64 oracle and the float32 restatement of the penalised M-step (vx_grid_mstep_irt_map,
-vipsy_amd/csrc/k_grid_mstep_map.hip) and of fit_em(prior=): tests/test_map_host.py on the CPU, tests/test_gpu_map.py and
+vipsy_amd/csrc/k_grid_mstep.hip) and of fit_em(prior=): tests/test_map_host.py on the CPU, tests/test_gpu_map.py and
 tests/test_gpu_map_paths.py on the GPU.
 
 Unknowns of an item, everywhere in this file, as the kernel orders them: p = (b, a_0, a_1, a_2, c_un, d_un) -- six rows whatever
@@ -231,7 +231,7 @@ def item_eval(model, U, Dc, c1, c0, p, fr, pm, pp, dtype=np.float64):
         P, Q = c + (d - c) * sg, omd + (d - c) * sn
         inside = (P >= eps) & (Q >= eps)
         Pc, Qc = np.clip(P, eps, dt(1) - eps), np.clip(Q, eps, dt(1) - eps)
-        small = np.minimum(Pc, Qc)                                     # log of the larger one as log1p(-the smaller): gmm_log1m
+        small = np.minimum(Pc, Qc)                                     # log of the larger one as log1p(-the smaller): gm_log1m
         ls, lb = np.log(small), np.log1p(-small)
         lp1, lp0 = np.where(Pc >= Qc, lb, ls).astype(dtype), np.where(Pc >= Qc, ls, lb).astype(dtype)
         inv = np.where(inside, 1 / (Pc * Qc), 0).astype(dtype)

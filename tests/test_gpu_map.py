@@ -7,7 +7,7 @@ Every rule is path-independent: none follows the kernel's accept / reject decisi
      output is the float64 one-step result to C_STEP eps32 |H^-1| S.
   3. Exact statements: the same bits twice, item j alone gives its bits of the full launch, what is fixed keeps its bits,
      lprior is the float64 log prior at the incoming parameters to float32 rounding, and precision 0 everywhere on the 2PL
-     case agrees with vx_grid_mstep_irt.
+     case agrees with vx_grid_mstep_irt -- in a and b to the bit, on the 1PL case and at D = 2 and 3 too.
   4. End to end: fit_em(prior=) on the 3PL and the 4PL case, on the 1PL case, and at x_feature = 2 (4PL) and 3 (2PL, its prior
      on a given entry by entry) with the engine's own triangular mask.
 The step control from far starts and the exact promises of the kernel's header: tests/test_gpu_map_paths.py.
@@ -152,6 +152,39 @@ def test_precision_zero_agrees_with_the_unpenalised_entry():
         print("%s, precision 0: gain at most %.3g, parameters at most %.3g" % (tag, gain.max(), dev.max()))
         assert last <= 1e-6 and gain.max() <= mc.C_Q and dev.max() <= 1.0, (tag, gain, dev)
     assert p[:, mc.UNANSWERED].tobytes() == q[:, mc.UNANSWERED].tobytes()
+
+
+# map_cases has no 2PL case at D = 2: the 3PL D = 2 case's tables, grid, mask and start, launched as a 2PL (c_un is not passed)
+ZERO_PRECISION = [("map4_2pl_j8_g61", None), ("map7_1pl_j7_g61", None), ("map3_3pl_d2_j7_g441", "irt_2pl"),
+                  ("map9_2pl_d3_j7_g343", None)]
+
+
+@pytest.mark.parametrize("name,model", ZERO_PRECISION, ids=["2pl_d1", "1pl", "2pl_d2", "2pl_d3"])
+def test_precision_zero_gives_the_bits_of_the_unpenalised_entry(name, model):
+    """Every precision 0 with finite means (the case's own), the same start, the constant item left out: both entries are one
+    kernel, and what a prior adds to it is then nothing -- the penalty and its gradient term are products with 0, adding +-0 to
+    a float that is not zero changes no bit of it, and a step of zero leaves p where it was.  a and b come back the same bytes."""
+    from vipsy_amd.engine import HipBackend
+    cs, L = mc.case(name), mc.launch(name)
+    if model is not None:
+        cs = dict(cs, model=model)
+    sel = np.arange(cs["J"] - 1)
+    D, two = cs["D"], cs["model"] != "irt_1pl"
+    pr = L["prior"].copy()
+    pr[1] = 0
+    assert np.isfinite(pr[0]).all()
+    p, _ = _launch(cs, L, L["p0"], 64, prior=pr, items=sel)
+    be = HipBackend()
+    a, b = (_t(L["p0"][1:1 + D, sel]) if two else None), _t(L["p0"][0, sel])
+    fr = _t(cs["a_free"][:, sel].astype(np.float32)) if two else None
+    be.grid_mstep_irt(be.cfg(cs["model"], D, len(sel), 0, cs["Dc"], 1.0, 0, 0, 0), _t(cs["theta"]), cs["G"], _t(L["n1"][sel]),
+                      _t(L["n0"][sel]), fr, a, b, 64)
+    torch.cuda.synchronize()
+    assert p[0].tobytes() == _np(b).tobytes()
+    if two:
+        assert p[1:1 + D].tobytes() == _np(a).tobytes()
+    moved = L["free"][:1 + D, sel] & mc.answered(L)[None, sel]
+    assert (p[:1 + D][moved] != L["p0"][:1 + D, sel][moved]).all()     # (both moved: the same bytes are not the start's)
 
 
 # ---- 4. end to end -------------------------------------------------------------------------------------------------------------

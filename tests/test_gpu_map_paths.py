@@ -1,5 +1,5 @@
 """vx_grid_mstep_irt_map on the GPU where tests/test_gpu_map.py does not take it: the step control of the penalised kernel from far
-starts, and the sentences of the kernel's header (vipsy_amd/csrc/k_grid_mstep_map.hip) that are exact promises.
+starts, and the sentences of the kernel's header (vipsy_amd/csrc/k_grid_mstep.hip) that are exact promises.
 
   A. Far starts (tests/map_cases.py: FAR -- p0 + free U(-amp, amp), amp 1.5, 3 and 5, on the 3PL, 1PL, 4PL D = 2, 2PL D = 3 and
      4PL D = 3 cases, and three launches under priors 64 and 256 times as precise, where the penalty decides trials).

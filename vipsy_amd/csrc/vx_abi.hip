@@ -34,7 +34,6 @@
 #include "k_grid_counts.hip"
 #include "k_grid_draw.hip"
 #include "k_grid_mstep.hip"
-#include "k_grid_mstep_map.hip"
 #include "k_grid_info.hip"
 #include "k_grid_pairs.hip"
 #include "k_grid_fit.hip"
@@ -2444,36 +2443,37 @@ int vx_grid_counts_cond(const uint8_t* y, const int64_t* rows, int64_t nb, int32
     });
 }
 
-// The M-step on the expected-count tables (k_grid_mstep.hip): one wave an item, every Newton step inside the one launch
-int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0, const float* a_free,
-                      float* a, float* b, int32_t newton, void* hs) {
-    if (!irt_items_ok(cfg, 2, GM_MAXD, a, b, nullptr, nullptr) || !grid_shape_ok(cfg->J, G, 1) || newton < 1 || newton > GM_MAX_NEWTON ||
-        !theta || !n1 || !n0)
+// The M-step on the expected-count tables (k_grid_mstep.hip): one wave an item, every Newton step inside the one launch.  One
+// launcher behind both entries; `penalised` is the kernel's PRIOR: all four models, with a normal prior an unknown.
+static int grid_mstep_irt(bool penalised, const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0,
+                          const float* a_free, float* a, float* b, float* c_un, float* d_un, const float* prior, int32_t newton,
+                          float* lprior, void* hs) {
+    if (!irt_items_ok(cfg, penalised ? 4 : 2, GM_MAXD, a, b, c_un, d_un) || !grid_shape_ok(cfg->J, G, 1) || newton < 1 ||
+        newton > GM_MAX_NEWTON || !theta || !n1 || !n0 || (penalised && !prior))
         return VX_EINVAL;
     const dim3 grid((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES));
     return with_irt_model(cfg->model, [&](auto m) -> int {
-        constexpr int M = decltype(m)::value < 2 ? 1 : 2;                               // (the gate admits 1PL and 2PL only)
-        hipLaunchKernelGGL((k_grid_mstep_irt<M>), grid, dim3(GM_THREADS), 0, (hipStream_t)hs, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc,
-                           theta, n1, n0, a_free, a, b, (int)newton);
-        VX_CHECK_LAUNCH();
-        return VX_OK;
+        auto launch = [&](auto pr) -> int {
+            constexpr bool PRIOR = decltype(pr)::value;
+            constexpr int M = PRIOR || decltype(m)::value < 2 ? decltype(m)::value : 2;     // (without a prior the gate admits 1PL and 2PL only)
+            hipLaunchKernelGGL((k_grid_mstep_irt<M, PRIOR>), grid, dim3(GM_THREADS), 0, (hipStream_t)hs, (int)cfg->D, (int)cfg->J, (int)G,
+                               cfg->Dc, theta, n1, n0, a_free, a, b, c_un, d_un, prior, lprior, (int)newton);
+            VX_CHECK_LAUNCH();
+            return VX_OK;
+        };
+        return penalised ? launch(std::true_type()) : launch(std::false_type());
     });
 }
 
-// The penalised M-step (k_grid_mstep_map.hip): vx_grid_mstep_irt's launch for all four models, with a normal prior an unknown.
+int vx_grid_mstep_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0, const float* a_free,
+                      float* a, float* b, int32_t newton, void* hs) {
+    return grid_mstep_irt(false, cfg, theta, G, n1, n0, a_free, a, b, nullptr, nullptr, nullptr, newton, nullptr, hs);
+}
+
 // The precisions live in device memory: that they are >= 0 and finite is checked where `prior` is made (vipsy_amd/grid.py).
 int vx_grid_mstep_irt_map(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* n1, const float* n0, const float* a_free,
                           float* a, float* b, float* c_un, float* d_un, const float* prior, int32_t newton, float* lprior, void* hs) {
-    if (!irt_items_ok(cfg, 4, GM_MAXD, a, b, c_un, d_un) || !grid_shape_ok(cfg->J, G, 1) || newton < 1 || newton > GM_MAX_NEWTON ||
-        !theta || !n1 || !n0 || !prior)
-        return VX_EINVAL;
-    const dim3 grid((unsigned)((cfg->J + GM_WAVES - 1) / GM_WAVES));
-    return with_irt_model(cfg->model, [&](auto m) -> int {
-        hipLaunchKernelGGL((k_grid_mstep_irt_map<decltype(m)::value>), grid, dim3(GM_THREADS), 0, (hipStream_t)hs, (int)cfg->D,
-                           (int)cfg->J, (int)G, cfg->Dc, theta, n1, n0, a_free, a, b, c_un, d_un, prior, lprior, (int)newton);
-        VX_CHECK_LAUNCH();
-        return VX_OK;
-    });
+    return grid_mstep_irt(true, cfg, theta, G, n1, n0, a_free, a, b, c_un, d_un, prior, newton, lprior, hs);
 }
 
 int vx_grid_mstep_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* n1, const float* n0, float* g_un,

@@ -1858,19 +1858,18 @@ class IrtEngine(GridMixin, _EngineBase):
         a = self.unconstrained("a").contiguous().clone() if two else None
         free = self.unconstrained("a", self.free).contiguous().clone() if two else None
         b = self.unconstrained("b").reshape(-1).contiguous().clone()
-        if prior is None:
-            call = self._grid_call(None, None, nodes, span, params=(a, b, None, None))
-            return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_irt(call.cfg, call.theta, call.G, n1, n0, free, a, b, newton),
-                                 {"a": a, "b": b} if two else {"b": b}, max_iter, tol, progress)
-        pr = torch.from_numpy(em_prior(prior, self.model, self.D_model, self.J_items)).to(self.dev)
+        pr = None if prior is None else torch.from_numpy(em_prior(prior, self.model, self.D_model, self.J_items)).to(self.dev)
         c = self.unconstrained("c").reshape(-1).contiguous().clone() if self.model in ("irt_3pl", "irt_4pl") else None
         d = self.unconstrained("d").reshape(-1).contiguous().clone() if self.model == "irt_4pl" else None
-        lprior = torch.zeros(self.J_items, dtype=torch.float32, device=self.dev)
+        lprior = None if prior is None else torch.zeros(self.J_items, dtype=torch.float32, device=self.dev)
         call = self._grid_call(None, None, nodes, span, params=(a, b, c, d))
+        if prior is None:
+            mstep = lambda n1, n0: self.be.grid_mstep_irt(call.cfg, call.theta, call.G, n1, n0, free, a, b, newton)
+        else:
+            mstep = lambda n1, n0: self.be.grid_mstep_irt_map(call.cfg, call.theta, call.G, n1, n0, free, a, b, c, d, pr, newton,
+                                                              lprior)
         leaves = {k: v for k, v in (("a", a), ("b", b), ("c", c), ("d", d)) if v is not None}
-        return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_irt_map(call.cfg, call.theta, call.G, n1, n0, free, a, b, c, d,
-                                                                             pr, newton, lprior),
-                             leaves, max_iter, tol, progress, lprior=lprior)
+        return self._em_loop(call, mstep, leaves, max_iter, tol, progress, lprior=lprior)
 
     def _info_call(self, y_u8, rows, nodes=61, span=6.0):
         """What GridMixin.item_information needs of this class: the GridCall, K (columns an item: b, then a_0 .. a_{D-1}; 1PL: b),

@@ -57,7 +57,7 @@ def score_grid(D, nodes=61, span=6.0):
     return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
 
 
-EM_PRIOR_ROWS = 6                # GMM_ROWS (vipsy_amd/csrc/k_grid_mstep_map.hip): b, a_0 .. a_2, c_un, d_un
+EM_PRIOR_ROWS = 6                # GM_ROWS (vipsy_amd/csrc/k_grid_mstep.hip): b, a_0 .. a_2, c_un, d_un
 EM_PRIOR_KEYS = {"irt_1pl": ("b",), "irt_2pl": ("a", "b"), "irt_3pl": ("a", "b", "c"), "irt_4pl": ("a", "b", "c", "d")}
 
 
