@@ -574,23 +574,35 @@ int vx_grid_mstep_irt_map(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, 
  *     s_i[(j,k)] = sum_g p_i(g) ( [y_ij == 1] W1[g][(j,k)] - [y_ij == 0] W0[g][(j,k)] ),   W1 = (1 - P_j(g)) u_jgk,  W0 = P_j(g) u_jgk,
  * p_i(g) as vx_grid_counts forms it, u_g = Dc (1, theta_g) for the IRT links, ([eta = 0], -[eta = 1]) for DINA / DINO on the
  * unconstrained g / s scale.  info = sum_i s_i s_i^T [P][P], symmetric bit for bit, over the DENSE parameter layout: column
- * c = j K + k with K = D + 1 (k = 0: b, k = 1 + d: a_d) for 2PL, 1 for 1PL, 2 (g_un, s_un) for DINA / DINO, P = J K <= 4096;
+ * c = j K + k with K = D + 1 (k = 0: b, k = 1 + d: a_d) for 2PL, 1 for 1PL, 2 (g_un, s_un) for DINA / DINO; 3PL / 4PL (the tables of
+ * vx_grid_wtable_irt_map) add k = D + 1: c_un and, for 4PL, k = D + 2: d_un, K = D + 2 / D + 3 <= 6; P = J K <= 4096;
  * gradient = sum_i s_i [P], the gradient of the marginal log-likelihood -- by construction what the M-step of vx_grid_mstep_irt
  * forms from n1 / n0: P, 1 - P and the clamp come from its cell (a node where the z clamp is active contributes 0).  Both are taken
  * AT THE PARAMETERS AS THEY STAND; the inverse of info is a covariance only at the marginal maximum.
  *   1. vx_grid_wtable_irt (cfg: model 1 | 2, D <= 3, J, Dc) / vx_grid_wtable_cdm (cfg: K, J) fill `wimg` (vx_grid_wimage_bytes(P, G)
  *      bytes, 16-byte aligned) with W1 / W0 as fp16-pair operand images, scaled by a power of two that the image carries.
+ *      vx_grid_wtable_irt_map (cfg: model 1 .. 4) is the table at the fit of vx_grid_mstep_irt_map.  Models 1 and 2: the image of
+ *      vx_grid_wtable_irt, byte for byte.  Models 3 and 4: the cell of that M-step (c, d, 1 - d capped, P = c + (d - c) s(z),
+ *      Q = (1 - d) + (d - c) s(-z), a node with P or Q below eps32 contributes 0), W1 = v / P and W0 = v / Q with v the derivative
+ *      of P: (d - c) s(z) s(-z) Dc (1, theta_g) for b and a, s(-z) c (1 - c) for c_un, s(z) d (1 - d) for d_un.  `gradient` is then
+ *      the likelihood part of what vx_grid_mstep_irt_map forms from n1 / n0.  A 3PL entry stays below max(1, Dc max(1, |theta|_inf)),
+ *      but a 4PL entry grows like 1 / (d - c) and d <= c is admissible: the power of two comes from the table's own largest
+ *      magnitude, found in a first pass by an integer maximum (no float atomics: the same call gives the same bits), and the
+ *      image carries |W 2^s| < 2^15.  It refuses J K > 4096.
  *   2. vx_grid_info: y, rows, nb, img, logw as vx_grid_posterior took them and loglik as it returned it.  Three chained products on
  *      v_mfma_f32_32x32x16_f16 (fp16 pairs, fp32 accumulation): the log-likelihoods, p W (over nodes) and S^T S (over persons).
  *      Nothing of size [nb][G] touches memory; S [persons][P] lives in `workspace` as fp16 pairs, a slab of persons (a multiple of
  *      256) at a time -- as many as ws_floats allow --, and the slabs' matrices are added in person order.  No atomics: the same
  *      call with the same ws_floats gives the same bits.  vx_grid_info_workspace_floats(nb, P, G): the preferred size (one slab
  *      where 512 MB allow it); vx_grid_info_workspace_min_floats(P, G): the smallest accepted.  workspace is 16-byte aligned.
- * Persons' 254 / 255 cells contribute nothing.  Limits: 1 <= J <= 1024, 1 <= G <= 1024, 1 <= K <= 4, nb >= 1, ws_floats at least the
+ * Persons' 254 / 255 cells contribute nothing.  Limits: 1 <= J <= 1024, 1 <= G <= 1024, 1 <= K <= 6, J K <= 4096, nb >= 1, ws_floats at least the
  * minimum; VX_EINVAL beyond. */
 int64_t vx_grid_wimage_bytes(int32_t P, int32_t G);
 int vx_grid_wtable_irt(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int32_t G, const float* a /*[D][J] or NULL (1PL)*/,
                        const float* b /*[J]*/, void* wimg, void* hip_stream);
+int vx_grid_wtable_irt_map(const vx_irt_cfg* cfg, const float* theta /*[G][D]*/, int32_t G, const float* a /*[D][J] or NULL (1PL)*/,
+                           const float* b /*[J]*/, const float* c_un /*[J], model >= 3*/, const float* d_un /*[J], model 4*/,
+                           void* wimg, void* hip_stream);
 int vx_grid_wtable_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q /*[K][J]*/, const float* g_un, const float* s_un,
                        void* wimg, void* hip_stream);
 int64_t vx_grid_info_workspace_floats(int64_t nb, int32_t P, int32_t G);

@@ -13,7 +13,13 @@ Shapes: 1M persons x 500 items x 61 nodes (2PL, P = 1 000 parameters), 1M x 40 i
     fp16 peak): useful FLOP = 2 n (2 J G + 2 P G) for k_grid_pscores, 2 n P (P + 1) / 2 for k_grid_xprod.
 The times are reported, not asserted.
 
-usage (GPU box):  python tools/se_probe.py [out.txt]        VX_PROBE_SCALE=0.01 shrinks the person counts (rehearsal)"""
+--model irt_3pl | irt_4pl: item_se(prior=) instead, at 1M persons x 500 items x 61 nodes (P = 1 500 / 2 000) under the priors
+c_un ~ N(-1.4, 1), d_un ~ N(2.2, 1), behind the 2PL shape of the same size for comparison: the table entry
+(vx_grid_wtable_irt_map: the maximum pass, the trailer, the fill pass; device events around 200 back-to-back calls, and each
+kernel's device time by torch.profiler), vx_grid_info at K = 3 / 4, item_se(prior=) end to end, and 4 096 sampled persons
+against the float64 oracle of tests/se_map_cases.py.
+
+usage (GPU box):  python tools/se_probe.py [out.txt] [--model irt_3pl]        VX_PROBE_SCALE=0.01 shrinks the person counts (rehearsal)"""
 import os
 import sys
 import time
@@ -79,9 +85,9 @@ def torch_info(y, T1, T0, logw, W1, W0, K):
     return info, grad
 
 
-def kernel_times(fn):
-    """Device microseconds of k_grid_pscores and k_grid_xprod inside one call of fn, or None where the profiler has no device
-    activity to offer."""
+def kernel_times(fn, names=("k_grid_pscores", "k_grid_xprod")):
+    """Device microseconds of the kernels whose names contain one of `names` inside one call of fn, or None where the profiler
+    has no device activity to offer."""
     try:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
@@ -92,10 +98,10 @@ def kernel_times(fn):
             t = getattr(ev, "device_time_total", None)
             if t is None:
                 t = getattr(ev, "cuda_time_total", 0.0)
-            for k in ("k_grid_pscores", "k_grid_xprod"):
+            for k in names:
                 if k in ev.key:
                     out[k] = out.get(k, 0.0) + float(t)
-        return out if len(out) == 2 else None
+        return out if len(out) == len(names) else None
     except Exception as e:  # noqa: BLE001
         say("    (no kernel times: %s)" % e)
         return None
@@ -119,6 +125,7 @@ def probe(tag, eng, kw, cs, kind, T1, T0):
 
     t_info = timed(run)
     kt = kernel_times(run)
+    t_table = timed(lambda: fill_wtable(wimg), warm=5, reps=200)
     W1n, W0n, _ = se.tables(cs, kind, cs["params"])
     W1, W0 = torch.from_numpy(W1n.astype(np.float32)).to(dev), torch.from_numpy(W0n.astype(np.float32)).to(dev)
     t_torch = timed(lambda: torch_info(y, T1, T0, call.logw, W1, W0, K), warm=1, reps=3)
@@ -133,6 +140,7 @@ def probe(tag, eng, kw, cs, kind, T1, T0):
     say("%s: N = %d  J = %d  G = %d  P = %d" % (tag, N, J, G, P))
     say("    item_se() end to end           %9.3f ms   (workspace %.1f MB)" % (t_e2e, ws_floats * 4 / 1e6))
     say("    vx_grid_info alone             %9.3f ms" % t_info)
+    say("    the table entry alone          %9.3f ms   (one pass; 200 back-to-back calls)" % t_table)
     if kt:
         roof = PEAK_F16_MFMA / 3
         f_ps, f_xp = 2.0 * N * (2 * J * G + 2 * P * G), 2.0 * N * P * (P + 1) / 2
@@ -206,13 +214,99 @@ def dina_shape(tag, N, J, K, seed):
     return ok
 
 
+def asym_shape(tag, N, J, nodes, model, seed):
+    """item_se(prior=) of a 3PL / 4PL engine in one dimension, at the generating values."""
+    from tests import se_map_cases as sm
+    from vipsy_amd.grid import score_grid
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    rng = np.random.RandomState(seed)
+    four = model == "irt_4pl"
+    a = rng.uniform(0.4, 1.0, size=(1, J)).astype(np.float32)
+    b = rng.normal(size=(1, J)).astype(np.float32)
+    c = sc._logit(rng.uniform(0.1, 0.3, size=(1, J))).astype(np.float32)
+    d = sc._logit(rng.uniform(0.85, 0.97, size=(1, J))).astype(np.float32)
+    params = {"a": a, "b": b, "c": c}
+    prior = {"c": (-1.4, 1.0)}
+    if four:
+        params["d"] = d
+        prior["d"] = (2.2, 1.0)
+    t = {k: torch.from_numpy(v).to(dev) for k, v in params.items()}
+    lo, hi = torch.sigmoid(t["c"]), (torch.sigmoid(t["d"]) if four else 1.0)
+    x = torch.randn(N, 1, device=dev, generator=g)
+    y = (torch.rand(N, J, device=dev, generator=g) < lo + (hi - lo) * torch.sigmoid(x @ t["a"] + t["b"])).to(torch.uint8)
+    y[torch.rand(N, J, device=dev, generator=g) < 0.05] = 255
+    del x
+    eng = IrtEngine(y, model=model, D=1, amortized=True, H=64, seed=1)
+    for k, v in t.items():
+        eng.unconstrained(k).copy_(v)
+    be, kw = eng.be, {"nodes": nodes, "prior": prior}
+    t_e2e = timed(lambda: eng.item_se(**kw))
+    call, K, fill_wtable, _ = eng._info_call(None, None, **kw)
+    post = eng._grid_posterior(call)
+    P, G = J * K, call.G
+    f32 = dict(dtype=torch.float32, device=dev)
+    wimg = torch.empty(be.grid_wimage_bytes(P, G), dtype=torch.uint8, device=dev)
+    ws_floats = be.grid_info_workspace(N, P, G)
+    info, grad, ws = torch.empty(P, P, **f32), torch.empty(P, **f32), torch.empty(ws_floats, **f32)
+    t_table = timed(lambda: fill_wtable(wimg), warm=5, reps=200)
+
+    def run():
+        be.grid_info(call.y, None, N, J, G, K, post["img"], wimg, call.logw, post["loglik"], info, grad, ws, ws_floats)
+
+    t_info = timed(run)
+    kt = kernel_times(run)
+    ktab = kernel_times(lambda: fill_wtable(wimg), ("k_grid_wtable_irt_asym", "k_grid_wscale"))
+    say("%s: N = %d  J = %d  G = %d  K = %d  P = %d" % (tag, N, J, G, K, P))
+    say("    item_se(prior=) end to end     %9.3f ms   (workspace %.1f MB)" % (t_e2e, ws_floats * 4 / 1e6))
+    say("    vx_grid_info alone             %9.3f ms" % t_info)
+    say("    the table entry alone          %9.3f ms   (trailer reset, maximum pass, trailer, fill pass; 200 back-to-back calls)" % t_table)
+    if ktab:
+        say("    k_grid_wtable_irt_asym, both passes %6.1f us   k_grid_wscale %.1f us   (device time inside one call; %d x %d cells)"
+            % (ktab["k_grid_wtable_irt_asym"], ktab["k_grid_wscale"], ((G + 31) // 32) * 32, ((P + 32) // 32) * 32))
+    if kt:
+        roof = PEAK_F16_MFMA / 3
+        f_ps, f_xp = 2.0 * N * (2 * J * G + 2 * P * G), 2.0 * N * P * (P + 1) / 2
+        for k, fl in (("k_grid_pscores", f_ps), ("k_grid_xprod", f_xp)):
+            ms = kt[k] / 1e3
+            say("    %-30s %9.3f ms   useful %.1f TFLOP/s = %.1f %% of the fp16-pair roofline" % (k + " alone", ms, fl / ms / 1e9, 100 * fl / (ms * 1e-3) / roof))
+    rng = np.random.RandomState(77)
+    idx = np.sort(rng.choice(N, size=min(4096, N), replace=False))
+    rows = torch.from_numpy(idx).to(dev)
+    sub = eng.item_information(rows=rows, **kw)
+    torch.cuda.synchronize()
+    theta, logw = score_grid(1, nodes, 6.0)
+    cs = {"name": tag, "model": model, "D": 1, "J": J, "Dc": 1.0, "theta": theta, "logw": logw, "params": params,
+          "a_free": np.ones((1, J), bool), "prior": prior, "y": y[rows].cpu().numpy()}
+    want = sm.oracle(cs)
+    e_i, _, e_g = sm.info_errors(sub["info"].cpu().numpy(), sub["gradient"].cpu().numpy(), want["info"], want["gradient"], len(idx))
+    say("    %d sampled persons against float64 (row rule %.0e): info %.2e  gradient %.2e; condition of info + precision %.1f"
+        % (len(idx), ROW_TOL, e_i, e_g, want["condition"]))
+    ok = max(e_i, e_g) <= ROW_TOL
+    say("    within the row rule: %s" % ("yes" if ok else "NO"))
+    del eng, y
+    torch.cuda.empty_cache()
+    return ok
+
+
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else None
+    args = [a for a in sys.argv[1:]]
+    model = None
+    if "--model" in args:
+        i = args.index("--model")
+        model = args[i + 1]
+        del args[i:i + 2]
+        if model not in ("irt_2pl", "irt_3pl", "irt_4pl"):
+            raise SystemExit("--model takes irt_2pl, irt_3pl or irt_4pl")
+    out = args[0] if args else None
     say("se_probe: %s, torch %s, %s" % (torch.cuda.get_device_name(0), torch.__version__, time.strftime("%Y-%m-%d")))
     n = max(4096, int(1000000 * SCALE))
     ok = irt_shape("2PL, 61 nodes", n, 500, 1, 61, (0.4, 1.0), 1)
-    ok = irt_shape("3-D 2PL, 9^3 nodes", n, 40, 3, 9, (0.4, 1.0), 3) and ok
-    ok = dina_shape("DINA, K = 8", n, 30, 8, 2) and ok
+    if model in ("irt_3pl", "irt_4pl"):
+        ok = asym_shape("%s under item priors, 61 nodes" % model[4:].upper(), n, 500, 61, model, 4) and ok
+    elif model is None:
+        ok = irt_shape("3-D 2PL, 9^3 nodes", n, 40, 3, 9, (0.4, 1.0), 3) and ok
+        ok = dina_shape("DINA, K = 8", n, 30, 8, 2) and ok
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:

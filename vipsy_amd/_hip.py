@@ -140,6 +140,7 @@ SIGNATURES = {
     "vx_grid_mstep_irt_map": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 3 + [_P] * 4 + [_P, _I32, _P, _P]),
     "vx_grid_wimage_bytes": (_I64, [_I32, _I32]),
     "vx_grid_wtable_irt": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 2 + [_P, _P]),
+    "vx_grid_wtable_irt_map": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 4 + [_P, _P]),
     "vx_grid_wtable_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32] + [_P] * 3 + [_P, _P]),
     "vx_grid_info_workspace_floats": (_I64, [_I64, _I32, _I32]),
     "vx_grid_info_workspace_min_floats": (_I64, [_I32, _I32]),

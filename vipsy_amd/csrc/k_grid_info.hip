@@ -5,7 +5,9 @@
 //
 // p_i(g) the posterior k_grid_counts.hip forms, u_g = Dc (1, theta_g) for the IRT links and ([eta = 0], -[eta = 1]) for DINA /
 // DINO on the unconstrained g / s scale.  info = sum_i s_i s_i^T, gradient = sum_i s_i.  Dense parameter layout: column
-// c = j K + k, K = D + 1 (k = 0: b, k = 1 + d: a_d) for 2PL, 1 for 1PL, 2 (g_un, s_un) for DINA / DINO; P = J K <= 4096.
+// c = j K + k, K = D + 1 (k = 0: b, k = 1 + d: a_d) for 2PL, 1 for 1PL, 2 (g_un, s_un) for DINA / DINO; 3PL / 4PL add k = D + 1:
+// c_un and k = D + 2: d_un (K = D + 2 / D + 3 <= 6), with W1 = v / P, W0 = v / Q, v = dP / d(unknown) of the penalised M-step's cell
+// (gi_asym_cell) -- the same identity, and the 2PL tables are its case c = 0, d = 1.  P = J K <= 4096.
 // Three chained products on v_mfma_f32_32x32x16_f16, fp16 pairs, fp32 accumulation:
 //
 //   tables    k_grid_wtable_irt / k_grid_wtable_cdm write W1 and W0 as the operand image of product 2, [node tile][k-step][parameter
@@ -14,6 +16,8 @@
 //             its nodes.  P, 1 - P and the clamp are the M-step's: gm_cell (a node where the z clamp is active contributes 0),
 //             gp_cdm_eta / gp_cdm_qpat.  Values times 2^s, s = f16_scale_exp(Dc max(1, |theta|_inf)) (|W| <= that bound, and so is
 //             |s_i|: sum_g p = 1); 2^s and 2^-s sit in the image's 16-byte trailer, where the kernels read them.
+//             k_grid_wtable_irt_asym (3PL / 4PL): the same image and trailer, s from the table's own largest magnitude, found
+//             in a first pass (no closed bound: a 4PL entry grows like 1 / (d - c)); the image carries |W 2^s| < 2^15.
 //   1 + 2     k_grid_pscores: a workgroup takes 64 persons at a time.  Its waves share the node passes of k_grid_post's operand
 //             phase (GP_UNIT_* / GP_PASS / GP_INDICATORS, unchanged: person on the lane, 16 nodes of a tile in the registers),
 //             form p = exp(f - loglik_i) as k_grid_counts does and leave p 2^14 as fp16 pairs in LDS: registers 0..7 and 8..15 of an
@@ -37,7 +41,7 @@
 
 // GI_BT, GI_TILE, GI_MAX_BLOCKS, gi_pt, gi_pairs and gi_pair_index are in grid_plan.h, beside gi_slab_plan
 #define GI_MAXP 4096
-#define GI_MAXK 4
+#define GI_MAXK 6                       // 4PL in three dimensions: b, a_0 .. a_2, c_un, d_un
 #define GI_LDS_NT 16                    // node tiles up to which the LDS holds p of both person tiles of a unit
 
 __host__ __device__ inline int64_t gi_wimage_frag_bytes(int P, int G) { return (int64_t)gp_nt(G) * 2 * gi_pt(P) * 4 * 64 * 16; }
@@ -102,6 +106,82 @@ __global__ __launch_bounds__(256) void k_grid_wtable_irt(int D, int J, int G, fl
         }
         gi_put(wimg, PT, gp, cp, w1, w0);
     }
+}
+
+// 3PL / 4PL: one cell of column k of item j at node gp, unscaled.  The arithmetic of gm_eval<3 | 4> (k_grid_mstep.hip) said again:
+// the asymptotes capped as there, z in its order, v = dP / d(unknown k), W1 = v / Pc, W0 = v / Qc, both 0 where the node is not inside
+template <int MODEL>
+__device__ __forceinline__ void gi_asym_cell(int D, int J, float Dc, const float* __restrict__ theta, const float* __restrict__ a,
+                                             const float* __restrict__ b, const float* __restrict__ c_un,
+                                             const float* __restrict__ d_un, int gp, int j, int k, float& w1, float& w0) {
+    const float c = fminf(sigmoidf_(c_un[j]), 1.0f - VX_EPS32);
+    float dd = 1.f, omd = 0.f;
+    if (MODEL == 4) {
+        dd = fminf(sigmoidf_(d_un[j]), 1.0f - VX_EPS32);
+        omd = fmaxf(sigmoidf_(-d_un[j]), VX_EPS32);
+    }
+    const float dmc = dd - c;
+    float sz = b[j];
+    for (int d = 0; d < D; ++d) sz = fmaf(theta[(int64_t)gp * D + d], a[(int64_t)d * J + j], sz);
+    const float z = Dc * sz;
+    const float e = __expf(-fabsf(z));
+    const float r = fast_rcp(1.0f + e);
+    const float sg = (z >= 0.f) ? r : e * r;                        // sigmoid(z)
+    const float sn = (z >= 0.f) ? e * r : r;                        // sigmoid(-z), no cancellation
+    const float P = c + dmc * sg;
+    const float Q = omd + dmc * sn;
+    const bool inside = (P >= VX_EPS32) && (Q >= VX_EPS32);
+    const float Pc = fminf(fmaxf(P, VX_EPS32), 1.0f - VX_EPS32);
+    const float Qc = fminf(fmaxf(Q, VX_EPS32), 1.0f - VX_EPS32);
+    float v;
+    if (k <= D) v = dmc * sg * sn * (Dc * (k == 0 ? 1.f : theta[(int64_t)gp * D + (k - 1)]));
+    else if (k == D + 1) v = sn * (c * (1.0f - c));
+    else v = sg * (dd * omd);
+    w1 = inside ? v * fast_rcp(Pc) : 0.f;
+    w0 = inside ? v * fast_rcp(Qc) : 0.f;
+}
+
+// IRT with asymptotes (MODEL 3 | 4), K = D + MODEL - 1 columns an item: b, a_0 .. a_{D-1}, c_un, then d_un.  No bound in closed
+// form serves these tables: 3PL entries stay below max(1, Dc max(1, |theta|_inf)), but W0 of c_un and W1 of d_un of a 4PL item grow
+// like 1 / (d - c), and d <= c is admissible.  So the scale comes from the table itself, in two launches of this kernel around
+// k_grid_wscale: FILL = false takes the largest |W1|, |W0| of the launch's cells -- a block's by fmaxf in LDS, the blocks' by an
+// integer maximum on the bit patterns of those non-negative floats in trailer[2] (zeroed before; no float atomics: whatever
+// the order, the same bits) --, k_grid_wscale turns it into the trailer (2^s, 2^-s, 0, 0) with s = f16_scale_exp(that maximum),
+// and FILL = true writes the image at that scale.  The image then carries |W 2^s| < 2^15, and so does S: sum_g p = 1.
+template <int MODEL, bool FILL>
+__global__ __launch_bounds__(256) void k_grid_wtable_irt_asym(int D, int J, int G, float Dc, const float* __restrict__ theta,
+                                                              const float* __restrict__ a, const float* __restrict__ b,
+                                                              const float* __restrict__ c_un, const float* __restrict__ d_un,
+                                                              uint16_t* __restrict__ wimg, float* trailer) {
+    const int K = D + MODEL - 1, P = J * K, PT = gi_pt(P), PP = PT * 32, total = gp_nt(G) * 32 * PP;
+    const float sc = FILL ? trailer[0] : 1.0f;
+    float m = 0.f;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int gp = idx / PP, cp = idx - gp * PP;
+        float w1 = 0.f, w0 = 0.f;
+        if (gp < G && cp < P) {
+            const int j = cp / K, k = cp - j * K;
+            gi_asym_cell<MODEL>(D, J, Dc, theta, a, b, c_un, d_un, gp, j, k, w1, w0);
+        }
+        if (FILL) gi_put(wimg, PT, gp, cp, w1 * sc, w0 * sc);
+        else m = fmaxf(m, fmaxf(fabsf(w1), fabsf(w0)));
+    }
+    if (!FILL) {
+        __shared__ float red[256];
+        red[threadIdx.x] = m;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) atomicMax((unsigned int*)(trailer + 2), __float_as_uint(red[0]));
+    }
+}
+
+// trailer[2] = the largest magnitude of the table (k_grid_wtable_irt_asym<., false>) -> the trailer as gi_scale leaves it
+__global__ void k_grid_wscale(float* __restrict__ trailer) {
+    const int s = f16_scale_exp(trailer[2]);
+    trailer[0] = ldexpf(1.0f, s); trailer[1] = ldexpf(1.0f, -s); trailer[2] = 0.f; trailer[3] = 0.f;
 }
 
 // DINA / DINO: P and 1 - P as k_grid_table_cdm has them; a parameter at the Bernoulli clamp contributes 0

@@ -2511,6 +2511,34 @@ int vx_grid_wtable_irt(const vx_irt_cfg* cfg, const float* theta, int32_t G, con
     });
 }
 
+// The tables at the fit of vx_grid_mstep_irt_map: models 1 and 2 are vx_grid_wtable_irt's launch; 3 and 4 take the scale from the
+// table itself (k_grid_wtable_irt_asym: the maximum, the trailer, the image)
+int vx_grid_wtable_irt_map(const vx_irt_cfg* cfg, const float* theta, int32_t G, const float* a, const float* b, const float* c_un,
+                           const float* d_un, void* wimg, void* hs) {
+    if (!irt_items_ok(cfg, 4, GM_MAXD, a, b, c_un, d_un) || !grid_shape_ok(cfg->J, G, 1) || !theta || !wimg || !aligned16(wimg))
+        return VX_EINVAL;
+    if (cfg->model <= 2) return vx_grid_wtable_irt(cfg, theta, G, a, b, wimg, hs);
+    const int64_t P64 = (int64_t)cfg->J * (cfg->D + cfg->model - 1);
+    if (P64 > GI_MAXP) return VX_EINVAL;
+    const int P = (int)P64;
+    const int blocks = grid_1d((int64_t)gp_nt(G) * 32 * gi_pt(P) * 32, 256);
+    hipStream_t st = (hipStream_t)hs;
+    float* trailer = (float*)((uint8_t*)wimg + gi_wimage_frag_bytes(P, G));
+    if (hipError_t he = hipMemsetAsync(trailer, 0, 16, st)) return (int)he;
+    return with_irt_model(cfg->model, [&](auto m) -> int {
+        constexpr int M = decltype(m)::value < 4 ? 3 : 4;                               // (models 1 and 2 have left above)
+        hipLaunchKernelGGL((k_grid_wtable_irt_asym<M, false>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc,
+                           theta, a, b, c_un, d_un, (uint16_t*)wimg, trailer);
+        VX_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_grid_wscale, dim3(1), dim3(1), 0, st, trailer);
+        VX_CHECK_LAUNCH();
+        hipLaunchKernelGGL((k_grid_wtable_irt_asym<M, true>), dim3(blocks), dim3(256), 0, st, (int)cfg->D, (int)cfg->J, (int)G, cfg->Dc,
+                           theta, a, b, c_un, d_un, (uint16_t*)wimg, trailer);
+        VX_CHECK_LAUNCH();
+        return VX_OK;
+    });
+}
+
 int vx_grid_wtable_cdm(const vx_hodina_cfg* cfg, int32_t dino, const float* q, const float* g_un, const float* s_un, void* wimg,
                        void* hs) {
     if (!cdm_items_ok(cfg, dino, q, g_un, s_un) || !wimg || !aligned16(wimg)) return VX_EINVAL;

@@ -310,6 +310,11 @@ class HipBackend(object):
                                        _hip.stream_ptr())
         _hip.check(rc, "vx_grid_wtable_irt")
 
+    def grid_wtable_irt_map(self, cfg, theta, G, a, b, c_un, d_un, wimg):
+        rc = self.L.vx_grid_wtable_irt_map(ctypes.byref(cfg), _hip.ptr(theta), G, _hip.ptr(a), _hip.ptr(b), _hip.ptr(c_un),
+                                           _hip.ptr(d_un), _hip.ptr(wimg), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_wtable_irt_map")
+
     def grid_wtable_cdm(self, cfg, dino, q, g, s_, wimg):
         rc = self.L.vx_grid_wtable_cdm(ctypes.byref(cfg), int(dino), _hip.ptr(q), _hip.ptr(g), _hip.ptr(s_), _hip.ptr(wimg),
                                        _hip.stream_ptr())
@@ -1871,22 +1876,53 @@ class IrtEngine(GridMixin, _EngineBase):
         leaves = {k: v for k, v in (("a", a), ("b", b), ("c", c), ("d", d)) if v is not None}
         return self._em_loop(call, mstep, leaves, max_iter, tol, progress, lprior=lprior)
 
-    def _info_call(self, y_u8, rows, nodes=61, span=6.0):
+    def _info_call(self, y_u8, rows, nodes=61, span=6.0, prior=None):
         """What GridMixin.item_information needs of this class: the GridCall, K (columns an item: b, then a_0 .. a_{D-1}; 1PL: b),
-        the filler of the derivative tables and the free mask over the dense layout."""
-        if self.model not in ("irt_1pl", "irt_2pl"):
+        the filler of the derivative tables and the free mask over the dense layout.  With `prior` (fit_em's, checked here by
+        grid.em_prior before anything is computed) all four models are served: c_un (3PL up) and d_un (4PL) follow the loadings,
+        K = D + 2 / D + 3, both always free, and the filler is vx_grid_wtable_irt_map on compact copies of the leaves."""
+        if prior is None and self.model not in ("irt_1pl", "irt_2pl"):
             raise NotImplementedError("item_information / item_se for %s: the derivative tables are those of the logistic link of "
                                       "fit_em's M-step, which a guessing or slipping asymptote does not have; only irt_1pl and "
-                                      "irt_2pl have them" % self.model)
+                                      "irt_2pl have them without item priors -- pass prior= (fit_em's) for the matrix at the "
+                                      "Bayes-modal fit" % self.model)
+        if prior is not None and self.D_model <= SCORE_MAX_DIMS:
+            em_prior(prior, self.model, self.D_model, self.J_items)          # (beyond three dimensions _grid_call refuses)
         call = self._grid_call(y_u8, rows, nodes, span)
         two = self.model != "irt_1pl"
+        extra = 0 if prior is None else {"irt_3pl": 1, "irt_4pl": 2}.get(self.model, 0)
+        K = (self.D_model + 1 if two else 1) + extra
         a = self.unconstrained("a").contiguous() if two else None
         b = self.unconstrained("b").reshape(-1).contiguous()
-        free = torch.ones(self.J_items, self.D_model + 1 if two else 1, dtype=torch.bool, device=self.dev)
+        free = torch.ones(self.J_items, K, dtype=torch.bool, device=self.dev)
         if two:
-            free[:, 1:] = (self.unconstrained("a", self.free) != 0).t()
-        return call, (self.D_model + 1 if two else 1), lambda wimg: self.be.grid_wtable_irt(call.cfg, call.theta, call.G, a, b, wimg), \
-            free.reshape(-1)
+            free[:, 1:1 + self.D_model] = (self.unconstrained("a", self.free) != 0).t()
+        if prior is None:
+            return call, K, lambda wimg: self.be.grid_wtable_irt(call.cfg, call.theta, call.G, a, b, wimg), free.reshape(-1)
+        c = self.unconstrained("c").reshape(-1).contiguous() if extra >= 1 else None
+        d = self.unconstrained("d").reshape(-1).contiguous() if extra == 2 else None
+        return call, K, lambda wimg: self.be.grid_wtable_irt_map(call.cfg, call.theta, call.G, a, b, c, d, wimg), free.reshape(-1)
+
+    def _info_prior(self, prior, free):
+        """The prior's share of item_information(prior=) over the dense layout of _info_call, float64 numpy [P]: the precisions
+        1 / sd^2 as grid.em_prior gives them and the gradient of the log prior, -precision (p - mean), at the leaves as they
+        stand; both zero where the unknown is not free (free: bool [P]) or has no prior."""
+        J, D = self.J_items, self.D_model
+        pr = em_prior(prior, self.model, D, J).astype(np.float64)
+        rows, leaves = [0], [self.unconstrained("b").reshape(1, J)]
+        if self.model != "irt_1pl":
+            rows += list(range(1, 1 + D))
+            leaves.append(self.unconstrained("a").reshape(D, J))
+        if self.model in ("irt_3pl", "irt_4pl"):
+            rows.append(4)
+            leaves.append(self.unconstrained("c").reshape(1, J))
+        if self.model == "irt_4pl":
+            rows.append(5)
+            leaves.append(self.unconstrained("d").reshape(1, J))
+        p = torch.cat(leaves, 0).detach().cpu().numpy().astype(np.float64)      # [K][J]
+        prec = np.where(np.asarray(free, bool).reshape(J, len(rows)), pr[1, rows].T, 0.0)
+        grad = -prec * (p.T - pr[0, rows].T)
+        return prec.reshape(-1), grad.reshape(-1)
 
     def _pairs_call(self, y_u8, rows, nodes=61, span=6.0):
         """What GridMixin.residual_sums needs of this class: the GridCall (all four models; x_feature > 3 is refused with the
@@ -1986,11 +2022,20 @@ class IrtEngine(GridMixin, _EngineBase):
         return out
 
     def _se_leaves(self, se):
-        """Dense [P] -> the leaves' shapes: b (1, J) and, for 2PL, a (D, J)."""
+        """Dense [P] -> the leaves' shapes: b (1, J) and, for 2PL up, a (D, J).  The layout of item_se(prior=) for irt_3pl /
+        irt_4pl (K = D + 2 / D + 3) also has c_un (and d_un) (1, J) and, by the delta method, c (and d) on the probability scale:
+        se x (1 - x), x the asymptote as the tables cap it."""
         se = se.reshape(self.J_items, -1)
+        D = self.D_model
         out = {"b": se[:, 0].reshape(1, -1).copy()}
         if self.model != "irt_1pl":
-            out["a"] = se[:, 1:].T.copy()
+            out["a"] = se[:, 1:1 + D].T.copy()
+        eps = float(np.finfo(np.float32).eps)
+        for n, k in enumerate(("c", "d")[:max(se.shape[1] - (D + 1), 0)]):
+            un = self.unconstrained(k).detach().cpu().numpy().astype(np.float64).reshape(1, -1)
+            x, om = np.minimum(1.0 / (1.0 + np.exp(-un)), 1.0 - eps), np.maximum(1.0 / (1.0 + np.exp(un)), eps)
+            out[k + "_un"] = se[:, D + 1 + n].reshape(1, -1).copy()
+            out[k] = out[k + "_un"] * x * om
         return out
 
     # -- one ELBO-gradient step ------------------------------------------------------------------
@@ -2426,8 +2471,12 @@ class CcdmEngine(GridMixin, _EngineBase):
         return self._em_loop(call, lambda n1, n0: self.be.grid_mstep_cdm(call.cfg, dino, self.q, n1, n0, g, s_), {"g": g, "s": s_},
                              max_iter, tol, progress)
 
-    def _info_call(self, y_u8, rows):
-        """What GridMixin.item_information needs of this class: two columns an item, g_un and s_un, both free."""
+    def _info_call(self, y_u8, rows, prior=None):
+        """What GridMixin.item_information needs of this class: two columns an item, g_un and s_un, both free.  `prior`
+        (IrtEngine's item priors) is refused as fit_em refuses it."""
+        if prior is not None:
+            raise ValueError("item_information / item_se(prior=) on %s: the priors are those of the IRT item parameters "
+                             "(IrtEngine); the fit of DINA / DINO takes none" % type(self).__name__)
         call = self._grid_call(y_u8, rows)
         g, s_ = self.view("g"), self.view("s")
         return call, 2, lambda wimg: self.be.grid_wtable_cdm(call.cfg, self.cdm == "dino", self.q, g, s_, wimg), \

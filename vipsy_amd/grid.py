@@ -382,13 +382,17 @@ def group_fit_top(rmsd, top=20):
     return {"group": (sel // rmsd.shape[1]).astype(np.int64), "item": (sel % rmsd.shape[1]).astype(np.int64), "value": flat[sel]}
 
 
-def item_se_host(info, gradient, free, names=None):
+def item_se_host(info, gradient, free, names=None, precision=None):
     """The host layer of item_se(): standard errors from an information matrix, in float64 numpy.  info [P][P], gradient [P],
     free bool [P].  Kept are the free columns whose diagonal is not exactly 0 (a column of exact zeros belongs to an item nobody
     answered or to a class no pattern reaches); the kept block is inverted through its Cholesky factor -- no pseudo-inverse: a
     block that is not positive definite raises ValueError naming the parameter of the smallest pivot (names: a function of the
     dense column, by default the column number).  Returns `se` [P] (NaN where fixed or dropped), `cov` [kept][kept], `kept`,
-    `gradient_max` = max |gradient| over the kept columns and `condition`, the 2-norm condition number of the kept block."""
+    `gradient_max` = max |gradient| over the kept columns and `condition`, the 2-norm condition number of the kept block.
+    precision [P] (item_se(prior=): the precisions of the normal priors, >= 0): the block that is inverted is then
+    info[kept, kept] + diag(precision[kept]) -- the likelihood's information plus the prior's curvature -- and `gradient` is taken
+    as handed over (the caller adds the prior's share).  `kept` is still decided on the diagonal of `info` alone: about an item
+    nobody answered the data say nothing, and it stays NaN under any prior.  precision None: every bit as without the argument."""
     info = np.asarray(info, np.float64)
     gradient = np.asarray(gradient, np.float64).reshape(-1)
     free = np.asarray(free, bool).reshape(-1)
@@ -398,6 +402,11 @@ def item_se_host(info, gradient, free, names=None):
     kept = np.flatnonzero(free & (np.diag(info) != 0))
     A = info[np.ix_(kept, kept)]
     A = 0.5 * (A + A.T)
+    if precision is not None:
+        precision = np.asarray(precision, np.float64).reshape(-1)
+        if precision.shape != (P,) or not (np.isfinite(precision).all() and (precision >= 0).all()):
+            raise ValueError("precision must be [P], finite and >= 0")
+        A = A + np.diag(precision[kept])
     se = np.full(P, np.nan)
     if kept.size == 0:
         return {"se": se, "cov": np.zeros((0, 0)), "kept": kept, "gradient_max": 0.0, "condition": float("nan")}
@@ -942,7 +951,7 @@ class GridMixin(object):
             out["logpost"] = hist
         return out
 
-    def item_information(self, y_u8=None, rows=None, **kw):
+    def item_information(self, y_u8=None, rows=None, prior=None, **kw):
         """The cross-product (BHHH, empirical) information of the item parameters over the scored rows, AT THE PARAMETERS
         AS THEY STAND: with s_i the marginal score of person i (Fisher's identity over the grid posterior of score()), `info` =
         sum_i s_i s_i^T, float32 [P][P] on the device, symmetric bit for bit, and `gradient` = sum_i s_i [P], the gradient of
@@ -950,16 +959,29 @@ class GridMixin(object):
         K = x_feature + 1 (k = 0: b, k = 1 + d: a_d; 1PL: K = 1), CcdmEngine: K = 2 (g_un, s_un); P = J K <= 4096.  Also `n`
         (the persons), `free` bool [P] (the engine's free mask over a; b, g and s are always free) and `index`, the numpy arrays
         `item` and `k` [P].  Its inverse is a covariance only at the marginal maximum, i.e. after fit_em() has converged;
-        `gradient` says how far from it the parameters are.  Inputs, grid and limits as score(); 1PL / 2PL only; one rank only.
-        Works in buffers of its own.  Deterministic: the same call gives the same bits."""
+        `gradient` says how far from it the parameters are.  Inputs, grid and limits as score(); one rank only.
+        Works in buffers of its own.  Deterministic: the same call gives the same bits.
+        prior (IrtEngine; fit_em's argument, checked by grid.em_prior with its rules and ValueErrors): the matrix at the
+        Bayes-modal fit of fit_em(prior=), which opens irt_3pl and irt_4pl -- their columns go on with k = x_feature + 1: c_un and,
+        for 4PL, k = x_feature + 2: d_un (K = x_feature + 2 / + 3; 4PL at three dimensions allows 682 items), the tables of
+        vx_grid_wtable_irt_map.  `info` and `gradient` remain the LIKELIHOOD's (for 1PL / 2PL with the bits of the call without
+        `prior`); the prior's share comes beside them as float64 numpy [P] over the dense layout: `prior_precision` (1 / sd^2)
+        and `prior_gradient` = -precision (p - mean), both zero where the unknown is not free or has no prior.  info +
+        diag(prior_precision) approximates the negative Hessian of the log posterior, and gradient + prior_gradient is the
+        gradient of the log posterior: what vanishes where fit_em(prior=) converged.  Without `prior` nothing changes: 1PL / 2PL
+        and CcdmEngine as before, irt_3pl / irt_4pl refuse (the likelihood alone does not pin an asymptote: there is no fit to
+        stand at); CcdmEngine refuses a prior with ValueError, as its fit_em does."""
         self._one_rank_only("item_information / item_se over a process group: the matrix is the sum over the local shard's "
                             "persons and the cross-rank sum is not built")
-        call, K, fill_wtable, free = self._info_call(y_u8, rows, **kw)
+        if prior is None:
+            call, K, fill_wtable, free = self._info_call(y_u8, rows, **kw)
+        else:
+            call, K, fill_wtable, free = self._info_call(y_u8, rows, prior=prior, **kw)
         be, J, G, n = self.be, call.J, call.G, call.n
         P = J * K
         if P > INFO_MAX_PARAMS:
-            raise NotImplementedError("item_information takes at most %d item parameters (this model has %d x %d)"
-                                      % (INFO_MAX_PARAMS, J, K))
+            raise NotImplementedError("item_information takes at most %d item parameters (this model has %d x %d; irt_4pl at three "
+                                      "dimensions, 6 an item, allows 682 items)" % (INFO_MAX_PARAMS, J, K))
         post = self._grid_posterior(call)
         f32 = dict(dtype=torch.float32, device=self.dev)
         wimg = torch.empty(be.grid_wimage_bytes(P, G), dtype=torch.uint8, device=self.dev)
@@ -968,21 +990,34 @@ class GridMixin(object):
         ws_floats = be.grid_info_workspace(n, P, G)
         ws = torch.empty(ws_floats, **f32)
         be.grid_info(call.y, call.rows, n, J, G, K, post["img"], wimg, call.logw, post["loglik"], info, gradient, ws, ws_floats)
-        return {"info": info, "gradient": gradient, "n": n, "free": free,
-                "index": {"item": np.repeat(np.arange(J), K), "k": np.tile(np.arange(K), J)}}
+        out = {"info": info, "gradient": gradient, "n": n, "free": free,
+               "index": {"item": np.repeat(np.arange(J), K), "k": np.tile(np.arange(K), J)}}
+        if prior is not None:
+            out["prior_precision"], out["prior_gradient"] = self._info_prior(prior, free.cpu().numpy())
+        return out
 
-    def item_se(self, y_u8=None, rows=None, **kw):
+    def item_se(self, y_u8=None, rows=None, prior=None, **kw):
         """Standard errors of the item parameters from item_information(), as float64 numpy arrays shaped like the leaves
         (IrtEngine: `b` and, for 2PL, `a`; CcdmEngine: `g_un`, `s_un` and, by the delta method, `g`, `s` on the probability
         scale), NaN for a parameter that is fixed (a_free = 0) or was dropped because its column of the matrix is exactly zero
         (an item nobody answered; the s of a DINO single-attribute item).  Also `cov` (float64, kept x kept), `kept` (the dense
         columns of its rows), `gradient_max` and `condition` (item_se_host).  The matrix is the cross-product information AT THE
         PARAMETERS AS THEY STAND: these are standard errors only at the marginal maximum, after fit_em() has converged --
-        `gradient_max` shows how far from it the parameters are.  A kept block that is not positive definite raises ValueError."""
-        inf = self.item_information(y_u8, rows, **kw)
+        `gradient_max` shows how far from it the parameters are.  A kept block that is not positive definite raises ValueError.
+        prior (item_information's; IrtEngine, all four models): the matrix that is inverted is the cross-product information of
+        the likelihood PLUS the prior's precision on its diagonal, at the parameters as they stand -- an approximation to the
+        posterior covariance at the posterior mode, where fit_em(prior=) ends.  `gradient_max` is then the largest entry of
+        the gradient of the log POSTERIOR (gradient + prior_gradient), the quantity that vanishes there.  irt_3pl / irt_4pl
+        also return `c_un` (and `d_un`) shaped like the leaves and, by the delta method, `c` (`d`) on the probability scale:
+        se x (1 - x), x the asymptote as the tables cap it.  An item nobody answered stays NaN under any prior."""
+        inf = self.item_information(y_u8, rows, prior=prior, **kw)
         item, k = inf["index"]["item"], inf["index"]["k"]
-        out = item_se_host(inf["info"].cpu().numpy(), inf["gradient"].cpu().numpy(), inf["free"].cpu().numpy(),
-                           names=lambda c: "item %d, parameter %d of its %d" % (item[c], k[c], int(k.max()) + 1))
+        gradient = inf["gradient"].cpu().numpy()
+        if prior is not None:
+            gradient = gradient.astype(np.float64) + inf["prior_gradient"]
+        out = item_se_host(inf["info"].cpu().numpy(), gradient, inf["free"].cpu().numpy(),
+                           names=lambda c: "item %d, parameter %d of its %d" % (item[c], k[c], int(k.max()) + 1),
+                           precision=inf.get("prior_precision"))
         out.update(self._se_leaves(out.pop("se")))
         return out
 

@@ -323,26 +323,39 @@ class BasePsy(object):
             grid_kw["prior"] = prior
         return self.engine.fit_em(max_iter=max_iter, tol=tol, newton=newton, progress=progress, **grid_kw)
 
-    def item_information(self, data=None, **grid_kw):
+    def item_information(self, data=None, prior=None, **grid_kw):
         """The cross-product (BHHH) information matrix of the item parameters over the persons in `data` (None: the training
         data) AT THE PARAMETERS AS THEY STAND, and the gradient of the marginal log-likelihood: device tensors `info` [P][P] and
         `gradient` [P] over the dense layout, with `n`, `free` and `index` (IrtEngine / CcdmEngine.item_information).  The
         inverse of the matrix is a covariance only at the marginal maximum, that is after fit_em() has converged.  VIRT / VaeIRT
-        with irt_1pl / irt_2pl and x_feature <= 3, VCCDM; the other classes and models refuse.  One rank only."""
+        with irt_1pl / irt_2pl and x_feature <= 3, VCCDM; the other classes and models refuse.  One rank only.
+        prior (fit_em's item priors, e.g. {"c": (-1.4, 1.0), "d": (2.2, 1.0)}; VIRT / VaeIRT): the matrix at the Bayes-modal
+        fit of fit_em(prior=), which opens irt_3pl and irt_4pl (columns c_un, d_un after the loadings).  `info` and `gradient`
+        stay the likelihood's; `prior_precision` and `prior_gradient` (float64 numpy [P]) carry the prior's curvature and the
+        gradient of the log prior.  irt_3pl needs a finite sd on "c", irt_4pl on "c" and "d"; VCCDM refuses a prior."""
         if self.world > 1:
             raise NotImplementedError("item_information with a group of %d ranks: the matrix is the sum over the local shard's "
                                       "persons; the cross-rank sum is not built" % self.world)
+        if prior is not None:
+            grid_kw["prior"] = prior
         return self.engine.item_information(self._score_data(data), **grid_kw)
 
-    def item_se(self, data=None, **grid_kw):
+    def item_se(self, data=None, prior=None, **grid_kw):
         """Standard errors of the item parameters, ready to print: numpy arrays shaped like the leaves (`a`, `b`; VCCDM: `g_un`,
         `s_un` and `g`, `s` on the probability scale), NaN where a parameter is fixed or has no information, with `cov`, `kept`,
         `gradient_max` and `condition` (GridMixin.item_se).  They come from the inverse of the cross-product information AT THE
         PARAMETERS AS THEY STAND: standard errors only at the marginal maximum, that is after fit_em() has converged;
-        `gradient_max` shows how far from it the parameters are.  Models and refusals as item_information().  One rank only."""
+        `gradient_max` shows how far from it the parameters are.  Models and refusals as item_information().  One rank only.
+        prior (fit_em's; all four IRT models): the standard errors at the Bayes-modal fit, the ones a calibration report of
+        irt_3pl / irt_4pl items prints.  The matrix that is inverted is the cross-product information of the likelihood plus
+        the prior's precision, at the parameters as they stand: an approximation to the posterior covariance at the posterior
+        mode.  `gradient_max` is then the largest entry of the gradient of the log posterior, which vanishes where
+        fit_em(prior=) converged.  irt_3pl / irt_4pl also give `c_un` (`d_un`) and, by the delta method, `c` (`d`)."""
         if self.world > 1:
             raise NotImplementedError("item_se with a group of %d ranks: the information matrix is the sum over the local "
                                       "shard's persons; the cross-rank sum is not built" % self.world)
+        if prior is not None:
+            grid_kw["prior"] = prior
         return self.engine.item_se(self._score_data(data), **grid_kw)
 
     def residual_sums(self, data=None, **kw):
