@@ -725,6 +725,23 @@ int vx_sumscore_observed(const uint8_t* y /*[n_local][J]*/, const int64_t* rows 
                          const int32_t* items /*[Js] or NULL*/, int32_t Js, const int32_t* score /*[nb]*/,
                          int32_t* o1 /*[Js][Js + 1]*/, void* hip_stream);
 
+/* ---- Pairwise 2 x 2 tables (k_pair_tables.hip): the observed side of Chen & Thissen's LD X2.  With u_ij = [y_ij == 1], z_ij =
+ * [y_ij == 0] (every byte >= 2 is not observed, 254 and 255 among them) over the persons rows[i] (rows NULL: i), i < nb, and I_jk
+ * the persons with both cells observed: n_ab[j][k] = |{i in I_jk : y_ij = a, y_ik = b}|, that is n11 = u^T u, n10 = u^T z, n01 =
+ * z^T u, n00 = z^T z, four full int32 [J][J], zeroed by the entry.  n11 and n00 are symmetric, n10[j][k] = n01[k][j]; on the
+ * diagonal n10 = n01 = 0 and n11[j][j], n00[j][j] are the item's counts of 1s and 0s.  The products run on the 32x32x32 int8 MFMA
+ * with int32 accumulators straight from the person-major y (transposed on chip: there is no fragment workspace), and the person
+ * chunks' sums meet in the tables by integer atomics: exact up to 2^31 - 1 persons, the same bits in any order and on every call.
+ * vx_pair_tables_workspace_ints: the int32 the call wants as workspace -- 0 as built (workspace may then be NULL) -- or -1.
+ * vx_pair_tables_chunks: the person chunks a pair of item groups is cut into for (nb, J): the launch plan, for tests and probes.
+ * Limits: 1 <= J <= 1024, 1 <= nb <= 2^31 - 1 (the queries: -1 beyond), y and the tables non-null, ws_ints at least the query's
+ * answer; VX_EINVAL beyond, before the HIP runtime is touched. */
+int64_t vx_pair_tables_workspace_ints(int64_t nb, int32_t J);
+int64_t vx_pair_tables_chunks(int64_t nb, int32_t J);
+int vx_pair_tables(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[nb] or NULL*/, int64_t nb, int32_t J,
+                   int32_t* n11 /*[J][J]*/, int32_t* n10 /*[J][J]*/, int32_t* n01 /*[J][J]*/, int32_t* n00 /*[J][J]*/,
+                   int32_t* workspace /*or NULL*/, int64_t ws_ints, void* hip_stream);
+
 /* ---- slab reduction: out[i] = alpha * sum_s slabs[s][i]  (fixed order -> deterministic) */
 int vx_reduce_slabs(const float* slabs, int64_t n_slabs, int64_t len, float alpha, float* out,
                     void* hip_stream);

@@ -157,6 +157,9 @@ SIGNATURES = {
     "vx_sumscore_model": (ctypes.c_int, [_P, _P, _P, _I32, _I32] + [_P] * 3 + [_P, _I64, _P]),
     "vx_sumscore_persons": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P]),
     "vx_sumscore_observed": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _I32, _P, _P, _P]),
+    "vx_pair_tables_workspace_ints": (_I64, [_I64, _I32]),
+    "vx_pair_tables_chunks": (_I64, [_I64, _I32]),
+    "vx_pair_tables": (ctypes.c_int, [_P, _P, _I64, _I32] + [_P] * 4 + [_P, _I64, _P]),
     "vx_reduce_slabs": (ctypes.c_int, [_P, _I64, _I64, _F, _P, _P]),
     "vx_sum_workspace_floats": (_I64, []),
     "vx_sum": (ctypes.c_int, [_P, _I64, _F, _P, _P, _P, _P]),

@@ -204,3 +204,24 @@ inline SsPlan ss_plan(int Js, int G) {
 }
 // [e1 slabs: n_chunks x Js (Js + 1) | e0 slabs: the same]
 inline int64_t ss_ws_floats(int Js, int G) { return 2 * (int64_t)ss_plan(Js, G).n_chunks * Js * (Js + 1); }
+
+// ---- PtPlan: vx_pair_tables (k_pair_tables.hip) --------------------------------------------------------------------------
+#define PT_GROUP 128                    // items of a panel: four tiles of 32, tile f of group g = the items 128 g + 4 i + f
+#define PT_STAGE 128                    // persons staged between two barriers: four k-steps of 32
+#define PT_MAXJ 1024
+#define PT_TARGET_BLOCKS 256            // workgroups of a launch at the most: one of 512 threads a CU on 256 CUs, one round
+
+// workgroup = (pair ga <= gb of item groups, chunk of stages); the chunks' integer sums meet in the tables by atomic adds, so
+// the plan decides the launch only, never a bit of the result
+struct PtPlan { int groups; int64_t n_bp, n_stages, stages_per_chunk, n_chunks; };
+inline PtPlan pt_plan(int64_t nb, int J) {
+    PtPlan p;
+    p.groups = (J + PT_GROUP - 1) / PT_GROUP;
+    p.n_bp = (int64_t)p.groups * (p.groups + 1) / 2;
+    p.n_stages = (nb + PT_STAGE - 1) / PT_STAGE;
+    int64_t chunks = PT_TARGET_BLOCKS / p.n_bp > 1 ? PT_TARGET_BLOCKS / p.n_bp : 1;
+    if (chunks > p.n_stages) chunks = p.n_stages;
+    p.stages_per_chunk = (p.n_stages + chunks - 1) / chunks;
+    p.n_chunks = (p.n_stages + p.stages_per_chunk - 1) / p.stages_per_chunk;
+    return p;
+}

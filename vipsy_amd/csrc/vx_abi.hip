@@ -41,6 +41,7 @@
 #include "k_grid_cond.hip"
 #include "k_grid_counts_cond.hip"
 #include "k_sumscore.hip"
+#include "k_pair_tables.hip"
 
 #include <unordered_map>
 #include <mutex>
@@ -2778,6 +2779,44 @@ int vx_sumscore_observed(const uint8_t* y, const int64_t* rows, int64_t nb, int3
     hipLaunchKernelGGL(k_sumscore_observed, dim3((unsigned)blocks), dim3(SS_OBS_THREADS), 0, st, y, rows, nb, (int)J, items, (int)Js,
                        score, o1, per_block);
     VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+// Pairwise 2 x 2 tables (k_pair_tables.hip): u^T u, u^T z, z^T u, z^T z over persons on the int8 MFMA, no workspace
+static bool pair_tables_shape_ok(int64_t nb, int32_t J) { return J >= 1 && J <= PT_MAXJ && nb >= 1 && nb <= (int64_t)INT32_MAX; }
+
+int64_t vx_pair_tables_workspace_ints(int64_t nb, int32_t J) {
+    if (!pair_tables_shape_ok(nb, J)) return VX_EINVAL;
+    return 0;
+}
+
+int64_t vx_pair_tables_chunks(int64_t nb, int32_t J) {
+    if (!pair_tables_shape_ok(nb, J)) return VX_EINVAL;
+    return pt_plan(nb, (int)J).n_chunks;
+}
+
+int vx_pair_tables(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t J, int32_t* n11, int32_t* n10, int32_t* n01, int32_t* n00,
+                   int32_t* workspace, int64_t ws_ints, void* hs) {
+    if (!pair_tables_shape_ok(nb, J) || !y || !n11 || !n10 || !n01 || !n00 || ws_ints < 0) return VX_EINVAL;
+    (void)workspace;
+    hipStream_t st = (hipStream_t)hs;
+    const size_t bytes = sizeof(int32_t) * (size_t)J * (size_t)J;
+    for (int32_t* t : {n11, n10, n01, n00})
+        if (hipMemsetAsync(t, 0, bytes, st) != hipSuccess) return VX_EINVAL;
+    const PtPlan p = pt_plan(nb, (int)J);
+    const dim3 grid((unsigned)(p.n_bp * p.n_chunks));
+    // a dword a lane where the four items of a dword lie in one row and y is aligned, bytes where not
+    if ((J & 3) == 0 && ((uintptr_t)y & 3) == 0)
+        hipLaunchKernelGGL(k_pair_tables<true>, grid, dim3(PT_THREADS), 0, st, y, rows, nb, (int)J, p.groups, p.n_stages,
+                           p.stages_per_chunk, n11, n10, n01, n00);
+    else
+        hipLaunchKernelGGL(k_pair_tables<false>, grid, dim3(PT_THREADS), 0, st, y, rows, nb, (int)J, p.groups, p.n_stages,
+                           p.stages_per_chunk, n11, n10, n01, n00);
+    VX_CHECK_LAUNCH();
+    if (p.groups > 1) {
+        hipLaunchKernelGGL(k_pair_tables_mirror, dim3(grid_1d((int64_t)J * J, 256)), dim3(256), 0, st, (int)J, n11, n10, n01, n00);
+        VX_CHECK_LAUNCH();
+    }
     return VX_OK;
 }
 

@@ -390,6 +390,17 @@ class HipBackend(object):
                                          _hip.stream_ptr())
         _hip.check(rc, "vx_sumscore_observed")
 
+    def pair_tables_workspace(self, nb, J):
+        return self._size("vx_pair_tables_workspace_ints", nb, J)
+
+    def pair_tables_chunks(self, nb, J):
+        return self._size("vx_pair_tables_chunks", nb, J)
+
+    def pair_tables(self, y, rows, nb, J, n11, n10, n01, n00, ws, ws_ints):
+        rc = self.L.vx_pair_tables(_hip.ptr(y), _hip.ptr(rows), nb, J, _hip.ptr(n11), _hip.ptr(n10), _hip.ptr(n01), _hip.ptr(n00),
+                                   _hip.ptr(ws), int(ws_ints), _hip.stream_ptr())
+        _hip.check(rc, "vx_pair_tables")
+
     def cdm_sf_workspace(self, cfg, nb):
         return self._size("vx_cdm_sf_workspace_floats", ctypes.byref(cfg), nb)
 
@@ -722,6 +733,7 @@ class _EngineBase(object):
     score = expected_counts = plausible_values = item_fit = marginal_loglik = fit_em = item_information = item_se = _no_grid
     fit_population = _no_grid
     residual_sums = local_dependence = _no_grid
+    pair_tables = ld_x2 = _no_grid
     fit_sums = person_fit = item_msq = _no_grid
     group_counts = dif = _no_grid
     sumscore_tables = sx2 = score_table = _no_grid

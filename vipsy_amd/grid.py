@@ -471,6 +471,90 @@ def pair_q3_summary(q3, top=20):
             "item_k": kk[order].astype(np.int64), "value": val[order]}
 
 
+PAIR_TABLES = ("n11", "n10", "n01", "n00")                       # the tables of vx_pair_tables, in its argument order
+
+
+def _phi_2x2(t11, t10, t01, t00):
+    """phi of a 2 x 2 table, (t11 t00 - t10 t01) / sqrt(the product of the two row and the two column margins); NaN where a
+    margin is not positive."""
+    den = ((t11 + t10) * (t11 + t01)) * ((t01 + t00) * (t10 + t00))         # (an order a transposition leaves as it is)
+    ok = den > 0
+    return np.where(ok, (t11 * t00 - t10 * t01) / np.sqrt(np.where(ok, den, 1.0)), np.nan)
+
+
+def pair_x2_host(n11, n10, n01, n00, p1, p0, logw, min_pairs=8, min_expected=1.0):
+    """The host layer of ld_x2(): Chen & Thissen's (1997) LD X2 and G2 of every item pair, in float64 numpy, from the observed
+    2 x 2 tables n_ab [J][J] (vx_pair_tables: the persons who answered both items, a to the row item and b to the column item)
+    and the model's p1, p0 [J][G] = P(y_j = 1 | node g), P(y_j = 0 | node g) with the log-weights logw [G] of the nodes.
+    Expected: w = softmax(logw), e_ab[j][k] = sum_g w_g p_a[j][g] p_b[k][g], the four divided by their sum (p0 is given, not
+    1 - p1), E_ab = N_jk e_ab with N_jk = the sum of the four observed cells.  e10 is computed and e01 is its transpose; e11 and
+    e00 are made symmetric, so every statistic is symmetric bit for bit.
+    `x2` = sum_ab (O - E)^2 / E, `g2` = 2 sum_ab O ln(O / E) (0 ln 0 = 0), `z` = (x2 - 1) / sqrt 2, `p` = chi2_sf(x2, 1) = erfc(sqrt(x2 / 2)): NaN
+    where j = k, where N_jk < min_pairs and where any E_ab < min_expected.  `phi_obs`, `phi_exp` = phi of the observed and of the
+    expected table (NaN where a margin is 0), `sign` = sign(phi_obs - phi_exp): +1 the pair agrees more than the model says, -1
+    less; 0 where either phi is undefined and wherever x2 is NaN.  `n_pairs` = N int64 [J][J], `expected` = E [2][2][J][J],
+    indexed [a][b]."""
+    O = {ab: np.asarray(t, np.float64) for ab, t in (((1, 1), n11), ((1, 0), n10), ((0, 1), n01), ((0, 0), n00))}
+    p1, p0 = np.asarray(p1, np.float64), np.asarray(p0, np.float64)
+    J = O[1, 1].shape[0]
+    if O[1, 1].ndim != 2 or any(t.shape != (J, J) for t in O.values()):
+        raise ValueError("n11, n10, n01 and n00 must be [J][J]")
+    if p1.ndim != 2 or p1.shape[0] != J or p0.shape != p1.shape:
+        raise ValueError("p1 and p0 must be [J][G]")
+    lw = np.asarray(logw, np.float64).reshape(-1)
+    if lw.shape[0] != p1.shape[1]:
+        raise ValueError("logw must be [G]")
+    for name, v in (("min_pairs", min_pairs), ("min_expected", min_expected)):
+        if isinstance(v, bool) or not (isinstance(v, (int, float, np.floating, np.integer)) and np.isfinite(v) and v > 0):
+            raise ValueError("%s must be a positive finite number" % name)
+    w = np.exp(lw - lw.max())
+    w /= w.sum()
+    e11, e00, e10 = (p1 * w) @ p1.T, (p0 * w) @ p0.T, (p1 * w) @ p0.T
+    e = {(1, 1): 0.5 * (e11 + e11.T), (0, 0): 0.5 * (e00 + e00.T), (1, 0): e10, (0, 1): e10.T}
+    tot = (e[1, 1] + e[0, 0]) + (e[1, 0] + e[0, 1])
+    N = (O[1, 1] + O[0, 0]) + (O[1, 0] + O[0, 1])
+    E = {ab: N * (e[ab] / tot) for ab in e}
+
+    def x2_term(ab):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d2 = (O[ab] - E[ab]) ** 2
+            return np.where(d2 > 0, d2 / E[ab], 0.0)
+
+    def g2_term(ab):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pos = O[ab] > 0
+            return np.where(pos, O[ab] * np.log(np.where(pos, O[ab], 1.0) / E[ab]), 0.0)
+
+    # (11 + 00) + (10 + 01): the order that a transposition leaves as it is
+    x2 = (x2_term((1, 1)) + x2_term((0, 0))) + (x2_term((1, 0)) + x2_term((0, 1)))
+    g2 = 2.0 * ((g2_term((1, 1)) + g2_term((0, 0))) + (g2_term((1, 0)) + g2_term((0, 1))))
+    bad = np.eye(J, dtype=bool) | (N < min_pairs)
+    for ab in E:
+        bad |= ~(E[ab] >= min_expected)
+    x2, g2 = np.where(bad, np.nan, x2), np.where(bad, np.nan, g2)
+    # chi2_sf(x, 1) = erfc(sqrt(x / 2)), for all pairs at once
+    p = np.where(bad, np.nan, torch.erfc(torch.from_numpy(np.sqrt(0.5 * np.where(bad, 0.0, x2)))).numpy())
+    phi_obs = _phi_2x2(O[1, 1], O[1, 0], O[0, 1], O[0, 0])
+    phi_exp = _phi_2x2(e[1, 1], e[1, 0], e[0, 1], e[0, 0])
+    with np.errstate(invalid="ignore"):
+        sign = np.where(bad | ~np.isfinite(phi_obs) | ~np.isfinite(phi_exp), 0.0, np.sign(phi_obs - phi_exp))
+    return {"x2": x2, "g2": g2, "z": (x2 - 1.0) / np.sqrt(2.0), "p": p, "sign": sign, "phi_obs": phi_obs, "phi_exp": phi_exp,
+            "n_pairs": np.rint(N).astype(np.int64), "expected": np.stack([np.stack([E[0, 0], E[0, 1]]), np.stack([E[1, 0], E[1, 1]])])}
+
+
+def pair_x2_top(x2, sign, top=20):
+    """The `top` pairs j < k by descending x2 (ties: the lower pair first) as `item_j`, `item_k` (int64), `value` = their x2 and
+    `sign`; pairs without a statistic (NaN) are not listed."""
+    J = x2.shape[0]
+    jj, kk = np.triu_indices(J, 1)
+    val = x2[jj, kk]
+    fin = np.isfinite(val)
+    jj, kk, val = jj[fin], kk[fin], val[fin]
+    order = np.argsort(-val, kind="stable")[:top]
+    return {"item_j": jj[order].astype(np.int64), "item_k": kk[order].astype(np.int64), "value": val[order],
+            "sign": np.asarray(sign)[jj[order], kk[order]]}
+
+
 PERSON_SUMS = ("n", "l0", "e", "v", "sr2", "sw", "sz2")          # the rows of vx_grid_fit_*'s `person` ...
 ITEM_SUMS = ("n", "sr2", "sw", "sz2")                            # ... and of its `item`
 
@@ -1085,6 +1169,61 @@ class GridMixin(object):
         q3 = pair_q3_host(n, t["s"].cpu().numpy(), t["ss"].cpu().numpy(), t["sp"].cpu().numpy(), min_pairs)
         out = pair_q3_summary(q3, top)
         out["q3"], out["n_pairs"] = q3, np.rint(n).astype(np.int64)
+        return out
+
+    def pair_tables(self, y_u8=None, rows=None):
+        """The observed 2 x 2 table of every item pair over the scored rows (vx_pair_tables, the int8 MFMA): int32 device tensors
+        [J][J] `n11`, `n10`, `n01`, `n00` -- n_ab[j][k] = the persons who answered both items, a to item j and b to item k.  A
+        cell that is neither 0 nor 1 (255 = missing) takes its person out of that item's pairs only.  n11 and n00 are symmetric,
+        n10[j][k] = n01[k][j]; the diagonal of n11 / n00 holds the item's counts of 1s / 0s, that of n10 and n01 zeros; their sum
+        is residual_sums()["n"].  Inputs and `rows` as score(); the model's own items and persons only (no phantoms of a padded
+        engine).  Needs no grid and no item parameter: every model and every x_feature.  Exact integers up to 2**31 - 1
+        persons, the same bits on every call.  One rank only."""
+        self._one_rank_only("pair_tables / ld_x2 over a process group: the tables are the sums over the local shard's persons and "
+                            "the cross-rank sum is not built")
+        J = int(getattr(self, "J_items", self.J))
+        y, rows = self._score_inputs(y_u8, rows, J)
+        n = int(y.shape[0]) if rows is None else int(rows.numel())
+        out = {k: torch.empty(J, J, dtype=torch.int32, device=self.dev) for k in PAIR_TABLES}
+        ws_ints = self.be.pair_tables_workspace(n, J)
+        ws = torch.empty(ws_ints, dtype=torch.int32, device=self.dev) if ws_ints else None
+        self.be.pair_tables(y, rows, n, J, out["n11"], out["n10"], out["n01"], out["n00"], ws, ws_ints)
+        return out
+
+    def ld_x2(self, y_u8=None, rows=None, min_pairs=8, min_expected=1.0, top=20, **grid_kw):
+        """Chen & Thissen's (1997) LD X2 (and G2) of every item pair (pair_x2_host over pair_tables): the observed 2 x 2 table
+        of the persons who answered both items against the table the model predicts, E_ab = N_jk sum_g w_g p_a[j][g] p_b[k][g]
+        over the nodes and the prior of score(), with p1 and p0 read back from the operand image the kernels multiply with.
+        **The statistic is taken at the item parameters as they stand.  chi-square(1) is the reference Chen & Thissen propose
+        after the item parameters were ESTIMATED from these data -- estimation fits the margins.  At parameters that were not
+        fitted to these data (generating values, another sample's estimates) a fully specified 2 x 2 table has up to 3 degrees
+        of freedom and the statistic runs higher.  The reference is approximate in any case; the authors say so.**  With cells
+        missing completely at random (booklet designs) the persons who answered both items have the prior of score(); under
+        other missingness mechanisms they have not, and E is off by that much.
+        Returns numpy: `x2`, `g2`, `z` = (x2 - 1) / sqrt 2, `p` = chi2_sf(x2, 1), `sign` (+1: the pair agrees more than the model
+        says, -1: less), `phi_obs`, `phi_exp`, float64 [J][J], all symmetric; NaN in x2, g2, z, p on the diagonal, where fewer
+        than min_pairs persons answered both items and where an expected count is below min_expected (sign 0 there);
+        `n_pairs` int64 [J][J]; `expected` [2][2][J][J]; and `item_j`, `item_k`, `value`, `sign_top`: the `top` pairs j < k by
+        descending x2 with their signs.  Inputs, grid and refusals as score(); one rank only.  Not built: polytomous tables,
+        covariates= / at=, M2, more than one rank."""
+        min_pairs = self._int_in("min_pairs", min_pairs, 1)
+        top = self._int_in("top", top, 0)
+        if isinstance(min_expected, bool) or not (isinstance(min_expected, (int, float, np.floating, np.integer))
+                                                  and np.isfinite(min_expected) and min_expected > 0):
+            raise ValueError("min_expected must be a positive finite number")
+        for k in ("covariates", "at"):
+            if k in grid_kw:
+                raise NotImplementedError("ld_x2 with %s=: the expected tables are built under the prior of score() and need no "
+                                          "point estimate; the latent regression's prior is not built" % k)
+        self._one_rank_only("pair_tables / ld_x2 over a process group: the tables are the sums over the local shard's persons and "
+                            "the cross-rank sum is not built")
+        call = self._grid_call(y_u8, rows, **grid_kw)
+        p1, p0 = grid_image_probs(self._grid_image(call), call.J, call.G)
+        t = self.pair_tables(call.y, call.rows)
+        out = pair_x2_host(*(t[k].cpu().numpy() for k in PAIR_TABLES), p1.cpu().numpy(), p0.cpu().numpy(), call.logw.cpu().numpy(),
+                           min_pairs, min_expected)
+        tp = pair_x2_top(out["x2"], out["sign"], top)
+        out.update({"item_j": tp["item_j"], "item_k": tp["item_k"], "value": tp["value"], "sign_top": tp["sign"]})
         return out
 
     def fit_sums(self, y_u8=None, rows=None, at="eap", **grid_kw):

@@ -387,6 +387,38 @@ class BasePsy(object):
                                       "persons; the cross-rank sum is not built" % self.world)
         return self.engine.local_dependence(self._score_data(data), **kw)
 
+    def pair_tables(self, data=None, **kw):
+        """The observed 2 x 2 table of every item pair, as int32 device tensors [items][items]: `n11`, `n10`, `n01`, `n00`, the
+        persons who answered both items with a to the row item and b to the column item (GridMixin.pair_tables: exact integer
+        cross products on the int8 matrix cores).  A missing cell takes its person out of that item's pairs only.  `data`: None
+        = the training data; rows= as score().  VIRT / VaeIRT with any model and any x_feature -- no grid is needed -- and
+        VCCDM; the other classes refuse.  One rank only."""
+        if self.world > 1:
+            raise NotImplementedError("pair_tables with a group of %d ranks: the tables are the sums over the local shard's "
+                                      "persons; the cross-rank sum is not built" % self.world)
+        return self.engine.pair_tables(self._score_data(data), **kw)
+
+    def ld_x2(self, data=None, min_pairs=8, min_expected=1.0, top=20, **grid_kw):
+        """Chen & Thissen's LD X2 for every item pair, ready to print beside local_dependence(): the observed 2 x 2 table of the
+        persons who answered both items against the table the model predicts under the prior of score(), as a test with a
+        reference distribution where Q3 is a size without one.  A dict of numpy values: `x2`, `g2`, `z` = (x2 - 1) / sqrt 2, `p`
+        (the chi-square(1) tail of x2), `sign` (+1: the pair agrees more than the model says), `phi_obs`, `phi_exp`
+        [items][items], `n_pairs`, `expected` [2][2][items][items] and `item_j`, `item_k`, `value`, `sign_top`, the `top` (20)
+        pairs by x2 (GridMixin.ld_x2).  NaN means no statistic: the diagonal, fewer than `min_pairs` (8) persons answered both
+        items, or an expected count below `min_expected` (1).
+        **The statistic is taken at the item parameters as they stand.  chi-square(1) is the reference Chen & Thissen propose
+        after the item parameters were ESTIMATED from these data (estimation fits the margins); at parameters that were not
+        fitted to them, generating values for instance, a fully specified 2 x 2 table has up to 3 degrees of freedom and the
+        statistic runs higher.  The reference is approximate in any case, as the authors say.**  The expected table assumes
+        the persons who answered both items have the prior of score(): true for cells missing completely at random (booklet
+        designs), not for other missingness mechanisms.  `data`: None = the training data.  VIRT / VaeIRT with x_feature <= 3,
+        every IRT model (grid_kw: nodes, span), VCCDM; the other classes refuse.  Not built: polytomous tables, covariates= /
+        at=, M2, more than one rank."""
+        if self.world > 1:
+            raise NotImplementedError("ld_x2 with a group of %d ranks: the tables are the sums over the local shard's persons; "
+                                      "the cross-rank sum is not built" % self.world)
+        return self.engine.ld_x2(self._score_data(data), min_pairs=min_pairs, min_expected=min_expected, top=top, **grid_kw)
+
     def fit_sums(self, data=None, **grid_kw):
         """The sums behind person_fit() and item_msq(), as device tensors: `person` {n, l0, e, v, sr2, sw, sz2}, each [persons],
         `item` {n, sr2, sw, sz2}, each [items], and `theta_hat` or `pattern` (GridMixin.fit_sums).  `data`: None = the training
