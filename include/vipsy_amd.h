@@ -444,6 +444,54 @@ int vx_grid_posterior(const uint8_t* y /*[n_local][J]*/, const int64_t* rows /*[
                       float* loglik /*[nb]*/, float* mean /*[nb][D]*/, float* sd /*[nb][D]*/, int32_t* argmax /*[nb]*/,
                       void* hip_stream);
 
+/* ---- Grid scores of a bifactor / testlet model: one general dimension every item loads on and S specific dimensions, each loaded
+ * on by the items of one testlet only.  Given the general node the testlets are independent, and each is a one-dimensional
+ * integral over its own specific factor (Gibbons & Hedeker 1992), so with Gg general nodes (logw, coord) and Gh specific nodes
+ * (logv, u; both sets of log-weights normalised)
+ *     m[i][s][g] = log sum_h exp(logv[h] + sum_{j in s} log P(y_ij | coord[g], u[h]))     the bracket of testlet s
+ *     F[i][g]    = logw[g] + (#missing_i) VX_LOGP_MISSING + sum_s m[i][s][g]              (the constant enters once)
+ *     loglik[i]  = log sum_g exp(F[i][g])                                              the marginal log-likelihood of the row
+ *     mean[i], sd[i]                     EAP and PSD of the general dimension: the moments of coord under post[i][g] = exp(F - loglik)
+ *     argmax[i]                          the node that maximises F, the general MARGINAL posterior (ties: the lowest index)
+ *     mean_s[s][i] = sum_g post[i][g] E[u | g, y_is],  E[u | g, y_is] = sum_h u[h] exp(logv[h] + ll_is(g, h) - m[i][s][g])
+ *     sd_s[s][i]   = sqrt(sum_g post[i][g] E[u^2 | g, y_is] - mean_s^2)
+ * -- the work of ONE two-dimensional grid whatever S is: nothing of size Gg Gh^S exists anywhere.
+ * Testlet layout: the items testlet after testlet, each padded to whole chunks of 16; testlet t holds the chunks tl_start[t] ..
+ * tl_start[t + 1] - 1 of the KC = tl_start[n_tl] chunks; the items that load on the general dimension alone form one more
+ * (pseudo-)testlet, whose table does not depend on h.  Slot jp of the layout holds item col[jp] of the model (-1: padding) whose
+ * specific dimension is sdim[jp] (-1: none).  tl_start is read on the HOST (int32 [n_tl + 1], strictly increasing from 0 to KC; it
+ * is checked, and not used after the call returns); tl_start_dev is the same table in device memory.
+ *   1. vx_grid_table_bifactor fills `img` (vx_grid_bifactor_image_bytes(Gg, KC) bytes, 16-byte aligned): [Gg][KC][4: T1 head, T1
+ *      low, T0 head, T0 low][64 lanes][8 fp16], the layout of vx_grid_table_irt with the general node in the place of the node
+ *      tile and the specific node h in the place of the node in it; rows >= Gh and padding slots are zero.  z = Dc (b_j +
+ *      a[general][j] coord[g] + a[sdim][j] u[h]) through the cell of the step kernels; a [D][J], b, c_un, d_un as the step takes
+ *      them.  cfg: model (2 .. 4), D (>= 2), J, Dc.  col and sdim are int32 [16 KC] in DEVICE memory.
+ *   2. vx_grid_bifactor: y is [nb][16 KC] u8 IN THE TESTLET LAYOUT (the caller permutes the columns; padding slots hold 254).
+ *      fws NULL, or vx_grid_bifactor_workspace_floats(nb, Gg) floats that receive F, [unit of 64 persons][Gg][64].
+ *   3. vx_grid_bifactor_specific (optional): same y, layout, image; loglik and fws as step 2 left them.  mean_s, sd_s are
+ *      [n_tl][nb], the pseudo-testlet's row included.  It recomputes the tiles: the MFMA work of step 2 once more.
+ * The sums of a testlet run on v_mfma_f32_32x32x16_f16 (fp16 head + low of T 2^10, four MFMAs a chunk), the person on the lane;
+ * the log-sum-exp over h is a loop over the lane's accumulator registers and one exchange with lane ^ 32.  Nothing of size
+ * [nb][Gg Gh] touches memory, there are no atomics, and every sum runs in a fixed order (chunks, h, testlets, g ascending) that
+ * depends on neither the person's place in the batch nor the launch: the same call gives the same bits.
+ * Limits: 2 <= Gg <= 256, 1 <= Gh <= 32, 1 <= n_tl <= KC <= 1024, 1 <= J <= 1024, 2 <= D <= 4096, 0 <= general < D, nb >= 1, image
+ * <= 512 MB; VX_EINVAL beyond them. */
+int64_t vx_grid_bifactor_image_bytes(int32_t Gg, int32_t KC);
+int64_t vx_grid_bifactor_workspace_floats(int64_t nb, int32_t Gg);
+int vx_grid_table_bifactor(const vx_irt_cfg* cfg, const float* coord /*[Gg]*/, int32_t Gg, const float* u /*[Gh]*/, int32_t Gh,
+                           int32_t general, const int32_t* col /*[16 KC], device*/, const int32_t* sdim /*[16 KC], device*/,
+                           int32_t KC, const float* a /*[D][J]*/, const float* b /*[J]*/, const float* c_un /*[J] or NULL*/,
+                           const float* d_un /*[J] or NULL*/, void* img, void* hip_stream);
+int vx_grid_bifactor(const uint8_t* y /*[nb][16 KC]*/, int64_t nb, int32_t KC, int32_t Gg, int32_t Gh,
+                     const int32_t* tl_start /*[n_tl + 1], HOST*/, int32_t n_tl, const int32_t* tl_start_dev /*[n_tl + 1]*/,
+                     const void* img, const float* logw /*[Gg]*/, const float* coord /*[Gg]*/, const float* logv /*[Gh]*/,
+                     const float* u /*[Gh]*/, float* loglik /*[nb]*/, float* mean /*[nb]*/, float* sd /*[nb]*/,
+                     int32_t* argmax /*[nb]*/, float* fws /*or NULL*/, void* hip_stream);
+int vx_grid_bifactor_specific(const uint8_t* y /*[nb][16 KC]*/, int64_t nb, int32_t KC, int32_t Gg, int32_t Gh,
+                              const int32_t* tl_start /*[n_tl + 1], HOST*/, int32_t n_tl, const int32_t* tl_start_dev,
+                              const void* img, const float* logv /*[Gh]*/, const float* u /*[Gh]*/, const float* loglik /*[nb]*/,
+                              const float* fws, float* mean_s /*[n_tl][nb]*/, float* sd_s /*[n_tl][nb]*/, void* hip_stream);
+
 /* ---- Plausible values: draws of a person's node from the grid posterior p_i(g) ~ exp(logw[g] + ll[i][g]) of vx_grid_posterior
  * (same y, rows, nb, img, logw), by the Gumbel-max rule: node[i][m] = argmax_g (logw[g] + ll[i][g] + noise(r, g, m)), ties to the
  * lowest g.  No normalisation, no second pass, nothing of size [nb][G] touches memory, no workspace, no atomics.  The noise is

@@ -128,6 +128,12 @@ SIGNATURES = {
     "vx_grid_table_irt": (ctypes.c_int, [_CFG, _P, _I32] + [_P] * 4 + [_P, _P]),
     "vx_grid_table_cdm": (ctypes.c_int, [ctypes.POINTER(HoDinaCfg), _I32] + [_P] * 3 + [_P, _P]),
     "vx_grid_posterior": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 3 + [_P] * 4 + [_P]),
+    "vx_grid_bifactor_image_bytes": (_I64, [_I32, _I32]),
+    "vx_grid_bifactor_workspace_floats": (_I64, [_I64, _I32]),
+    "vx_grid_table_bifactor": (ctypes.c_int, [_CFG, _P, _I32, _P, _I32, _I32, _P, _P, _I32] + [_P] * 4 + [_P, _P]),
+    # tl_start (HOST, int32 [n_tl + 1]) is a typed pointer: the entry reads it, and refuses it when null
+    "vx_grid_bifactor": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P] + [_P] * 5 + [_P] * 4 + [_P, _P]),
+    "vx_grid_bifactor_specific": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P] + [_P] * 5 + [_P, _P, _P]),
     "vx_grid_draw": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _U64, _I64, _I32, _I32, _I64, _P, _P]),
     "vx_grid_posterior_cond": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 4 + [_P] * 5 + [_P]),
     "vx_grid_draw_cond": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 4 + [_U64, _I64, _I32, _I32, _I64, _P, _P]),

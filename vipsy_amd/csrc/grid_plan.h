@@ -187,6 +187,30 @@ inline GfPlan gf_plan(int64_t nb) {
 // the item partials of the workgroups: [n_blocks][GF_ITEM][J]
 inline int64_t gf_ws_floats(int64_t nb, int J) { return gf_plan(nb).n_blocks * GF_ITEM * (int64_t)J; }
 
+// ---- GbPlan: vx_grid_bifactor* (k_grid_bifactor.hip) ---------------------------------------------------------------------
+#define GB_MAXGG 256                    // general nodes
+#define GB_MAXGH 32                     // specific nodes: the rows of one tile
+#define GB_MAXKC 1024                   // chunks of the testlet layout (1 024 items, were every one a testlet of its own)
+#define GB_MAXD 4096                    // dimensions of the model the tables are built from
+#define GB_MAX_IMAGE ((int64_t)512 << 20)       // bytes of the operand image
+
+// [Gg][KC][4][64 lanes][8 fp16]
+VX_PLAN_HD inline int64_t gb_image_bytes(int64_t Gg, int64_t KC) { return Gg * KC * 4 * 64 * 16; }
+// what a call may be asked for, from its scalars alone (int64: no product of two of them can overflow)
+inline bool gb_shape_ok(int64_t Gg, int64_t Gh, int64_t KC, int64_t n_tl, int64_t nb, int64_t max_persons) {
+    return Gg >= 2 && Gg <= GB_MAXGG && Gh >= 1 && Gh <= GB_MAXGH && KC >= 1 && KC <= GB_MAXKC && n_tl >= 1 && n_tl <= KC &&
+           nb >= 1 && nb <= max_persons && gb_image_bytes(Gg, KC) <= GB_MAX_IMAGE;
+}
+// the chunk starts of the testlets: 0 = tl_start[0] < tl_start[1] < .. < tl_start[n_tl] = KC (no empty testlet)
+inline bool gb_testlets_ok(const int32_t* tl_start, int n_tl, int KC) {
+    if (!tl_start || tl_start[0] != 0 || tl_start[n_tl] != KC) return false;
+    for (int t = 0; t < n_tl; ++t)
+        if (tl_start[t + 1] <= tl_start[t]) return false;
+    return true;
+}
+// the workspace of specific = true: F, one float a person and general node, [units of 64 persons][Gg][64]
+inline int64_t gb_ws_floats(int64_t nb, int64_t Gg) { return ((nb + 63) / 64) * Gg * 64; }
+
 // ---- SsPlan: vx_sumscore_model (k_sumscore.hip) --------------------------------------------------------------------------
 #define SS_TARGET_WAVES 8192            // waves of the leave-one-out launch where the nodes allow: 8 a SIMD on 256 CUs
 

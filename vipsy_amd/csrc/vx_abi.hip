@@ -40,6 +40,7 @@
 #include "k_grid_point.hip"
 #include "k_grid_cond.hip"
 #include "k_grid_counts_cond.hip"
+#include "k_grid_bifactor.hip"
 #include "k_sumscore.hip"
 #include "k_pair_tables.hip"
 
@@ -2310,6 +2311,58 @@ int vx_grid_posterior(const uint8_t* y, const int64_t* rows, int64_t nb, int32_t
     if (D == 1) { LAUNCH_GP(1); } else if (D == 2) { LAUNCH_GP(2); } else if (D == 3) { LAUNCH_GP(3); }
     else if (D == 4) { LAUNCH_GP(4); } else if (D <= 6) { LAUNCH_GP(6); } else if (D <= 8) { LAUNCH_GP(8); } else { LAUNCH_GP(10); }
 #undef LAUNCH_GP
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+// Bifactor / testlet scores (k_grid_bifactor.hip): the table builder, the kernel of the general marginal, the specific moments.
+// tl_start is HOST memory (checked here; tl_start_dev is the same table on the device, which the kernels read).
+int64_t vx_grid_bifactor_image_bytes(int32_t Gg, int32_t KC) {
+    if (!gb_shape_ok(Gg, 1, KC, 1, 1, GRID_MAX_PERSONS)) return VX_EINVAL;
+    return gb_image_bytes(Gg, KC);
+}
+
+int64_t vx_grid_bifactor_workspace_floats(int64_t nb, int32_t Gg) {
+    if (!gb_shape_ok(Gg, 1, 1, 1, nb, GRID_MAX_PERSONS)) return VX_EINVAL;
+    return gb_ws_floats(nb, Gg);
+}
+
+int vx_grid_table_bifactor(const vx_irt_cfg* cfg, const float* theta_g, int32_t Gg, const float* u, int32_t Gh, int32_t general,
+                           const int32_t* col, const int32_t* sdim, int32_t KC, const float* a, const float* b, const float* c_un,
+                           const float* d_un, void* img, void* hs) {
+    if (!irt_items_ok(cfg, 4, GB_MAXD, a, b, c_un, d_un) || cfg->model < 2 || cfg->D < 2 || cfg->J < 1 || cfg->J > GP_MAXJ)
+        return VX_EINVAL;
+    if (!gb_shape_ok(Gg, Gh, KC, 1, 1, GRID_MAX_PERSONS) || general < 0 || general >= cfg->D) return VX_EINVAL;
+    if (!theta_g || !u || !col || !sdim || !img || !aligned16(img)) return VX_EINVAL;
+    const int blocks = grid_1d((int64_t)Gg * 32 * KC * 16, 256);
+    return with_irt_model(cfg->model, [&](auto m) -> int {
+        hipLaunchKernelGGL((k_grid_table_bifactor<decltype(m)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)hs, (int)cfg->D,
+                           (int)cfg->J, (int)Gg, (int)Gh, (int)KC, (int)general, cfg->Dc, theta_g, u, col, sdim, a, b, c_un, d_un,
+                           (uint16_t*)img);
+        VX_CHECK_LAUNCH();
+        return VX_OK;
+    });
+}
+
+int vx_grid_bifactor(const uint8_t* y, int64_t nb, int32_t KC, int32_t Gg, int32_t Gh, const int32_t* tl_start, int32_t n_tl,
+                     const int32_t* tl_start_dev, const void* img, const float* logw, const float* coord, const float* logv,
+                     const float* u, float* loglik, float* mean, float* sd, int32_t* argmax, float* fws, void* hs) {
+    if (!y || !tl_start_dev || !img || !aligned16(img) || !logw || !coord || !logv || !u || !loglik || !mean || !sd || !argmax)
+        return VX_EINVAL;
+    if (!gb_shape_ok(Gg, Gh, KC, n_tl, nb, GRID_MAX_PERSONS) || !gb_testlets_ok(tl_start, (int)n_tl, (int)KC)) return VX_EINVAL;
+    hipLaunchKernelGGL(k_grid_bifactor, dim3(grid_unit_blocks(nb)), dim3(GP_THREADS), 0, (hipStream_t)hs, y, nb, (int)KC, (int)Gg,
+                       (int)Gh, tl_start_dev, (int)n_tl, (const uint4*)img, logw, coord, logv, u, loglik, mean, sd, argmax, fws);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+int vx_grid_bifactor_specific(const uint8_t* y, int64_t nb, int32_t KC, int32_t Gg, int32_t Gh, const int32_t* tl_start,
+                              int32_t n_tl, const int32_t* tl_start_dev, const void* img, const float* logv, const float* u,
+                              const float* loglik, const float* fws, float* mean_s, float* sd_s, void* hs) {
+    if (!y || !tl_start_dev || !img || !aligned16(img) || !logv || !u || !loglik || !fws || !mean_s || !sd_s) return VX_EINVAL;
+    if (!gb_shape_ok(Gg, Gh, KC, n_tl, nb, GRID_MAX_PERSONS) || !gb_testlets_ok(tl_start, (int)n_tl, (int)KC)) return VX_EINVAL;
+    hipLaunchKernelGGL(k_grid_bifactor_spec, dim3(grid_unit_blocks(nb)), dim3(GP_THREADS), 0, (hipStream_t)hs, y, nb, (int)KC,
+                       (int)Gg, (int)Gh, tl_start_dev, (int)n_tl, (const uint4*)img, logv, u, loglik, fws, mean_s, sd_s);
     VX_CHECK_LAUNCH();
     return VX_OK;
 }

@@ -19,6 +19,7 @@ from .grid import (EM_MAX_NEWTON, PV_MAX_DRAWS, PV_STREAM, SCORE_MAX_DIMS, SCORE
                    design_cholesky, em_prior, grid_image_prob, item_fit_stats, population_logw, score_grid, tri_to_full)     # (re-exported: the grid family lives in grid.py)
 from .grid import (POINT_AT_BOUND, POINT_CONVERGED, POINT_EMPTY, POINT_MAX_ITER, POINT_MAX_ITERS, POINT_METHODS,  # noqa: F401
                    POINT_SINGULAR, POINT_STATUS, POINT_STEP_CAP, point_estimates_host)
+from .grid import bifactor_grid, bifactor_plan, bifactor_slab_persons, bifactor_structure  # noqa: F401
 
 MODEL_CODE = {"irt_1pl": 1, "irt_2pl": 2, "irt_3pl": 3, "irt_4pl": 4}       # vi.py:538-543
 LOSS_RING = 64                                                               # VX_LOSS_RING (include/vipsy_amd.h)
@@ -284,6 +285,40 @@ class HipBackend(object):
         rc = self.L.vx_grid_posterior(_hip.ptr(y), _hip.ptr(rows), nb, J, G, D, _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord),
                                       _hip.ptr(loglik), _hip.ptr(mean), _hip.ptr(sd), _hip.ptr(argmax), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_posterior")
+
+    def grid_bifactor_image_bytes(self, Gg, KC):
+        return self._size("vx_grid_bifactor_image_bytes", Gg, KC)
+
+    def grid_bifactor_workspace(self, nb, Gg):
+        return self._size("vx_grid_bifactor_workspace_floats", nb, Gg)
+
+    def grid_table_bifactor(self, cfg, theta, u, general, col, sdim, KC, a, b, c_un, d_un, img):
+        rc = self.L.vx_grid_table_bifactor(ctypes.byref(cfg), _hip.ptr(theta), int(theta.numel()), _hip.ptr(u), int(u.numel()),
+                                           int(general), _hip.ptr(col), _hip.ptr(sdim), int(KC), _hip.ptr(a), _hip.ptr(b),
+                                           _hip.ptr(c_un), _hip.ptr(d_un), _hip.ptr(img), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_table_bifactor")
+
+    @staticmethod
+    def _tl_start(tl_start):
+        """tl_start as the entries read it on the HOST: contiguous int32 numpy, and the pointer to it."""
+        tl = np.ascontiguousarray(tl_start, dtype=np.int32)
+        return tl, tl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+    def grid_bifactor(self, y, nb, KC, tl_start, tl_start_dev, img, logw, coord, logv, u, loglik, mean, sd, argmax, fws):
+        """tl_start: int32 numpy [n_tl + 1] on the HOST (the entry checks it); tl_start_dev: the same on the device."""
+        tl, tlp = self._tl_start(tl_start)
+        rc = self.L.vx_grid_bifactor(_hip.ptr(y), nb, int(KC), int(logw.numel()), int(logv.numel()), tlp, int(tl.size) - 1,
+                                     _hip.ptr(tl_start_dev), _hip.ptr(img), _hip.ptr(logw), _hip.ptr(coord), _hip.ptr(logv),
+                                     _hip.ptr(u), _hip.ptr(loglik), _hip.ptr(mean), _hip.ptr(sd), _hip.ptr(argmax), _hip.ptr(fws),
+                                     _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_bifactor")
+
+    def grid_bifactor_specific(self, y, nb, KC, Gg, tl_start, tl_start_dev, img, logv, u, loglik, fws, mean_s, sd_s):
+        tl, tlp = self._tl_start(tl_start)
+        rc = self.L.vx_grid_bifactor_specific(_hip.ptr(y), nb, int(KC), int(Gg), int(logv.numel()), tlp, int(tl.size) - 1,
+                                              _hip.ptr(tl_start_dev), _hip.ptr(img), _hip.ptr(logv), _hip.ptr(u), _hip.ptr(loglik),
+                                              _hip.ptr(fws), _hip.ptr(mean_s), _hip.ptr(sd_s), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_bifactor_specific")
 
     def grid_draw(self, y, rows, nb, J, G, img, logw, seed, row_offset, draw0, ndraws, stride, node):
         rc = self.L.vx_grid_draw(_hip.ptr(y), _hip.ptr(rows), nb, J, G, _hip.ptr(img), _hip.ptr(logw), int(seed), int(row_offset),
@@ -738,6 +773,7 @@ class _EngineBase(object):
     group_counts = dif = _no_grid
     sumscore_tables = sx2 = score_table = _no_grid
     point_estimates = _no_grid
+    score_bifactor = bifactor_structure = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1678,6 +1714,79 @@ class IrtEngine(GridMixin, _EngineBase):
         out = self._grid_posterior(self._grid_call(y_u8, rows, nodes, span))
         return {"eap": out["mean"], "psd": out["sd"], "loglik": out["loglik"], "node": out["node"]}
 
+    def bifactor_structure(self, general=0):
+        """The bifactor / testlet structure of this model, read from the engine's free mask (a_free, or the triangular default)
+        and the loadings as they stand, on the host (grid.bifactor_structure): {"general", "specific_dims", "testlet" (the column
+        of specific_dims an item loads on; -1: the general dimension alone), "sizes"}.  The model's own items and dimensions.
+        Every x_feature = 2 model is a bifactor with one specific dimension; the default mask of x_feature >= 3 is refused."""
+        if self.model == "irt_1pl" or self.D_model < 2:
+            return bifactor_structure(np.zeros((1, 1)), np.zeros((1, 1)), self.model, general)      # (raises)
+        return bifactor_structure(self.unconstrained("a", self.free).cpu().numpy(), self.unconstrained("a").cpu().numpy(),
+                                  self.model, general)
+
+    def score_bifactor(self, y_u8=None, rows=None, nodes=(61, 21), span=(6.0, 4.0), general=0, specific=False, covariates=None):
+        """Exact grid scores of a bifactor / testlet model (bifactor_structure(general)), any x_feature >= 2: given the general
+        node the testlets are independent, each a one-dimensional integral over its own specific factor (Gibbons & Hedeker), so
+        the work is that of ONE two-dimensional grid of nodes = (Gg, Gh) points (grid.bifactor_grid) whatever the number of
+        specific dimensions.  y_u8 / rows, missing codes, new respondents, phantoms and the shard of a process group as score().
+        Returns `loglik` (n,), `eap_general`, `psd_general` (n,) and `node` (n,) int32, the MAP node of the general MARGINAL
+        posterior (ties: the lowest); with specific=True also `eap_specific`, `psd_specific` (n, S) and `specific_dims` [S], the
+        model dimension behind each column -- a second kernel that recomputes the tiles, so the MFMA work doubles.  A specific
+        dimension without items gets the moments of the grid prior.  The item order is free: the responses are permuted into
+        the testlet layout on the device, grid.bifactor_slab_persons() persons at a time.  Deterministic: the same call gives
+        the same bits, and so does a person reached through `rows`.
+        ValueError beyond 2 <= Gg <= 256, 1 <= Gh <= 32, 1 024 items or an operand image of 512 MB (Gg x item chunks x 4 KB)."""
+        if covariates is not None:
+            raise NotImplementedError("score_bifactor with covariates=: the latent regression of fit_population() is built for "
+                                      "x_feature <= 3 and the tensor-product grid of score()")
+        theta_np, logw_np, u_np, logv_np = bifactor_grid(nodes, span)
+        st = self.bifactor_structure(general)
+        plan = bifactor_plan(st["testlet"], st["specific_dims"], theta_np.shape[0])
+        J, Dm, KC, S = self.J_items, self.D_model, plan["KC"], len(st["specific_dims"])
+        y, rows = self._score_inputs(y_u8, rows, J)
+        n = int(y.shape[0]) if rows is None else int(rows.numel())
+        dev = self.dev
+        theta, logw, u, logv = (torch.from_numpy(t).to(dev) for t in (theta_np, logw_np, u_np, logv_np))
+        col, sdim, tl_dev = (torch.from_numpy(plan[k]).to(dev) for k in ("col", "sdim", "tl_start"))
+        flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()      # noqa: E731
+        cfg = self.be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
+        img = torch.empty(self.be.grid_bifactor_image_bytes(len(theta_np), KC), dtype=torch.uint8, device=dev)
+        self.be.grid_table_bifactor(cfg, theta, u, st["general"], col, sdim, KC, self.unconstrained("a").contiguous(), flat("b"),
+                                    flat("c") if self.model in ("irt_3pl", "irt_4pl") else None,
+                                    flat("d") if self.model == "irt_4pl" else None, img)
+        f32 = dict(dtype=torch.float32, device=dev)
+        out = {"loglik": torch.empty(n, **f32), "eap_general": torch.empty(n, **f32), "psd_general": torch.empty(n, **f32),
+               "node": torch.empty(n, dtype=torch.int32, device=dev)}
+        if specific:
+            # a dimension without items: the moments of the grid prior
+            v = np.exp(logv_np.astype(np.float64))
+            v = v / v.sum()
+            m1 = float((v * u_np).sum())
+            sd0 = float(np.sqrt(max((v * u_np.astype(np.float64) ** 2).sum() - m1 * m1, 0.0)))
+            out["eap_specific"] = torch.full((n, S), m1, **f32)
+            out["psd_specific"] = torch.full((n, S), sd0, **f32)
+            out["specific_dims"] = st["specific_dims"]
+            real = np.flatnonzero(plan["tl_column"] >= 0)
+            real_t, cols_t = torch.from_numpy(real).to(dev), torch.from_numpy(plan["tl_column"][real]).to(dev)
+        # slot -> column of the responses, the padding slots to one more column of 254 ("outside the problem")
+        src = torch.where(col >= 0, col, torch.full_like(col, J)).long()
+        slab = bifactor_slab_persons(KC)
+        for s0 in range(0, n, slab):
+            s1 = min(n, s0 + slab)
+            ys = y[s0:s1] if rows is None else y[rows[s0:s1]]
+            yp = torch.cat([ys, torch.full((s1 - s0, 1), 254, dtype=torch.uint8, device=dev)], 1)[:, src].contiguous()
+            fws = torch.empty(self.be.grid_bifactor_workspace(s1 - s0, len(theta_np)), **f32) if specific else None
+            self.be.grid_bifactor(yp, s1 - s0, KC, plan["tl_start"], tl_dev, img, logw, theta, logv, u, out["loglik"][s0:s1],
+                                  out["eap_general"][s0:s1], out["psd_general"][s0:s1], out["node"][s0:s1], fws)
+            if specific:
+                ms = torch.empty(len(plan["tl_column"]), s1 - s0, **f32)
+                ss = torch.empty_like(ms)
+                self.be.grid_bifactor_specific(yp, s1 - s0, KC, len(theta_np), plan["tl_start"], tl_dev, img, logv, u,
+                                               out["loglik"][s0:s1], fws, ms, ss)
+                out["eap_specific"][s0:s1, cols_t] = ms[real_t].t()
+                out["psd_specific"][s0:s1, cols_t] = ss[real_t].t()
+        return out
+
     def _population_call(self, y_u8, rows, nodes, span, covariates):
         """The GridCall of a conditioned score: the nodes of score() with the log-weights of engine.population's Sigma, the tilt
         Lambda Gamma^T x_i [n][D] float32 by batch position and the prior means Gamma^T x_i."""
@@ -2451,6 +2560,12 @@ class CcdmEngine(GridMixin, _EngineBase):
         raise NotImplementedError("%s has no point_estimates: the point estimate of an attribute pattern is the MAP pattern "
                                   "score() already returns (`pattern`); ML / MAP / WLE by Fisher scoring belong to a continuous "
                                   "latent (IrtEngine with x_feature <= 3)" % type(self).__name__)
+
+    def score_bifactor(self, *args, **kw):
+        raise NotImplementedError("%s has no score_bifactor: a bifactor / testlet structure is one of continuous dimensions "
+                                  "(IrtEngine with x_feature >= 2); the attribute patterns are scored by score()" % type(self).__name__)
+
+    bifactor_structure = score_bifactor
 
     def _group_refusals(self, covariates, impact):
         if covariates is not None or impact:

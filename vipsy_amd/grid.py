@@ -3,7 +3,8 @@ and CcdmEngine: score(), expected_counts() / item_fit(), fit_em(), plausible_val
 residual_sums() / local_dependence(), fit_sums() / person_fit() / item_msq(), group_counts() / dif(), sumscore_tables() /
 sx2() / score_table() and marginal_loglik().  On
 IrtEngine alone: fit_population(), the latent regression, and the score() / plausible_values() / expected_counts() conditioned on
-it (covariates=).  All of it runs
+it (covariates=), and score_bifactor(), the exact scores of a bifactor / testlet model with any x_feature >= 2 (its structure
+reader, two-axis grid and testlet layout are the bifactor_* functions below; the method itself is in engine.py).  All of it runs
 on the vx_grid_* entries of the C ABI (k_grid_*.hip; no reference counterpart) and works in buffers of its own: nothing a step
 reads is touched."""
 from collections import namedtuple
@@ -55,6 +56,117 @@ def score_grid(D, nodes=61, span=6.0):
     lw = -0.5 * (theta ** 2).sum(axis=1)
     lw = lw - (lw.max() + np.log(np.exp(lw - lw.max()).sum()))
     return np.ascontiguousarray(theta, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)
+
+
+BIFACTOR_MAX_GENERAL = 256       # GB_MAXGG (vipsy_amd/csrc/grid_plan.h): general nodes
+BIFACTOR_MAX_SPECIFIC = 32       # GB_MAXGH: specific nodes, the rows of one tile
+BIFACTOR_MAX_ITEMS = 1024        # GP_MAXJ
+BIFACTOR_MAX_IMAGE = 512 << 20   # GB_MAX_IMAGE: bytes of the operand image
+BIFACTOR_SLAB_BYTES = 256 << 20  # the permuted responses of one slab of persons at the most ...
+BIFACTOR_SLAB_PERSONS = 262144   # ... and its persons at the most (a multiple of 256)
+
+
+def bifactor_structure(free, a, model, general=0):
+    """The bifactor / testlet structure of an IRT model, read from its free mask on the host: `free` and `a` [D][J] (the mask of
+    the loadings and their values as they stand), `general` the index of the dimension every item may load on.  Every other
+    dimension is a SPECIFIC one, and an item may be free on one of them at the most.  Returns {"general", "specific_dims" int64
+    [S = D - 1] (ascending), "testlet" int64 [J] (the column of specific_dims the item loads on; -1: the general dimension alone)
+    and "sizes" int64 [S] (items a specific dimension; 0 where none)}.
+    NotImplementedError: irt_1pl or x_feature = 1 (no loadings to read a structure from).  ValueError: `general` out of range; an
+    item that is free on two specific dimensions (the first such item is named: the model is not a bifactor -- the triangular
+    default mask of x_feature >= 3 is refused here); a loading that is not free and not zero (a fixed non-zero loading on a
+    second specific dimension would break the factorisation silently; pass a0 = a_free, as the reference's CFA example does)."""
+    free = np.asarray(free) != 0
+    a = np.asarray(a, np.float64)
+    if model == "irt_1pl" or free.ndim != 2 or free.shape[0] < 2:
+        raise NotImplementedError("a bifactor structure needs irt_2pl / irt_3pl / irt_4pl with x_feature >= 2 (got %s with "
+                                  "x_feature = %d): there are no loadings to read it from"
+                                  % (model, free.shape[0] if free.ndim == 2 else 1))
+    D, J = free.shape
+    if a.shape != (D, J):
+        raise ValueError("free and a must both be [x_feature][items]")
+    if isinstance(general, bool) or not isinstance(general, (int, np.integer)) or not 0 <= general < D:
+        raise ValueError("general must be the index of a dimension, 0 .. %d" % (D - 1))
+    general = int(general)
+    specific = np.array([d for d in range(D) if d != general], np.int64)
+    fs = free[specific]                                                          # [S][J]
+    twice = np.flatnonzero(fs.sum(0) > 1)
+    if twice.size:
+        j = int(twice[0])
+        raise ValueError("item %d is free on the specific dimensions %s: not a bifactor / testlet model with general dimension %d "
+                         "(an item loads on the general dimension and on ONE specific dimension at the most; %d items do not)"
+                         % (j, [int(d) for d in specific[fs[:, j]]], general, twice.size))
+    fixed = np.argwhere(~free & (a != 0))
+    if fixed.size:
+        d, j = int(fixed[0, 0]), int(fixed[0, 1])
+        raise ValueError("item %d has the fixed loading %g on dimension %d: a loading that is not free must be 0 in a bifactor "
+                         "model (pass a0 = a_free); %d loadings are not" % (j, a[d, j], d, len(fixed)))
+    testlet = np.where(fs.any(0), fs.argmax(0), -1).astype(np.int64)
+    return {"general": general, "specific_dims": specific, "testlet": testlet,
+            "sizes": np.bincount(testlet[testlet >= 0], minlength=len(specific)).astype(np.int64)}
+
+
+def bifactor_grid(nodes=(61, 21), span=(6.0, 4.0)):
+    """The two axes of score_bifactor: nodes = (Gg, Gh) equally spaced points on [-span[0], span[0]] for the general dimension
+    and on [-span[1], span[1]] for every specific one, weights proportional to exp(-x^2 / 2) normalised to sum 1 an axis -- the
+    N(0, I) prior of the model.  Gh = 1: the single point u = 0 with weight 1.  Returns float32 (theta [Gg], logw [Gg], u [Gh],
+    logv [Gh]).  ValueError beyond 2 <= Gg <= 256, 1 <= Gh <= 32 or for a span that is not positive and finite;
+    NotImplementedError for explicit nodes (arrays in place of the counts)."""
+    if not isinstance(nodes, (tuple, list)) or len(nodes) != 2:
+        raise ValueError("nodes must be a pair (general nodes, specific nodes)")
+    if any(isinstance(v, (np.ndarray, torch.Tensor, list, tuple)) for v in nodes):
+        raise NotImplementedError("score_bifactor with explicit nodes is not built: nodes = (Gg, Gh) points on [-span, span]")
+    for name, v, lo, hi in (("general", nodes[0], 2, BIFACTOR_MAX_GENERAL), ("specific", nodes[1], 1, BIFACTOR_MAX_SPECIFIC)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("the %s nodes must be an integer in %d .. %d (got %r)" % (name, lo, hi, v))
+    if not isinstance(span, (tuple, list)) or len(span) != 2 or not all(
+            isinstance(s, (int, float, np.floating, np.integer)) and not isinstance(s, bool) and np.isfinite(s) and s > 0 for s in span):
+        raise ValueError("span must be a pair of positive finite numbers (general, specific)")
+    out = []
+    for n, s in zip(nodes, span):
+        p = np.linspace(-float(s), float(s), int(n)) if n > 1 else np.zeros(1)
+        lw = -0.5 * p * p
+        lw = lw - (lw.max() + np.log(np.exp(lw - lw.max()).sum()))
+        out += [np.ascontiguousarray(p, dtype=np.float32), np.ascontiguousarray(lw, dtype=np.float32)]
+    return tuple(out)
+
+
+def bifactor_plan(testlet, specific_dims, Gg):
+    """The testlet layout of the items and the operand image over it (vipsy_amd/csrc/k_grid_bifactor.hip): the testlets in the
+    order of specific_dims, those without items left out, then the items that load on the general dimension alone as one
+    pseudo-testlet; inside a testlet the items in their own order; every testlet padded to whole chunks of 16.  Returns `col`
+    int32 [16 KC] (the item in a slot; -1: padding), `sdim` int32 [16 KC] (its specific DIMENSION of the model; -1: none),
+    `tl_start` int32 [n_tl + 1] (chunk starts), `tl_column` int64 [n_tl] (the column of specific_dims behind a testlet; -1: the
+    pseudo-testlet), `KC` and `image_bytes` = Gg KC 4096.  The public API puts no constraint on the order of the items: score_bifactor
+    permutes the responses into this layout.  ValueError: more than 1 024 items, an image beyond 512 MB."""
+    testlet = np.asarray(testlet, np.int64).reshape(-1)
+    specific_dims = np.asarray(specific_dims, np.int64).reshape(-1)
+    J = int(testlet.shape[0])
+    if not 1 <= J <= BIFACTOR_MAX_ITEMS:
+        raise ValueError("score_bifactor takes 1 .. %d items (got %d)" % (BIFACTOR_MAX_ITEMS, J))
+    col, sdim, tl_start, tl_column = [], [], [0], []
+    for s in list(range(len(specific_dims))) + [-1]:
+        items = np.flatnonzero(testlet == s)
+        if items.size == 0:
+            continue
+        pad = -items.size % 16
+        col += items.tolist() + [-1] * pad
+        sdim += [int(specific_dims[s]) if s >= 0 else -1] * items.size + [-1] * pad
+        tl_start.append(len(col) // 16)
+        tl_column.append(s)
+    KC = len(col) // 16
+    image_bytes = int(Gg) * KC * 4 * 64 * 16
+    if image_bytes > BIFACTOR_MAX_IMAGE:
+        raise ValueError("the operand image of %d general nodes x %d item chunks is %d MB; score_bifactor takes 512 MB at the most "
+                         "(fewer general nodes)" % (Gg, KC, image_bytes >> 20))
+    return {"col": np.array(col, np.int32), "sdim": np.array(sdim, np.int32), "tl_start": np.array(tl_start, np.int32),
+            "tl_column": np.array(tl_column, np.int64), "KC": KC, "image_bytes": image_bytes}
+
+
+def bifactor_slab_persons(KC):
+    """Persons whose permuted responses ([persons][16 KC] bytes) score_bifactor holds at a time: 256 MB of them, 262 144 persons
+    at the most, a multiple of 256 and at least 256.  A person's result does not depend on the slab it falls into."""
+    return int(max(256, min(BIFACTOR_SLAB_PERSONS, BIFACTOR_SLAB_BYTES // (16 * int(KC)) // 256 * 256)))
 
 
 EM_PRIOR_ROWS = 6                # GM_ROWS (vipsy_amd/csrc/k_grid_mstep.hip): b, a_0 .. a_2, c_un, d_un

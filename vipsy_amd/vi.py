@@ -210,6 +210,22 @@ class BasePsy(object):
         VCCDM: attr_prob, pattern, loglik (CcdmEngine.score).  The other classes refuse."""
         return self.engine.score(self._score_data(data), **kw)
 
+    def score_bifactor(self, data=None, **kw):
+        """Exact grid scores of a bifactor / testlet model -- VIRT / VaeIRT, irt_2pl / irt_3pl / irt_4pl, any x_feature >= 2, with
+        a free mask (a_free, and a0 = a_free so that the loadings that are not free are zero) in which every item loads on the
+        `general` dimension and on one specific dimension at the most: loglik, eap_general, psd_general, node (persons,), and
+        with specific=True eap_specific, psd_specific (persons, x_feature - 1) and specific_dims (IrtEngine.score_bifactor:
+        rows, nodes=(61, 21), span=(6.0, 4.0), general=0, specific=False).  `data` None: the training data; with a `group` this
+        rank's shard, as score().  The work is that of one two-dimensional grid whatever x_feature is -- score() itself stops
+        at x_feature = 3.  The other classes refuse; covariates= is not built."""
+        return self.engine.score_bifactor(self._score_data(data), **kw)
+
+    def bifactor_structure(self, general=0):
+        """{"general", "specific_dims", "testlet" (per item: the column of specific_dims it loads on, -1: general only),
+        "sizes"} as read from the model's free mask on the host (IrtEngine.bifactor_structure); ValueError naming the first
+        item that is free on two specific dimensions, or whose fixed loading is not zero."""
+        return self.engine.bifactor_structure(general)
+
     def point_estimates(self, data=None, **kw):
         """Likelihood-based person scores of the persons in `data` (None: the training data; with a `group` this rank's shard, as
         score()), ready to print: Warm's weighted likelihood estimate (method="wle", the default: what PISA, TIMSS, ConQuest and
