@@ -492,6 +492,33 @@ int vx_grid_bifactor_specific(const uint8_t* y /*[nb][16 KC]*/, int64_t nb, int3
                               const void* img, const float* logv /*[Gh]*/, const float* u /*[Gh]*/, const float* loglik /*[nb]*/,
                               const float* fws, float* mean_s /*[n_tl][nb]*/, float* sd_s /*[n_tl][nb]*/, void* hip_stream);
 
+/* ---- Expected counts of a bifactor / testlet model (the Bock-Aitkin E-step of a marginal maximum-likelihood fit), in the notation
+ * above, with ll_is(g, h) the log-likelihood of testlet s at (coord[g], u[h]), loglik and fws (F) as vx_grid_bifactor left them:
+ *     post[i][g]      = exp(F[i][g] - loglik[i])                           r_is(g, h) = exp(logv[h] + ll_is(g, h) - m[i][s][g])
+ *     n1[j][g Gh + h] = sum_i [y_ij == 1] post[i][g] r_{i,s(j)}(g, h)       n0 likewise with [y_ij == 0]
+ *     mass[g]         = sum_i post[i][g]                                   mass_s[t][g Gh + h] = sum_i post[i][g] r_it(g, h)
+ * Given the general node the posterior of a testlet over (g, h) is a two-dimensional table and every item belongs to one testlet,
+ * so an item's counts live on the Gg x Gh grid of its own testlet whatever S is; an item of the pseudo-testlet has r = exp(logv[h]).
+ * y, the layout, tl_start / tl_start_dev, col (int32 [16 KC], device), img, logv as vx_grid_bifactor and vx_grid_table_bifactor
+ * take them.  n1, n0 are [J][Gg Gh] in the MODEL's item order (slot jp of the layout goes to item col[jp]; every item must hold
+ * one slot), mass_s [n_tl][Gg Gh] in the layout's testlet order, the pseudo-testlet included, or NULL.  accumulate = 0: the tables
+ * are written; 1: this call's sums are added to what they hold -- a caller that loops over slabs of persons gets their sum in
+ * person order.  255 enters neither table, 254 adds nothing, a person with no response adds their prior to mass and mass_s.
+ * m and r are formed with the arithmetic that formed F, so a person's weights sum to 1 to rounding.  The contraction over persons
+ * runs on v_mfma_f32_32x32x16_f16 (p 2^14 as an fp16 head and low term, fp32 accumulation), [y == 1] and [y == 0] of a chunk of
+ * 16 items in the two halves of one fragment.  Nothing of size [nb][Gg Gh] touches memory.  No float atomics: the partial tables
+ * of the person chunks go to slabs in `workspace` (vx_grid_bifactor_counts_workspace_floats(nb, KC, Gg, n_tl) floats, 16-byte
+ * aligned) and are added in ascending order; every sum has a fixed order and the same call gives the same bits.  The cut of the
+ * persons depends on (nb, Gg) alone: a testlet's tables do not depend on the other testlets of the layout except through F and
+ * loglik.  Limits as vx_grid_bifactor, accumulate in {0, 1}; VX_EINVAL beyond them and for NULL or misaligned pointers. */
+int64_t vx_grid_bifactor_counts_workspace_floats(int64_t nb, int32_t KC, int32_t Gg, int32_t n_tl);
+int vx_grid_bifactor_counts(const uint8_t* y /*[nb][16 KC]*/, int64_t nb, int32_t KC, int32_t Gg, int32_t Gh,
+                            const int32_t* tl_start /*[n_tl + 1], HOST*/, int32_t n_tl, const int32_t* tl_start_dev,
+                            const int32_t* col /*[16 KC], device*/, int32_t J, const void* img, const float* logv /*[Gh]*/,
+                            const float* loglik /*[nb]*/, const float* fws, int32_t accumulate, float* n1 /*[J][Gg Gh]*/,
+                            float* n0 /*[J][Gg Gh]*/, float* mass /*[Gg]*/, float* mass_s /*[n_tl][Gg Gh] or NULL*/,
+                            float* workspace, void* hip_stream);
+
 /* ---- Plausible values: draws of a person's node from the grid posterior p_i(g) ~ exp(logw[g] + ll[i][g]) of vx_grid_posterior
  * (same y, rows, nb, img, logw), by the Gumbel-max rule: node[i][m] = argmax_g (logw[g] + ll[i][g] + noise(r, g, m)), ties to the
  * lowest g.  No normalisation, no second pass, nothing of size [nb][G] touches memory, no workspace, no atomics.  The noise is

@@ -134,6 +134,9 @@ SIGNATURES = {
     # tl_start (HOST, int32 [n_tl + 1]) is a typed pointer: the entry reads it, and refuses it when null
     "vx_grid_bifactor": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P] + [_P] * 5 + [_P] * 4 + [_P, _P]),
     "vx_grid_bifactor_specific": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P] + [_P] * 5 + [_P, _P, _P]),
+    "vx_grid_bifactor_counts_workspace_floats": (_I64, [_I64, _I32, _I32, _I32]),
+    "vx_grid_bifactor_counts": (ctypes.c_int, [_P, _I64, _I32, _I32, _I32, ctypes.POINTER(_I32), _I32, _P, _P, _I32] + [_P] * 4
+                                + [_I32] + [_P] * 4 + [_P, _P]),
     "vx_grid_draw": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _U64, _I64, _I32, _I32, _I64, _P, _P]),
     "vx_grid_posterior_cond": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 4 + [_P] * 5 + [_P]),
     "vx_grid_draw_cond": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _I32] + [_P] * 4 + [_U64, _I64, _I32, _I32, _I64, _P, _P]),

@@ -211,6 +211,45 @@ inline bool gb_testlets_ok(const int32_t* tl_start, int n_tl, int KC) {
 // the workspace of specific = true: F, one float a person and general node, [units of 64 persons][Gg][64]
 inline int64_t gb_ws_floats(int64_t nb, int64_t Gg) { return ((nb + 63) / 64) * Gg * 64; }
 
+// ---- GbcPlan: vx_grid_bifactor_counts (k_grid_bifactor_counts.hip) -------------------------------------------------------
+#define GBC_CG 2                        // chunks of a testlet a workgroup keeps accumulators for
+#define GBC_NG 2                        // general nodes a workgroup (GB_NG)
+#define GBC_WAVES 4                     // waves a workgroup (GP_WAVES), one unit of 64 persons each at a time
+#define GBC_ROUND (64 * GBC_WAVES)      // persons a workgroup takes at a time
+#define GBC_MIN_ROUNDS 2                // rounds a chunk has before the persons are split further
+#define GBC_MAX_BLOCKS 256              // (node pairs x person chunks) of a launch, about; times the chunk groups = workgroups
+#define GBC_MIN_CHUNKS 4                // person chunks the many node pairs of a fine general axis still leave
+
+// The launch for (nb, KC, Gg, n_tl).  The cut of the persons looks at (nb, Gg) ALONE: a testlet's tables then do not depend on
+// which other testlets the layout holds.  The slab: [n1 | n0: [16 KC][Gg][32] | mass_s: [n_tl][Gg][32] | mass: [Gg]].
+struct GbcPlan {
+    int n_gpairs;                       // pairs of general nodes
+    int64_t n_units, units_per_chunk, n_chunks;      // units of 64 persons, in contiguous chunks of whole rounds
+    int64_t off_ms, off_mass, slab_len;
+};
+inline GbcPlan gbc_plan(int64_t nb, int KC, int Gg, int n_tl) {
+    GbcPlan p;
+    p.n_gpairs = (Gg + GBC_NG - 1) / GBC_NG;
+    p.n_units = (nb + 63) / 64;
+    const int64_t rounds = (p.n_units + GBC_WAVES - 1) / GBC_WAVES;
+    int64_t chunks = (rounds + GBC_MIN_ROUNDS - 1) / GBC_MIN_ROUNDS;
+    const int64_t cap = GBC_MAX_BLOCKS / p.n_gpairs > GBC_MIN_CHUNKS ? GBC_MAX_BLOCKS / p.n_gpairs : GBC_MIN_CHUNKS;
+    if (chunks > cap) chunks = cap;
+    const int64_t rounds_per_chunk = (rounds + chunks - 1) / chunks;
+    p.units_per_chunk = rounds_per_chunk * GBC_WAVES;
+    p.n_chunks = (rounds + rounds_per_chunk - 1) / rounds_per_chunk;
+    p.off_ms = (int64_t)2 * 16 * KC * Gg * 32;
+    p.off_mass = p.off_ms + (int64_t)n_tl * Gg * 32;
+    p.slab_len = p.off_mass + Gg;
+    return p;
+}
+// chunk groups of a layout: every testlet in groups of GBC_CG chunks, the last one short
+inline int gbc_groups(const int32_t* tl_start, int n_tl) {
+    int n = 0;
+    for (int t = 0; t < n_tl; ++t) n += (tl_start[t + 1] - tl_start[t] + GBC_CG - 1) / GBC_CG;
+    return n;
+}
+
 // ---- SsPlan: vx_sumscore_model (k_sumscore.hip) --------------------------------------------------------------------------
 #define SS_TARGET_WAVES 8192            // waves of the leave-one-out launch where the nodes allow: 8 a SIMD on 256 CUs
 

@@ -41,6 +41,7 @@
 #include "k_grid_cond.hip"
 #include "k_grid_counts_cond.hip"
 #include "k_grid_bifactor.hip"
+#include "k_grid_bifactor_counts.hip"
 #include "k_sumscore.hip"
 #include "k_pair_tables.hip"
 
@@ -2363,6 +2364,36 @@ int vx_grid_bifactor_specific(const uint8_t* y, int64_t nb, int32_t KC, int32_t 
     if (!gb_shape_ok(Gg, Gh, KC, n_tl, nb, GRID_MAX_PERSONS) || !gb_testlets_ok(tl_start, (int)n_tl, (int)KC)) return VX_EINVAL;
     hipLaunchKernelGGL(k_grid_bifactor_spec, dim3(grid_unit_blocks(nb)), dim3(GP_THREADS), 0, (hipStream_t)hs, y, nb, (int)KC,
                        (int)Gg, (int)Gh, tl_start_dev, (int)n_tl, (const uint4*)img, logv, u, loglik, fws, mean_s, sd_s);
+    VX_CHECK_LAUNCH();
+    return VX_OK;
+}
+
+// Expected counts of a bifactor model (k_grid_bifactor_counts.hip): one kernel over (chunk groups x node pairs x person chunks),
+// then the chunks' slabs added in ascending order and scattered to the model's item order
+int64_t vx_grid_bifactor_counts_workspace_floats(int64_t nb, int32_t KC, int32_t Gg, int32_t n_tl) {
+    if (!gb_shape_ok(Gg, 1, KC, n_tl, nb, GRID_MAX_PERSONS)) return VX_EINVAL;
+    const GbcPlan p = gbc_plan(nb, (int)KC, (int)Gg, (int)n_tl);
+    return p.n_chunks * p.slab_len;
+}
+
+int vx_grid_bifactor_counts(const uint8_t* y, int64_t nb, int32_t KC, int32_t Gg, int32_t Gh, const int32_t* tl_start, int32_t n_tl,
+                            const int32_t* tl_start_dev, const int32_t* col, int32_t J, const void* img, const float* logv,
+                            const float* loglik, const float* fws, int32_t accumulate, float* n1, float* n0, float* mass,
+                            float* mass_s, float* workspace, void* hs) {
+    if (!y || !tl_start_dev || !col || !img || !aligned16(img) || !logv || !loglik || !fws || !n1 || !n0 || !mass || !workspace ||
+        !aligned16(workspace))
+        return VX_EINVAL;
+    if (J < 1 || J > GP_MAXJ || (accumulate != 0 && accumulate != 1)) return VX_EINVAL;
+    if (!gb_shape_ok(Gg, Gh, KC, n_tl, nb, GRID_MAX_PERSONS) || !gb_testlets_ok(tl_start, (int)n_tl, (int)KC)) return VX_EINVAL;
+    const GbcPlan p = gbc_plan(nb, (int)KC, (int)Gg, (int)n_tl);
+    const int n_groups = gbc_groups(tl_start, (int)n_tl);
+    hipStream_t st = (hipStream_t)hs;
+    hipLaunchKernelGGL(k_grid_bifactor_counts, dim3((unsigned)n_groups, (unsigned)p.n_gpairs, (unsigned)p.n_chunks), dim3(GP_THREADS), 0,
+                       st, y, nb, (int)KC, (int)Gg, (int)Gh, tl_start_dev, (int)n_tl, (const uint4*)img, logv, loglik, fws,
+                       p.units_per_chunk, workspace, p.slab_len);
+    VX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_grid_bifactor_counts_reduce, dim3(grid_1d(p.slab_len, 256)), dim3(256), 0, st, workspace, p.n_chunks,
+                       p.slab_len, (int)KC, (int)Gg, (int)Gh, (int)n_tl, col, (int)J, (int)accumulate, n1, n0, mass, mass_s);
     VX_CHECK_LAUNCH();
     return VX_OK;
 }

@@ -20,6 +20,8 @@ from .grid import (EM_MAX_NEWTON, PV_MAX_DRAWS, PV_STREAM, SCORE_MAX_DIMS, SCORE
 from .grid import (POINT_AT_BOUND, POINT_CONVERGED, POINT_EMPTY, POINT_MAX_ITER, POINT_MAX_ITERS, POINT_METHODS,  # noqa: F401
                    POINT_SINGULAR, POINT_STATUS, POINT_STEP_CAP, point_estimates_host)
 from .grid import bifactor_grid, bifactor_plan, bifactor_slab_persons, bifactor_structure  # noqa: F401
+from .grid import (BIFACTOR_EM_NODES, BifactorCall, bifactor_em_index, bifactor_em_prior, bifactor_gather,  # noqa: F401
+                   bifactor_scatter)
 
 MODEL_CODE = {"irt_1pl": 1, "irt_2pl": 2, "irt_3pl": 3, "irt_4pl": 4}       # vi.py:538-543
 LOSS_RING = 64                                                               # VX_LOSS_RING (include/vipsy_amd.h)
@@ -319,6 +321,19 @@ class HipBackend(object):
                                               _hip.ptr(tl_start_dev), _hip.ptr(img), _hip.ptr(logv), _hip.ptr(u), _hip.ptr(loglik),
                                               _hip.ptr(fws), _hip.ptr(mean_s), _hip.ptr(sd_s), _hip.stream_ptr())
         _hip.check(rc, "vx_grid_bifactor_specific")
+
+    def grid_bifactor_counts_workspace(self, nb, KC, Gg, n_tl):
+        return self._size("vx_grid_bifactor_counts_workspace_floats", nb, KC, Gg, n_tl)
+
+    def grid_bifactor_counts(self, y, nb, KC, Gg, tl_start, tl_start_dev, col, J, img, logv, loglik, fws, accumulate, n1, n0, mass,
+                             mass_s, ws):
+        """n1, n0 [J][Gg Gh], mass [Gg], mass_s [n_tl][Gg Gh] or None; accumulate: add to what the tables hold."""
+        tl, tlp = self._tl_start(tl_start)
+        rc = self.L.vx_grid_bifactor_counts(_hip.ptr(y), nb, int(KC), int(Gg), int(logv.numel()), tlp, int(tl.size) - 1,
+                                            _hip.ptr(tl_start_dev), _hip.ptr(col), int(J), _hip.ptr(img), _hip.ptr(logv),
+                                            _hip.ptr(loglik), _hip.ptr(fws), 1 if accumulate else 0, _hip.ptr(n1), _hip.ptr(n0),
+                                            _hip.ptr(mass), _hip.ptr(mass_s), _hip.ptr(ws), _hip.stream_ptr())
+        _hip.check(rc, "vx_grid_bifactor_counts")
 
     def grid_draw(self, y, rows, nb, J, G, img, logw, seed, row_offset, draw0, ndraws, stride, node):
         rc = self.L.vx_grid_draw(_hip.ptr(y), _hip.ptr(rows), nb, J, G, _hip.ptr(img), _hip.ptr(logw), int(seed), int(row_offset),
@@ -774,6 +789,7 @@ class _EngineBase(object):
     sumscore_tables = sx2 = score_table = _no_grid
     point_estimates = _no_grid
     score_bifactor = bifactor_structure = _no_grid
+    expected_counts_bifactor = fit_em_bifactor = _no_grid
 
     def _gather_pp(self, rows, nb):
         """loc/raw (and their gradient targets) of the batch rows of a per-person guide."""
@@ -1739,53 +1755,188 @@ class IrtEngine(GridMixin, _EngineBase):
         if covariates is not None:
             raise NotImplementedError("score_bifactor with covariates=: the latent regression of fit_population() is built for "
                                       "x_feature <= 3 and the tensor-product grid of score()")
-        theta_np, logw_np, u_np, logv_np = bifactor_grid(nodes, span)
-        st = self.bifactor_structure(general)
-        plan = bifactor_plan(st["testlet"], st["specific_dims"], theta_np.shape[0])
-        J, Dm, KC, S = self.J_items, self.D_model, plan["KC"], len(st["specific_dims"])
-        y, rows = self._score_inputs(y_u8, rows, J)
-        n = int(y.shape[0]) if rows is None else int(rows.numel())
-        dev = self.dev
-        theta, logw, u, logv = (torch.from_numpy(t).to(dev) for t in (theta_np, logw_np, u_np, logv_np))
-        col, sdim, tl_dev = (torch.from_numpy(plan[k]).to(dev) for k in ("col", "sdim", "tl_start"))
-        flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()      # noqa: E731
-        cfg = self.be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
-        img = torch.empty(self.be.grid_bifactor_image_bytes(len(theta_np), KC), dtype=torch.uint8, device=dev)
-        self.be.grid_table_bifactor(cfg, theta, u, st["general"], col, sdim, KC, self.unconstrained("a").contiguous(), flat("b"),
-                                    flat("c") if self.model in ("irt_3pl", "irt_4pl") else None,
-                                    flat("d") if self.model == "irt_4pl" else None, img)
+        bf = self._bifactor_call(y_u8, rows, nodes, span, general)
+        bf.fill()
+        n, S, Gg, KC, plan, dev = bf.n, len(bf.st["specific_dims"]), bf.Gg, bf.KC, bf.plan, self.dev
         f32 = dict(dtype=torch.float32, device=dev)
         out = {"loglik": torch.empty(n, **f32), "eap_general": torch.empty(n, **f32), "psd_general": torch.empty(n, **f32),
                "node": torch.empty(n, dtype=torch.int32, device=dev)}
         if specific:
             # a dimension without items: the moments of the grid prior
-            v = np.exp(logv_np.astype(np.float64))
+            v = np.exp(bf.logv_np.astype(np.float64))
             v = v / v.sum()
-            m1 = float((v * u_np).sum())
-            sd0 = float(np.sqrt(max((v * u_np.astype(np.float64) ** 2).sum() - m1 * m1, 0.0)))
+            m1 = float((v * bf.u_np).sum())
+            sd0 = float(np.sqrt(max((v * bf.u_np.astype(np.float64) ** 2).sum() - m1 * m1, 0.0)))
             out["eap_specific"] = torch.full((n, S), m1, **f32)
             out["psd_specific"] = torch.full((n, S), sd0, **f32)
-            out["specific_dims"] = st["specific_dims"]
+            out["specific_dims"] = bf.st["specific_dims"]
             real = np.flatnonzero(plan["tl_column"] >= 0)
             real_t, cols_t = torch.from_numpy(real).to(dev), torch.from_numpy(plan["tl_column"][real]).to(dev)
-        # slot -> column of the responses, the padding slots to one more column of 254 ("outside the problem")
-        src = torch.where(col >= 0, col, torch.full_like(col, J)).long()
-        slab = bifactor_slab_persons(KC)
-        for s0 in range(0, n, slab):
-            s1 = min(n, s0 + slab)
-            ys = y[s0:s1] if rows is None else y[rows[s0:s1]]
-            yp = torch.cat([ys, torch.full((s1 - s0, 1), 254, dtype=torch.uint8, device=dev)], 1)[:, src].contiguous()
-            fws = torch.empty(self.be.grid_bifactor_workspace(s1 - s0, len(theta_np)), **f32) if specific else None
-            self.be.grid_bifactor(yp, s1 - s0, KC, plan["tl_start"], tl_dev, img, logw, theta, logv, u, out["loglik"][s0:s1],
-                                  out["eap_general"][s0:s1], out["psd_general"][s0:s1], out["node"][s0:s1], fws)
+        for s0, s1, yp in bf.slabs():
+            fws = torch.empty(self.be.grid_bifactor_workspace(s1 - s0, Gg), **f32) if specific else None
+            self.be.grid_bifactor(yp, s1 - s0, KC, plan["tl_start"], bf.tl_dev, bf.img, bf.logw, bf.theta, bf.logv, bf.u,
+                                  out["loglik"][s0:s1], out["eap_general"][s0:s1], out["psd_general"][s0:s1], out["node"][s0:s1], fws)
             if specific:
                 ms = torch.empty(len(plan["tl_column"]), s1 - s0, **f32)
                 ss = torch.empty_like(ms)
-                self.be.grid_bifactor_specific(yp, s1 - s0, KC, len(theta_np), plan["tl_start"], tl_dev, img, logv, u,
+                self.be.grid_bifactor_specific(yp, s1 - s0, KC, Gg, plan["tl_start"], bf.tl_dev, bf.img, bf.logv, bf.u,
                                                out["loglik"][s0:s1], fws, ms, ss)
                 out["eap_specific"][s0:s1, cols_t] = ms[real_t].t()
                 out["psd_specific"][s0:s1, cols_t] = ss[real_t].t()
         return out
+
+    def _bifactor_call(self, y_u8, rows, nodes, span, general, params=None):
+        """What score_bifactor, expected_counts_bifactor and fit_em_bifactor share (grid.BifactorCall): the two axes, the structure
+        and the testlet layout, the responses and rows, the operand image (bf.fill() tabulates `params` into it: compact a
+        [D_model][J_items], b, c_un, d_un or None -- by default the leaves as they stand) and bf.slabs(), the responses permuted
+        into the layout, grid.bifactor_slab_persons() persons at a time."""
+        theta_np, logw_np, u_np, logv_np = bifactor_grid(nodes, span)
+        st = self.bifactor_structure(general)
+        plan = bifactor_plan(st["testlet"], st["specific_dims"], theta_np.shape[0])
+        J, Dm, KC = self.J_items, self.D_model, plan["KC"]
+        y, rows = self._score_inputs(y_u8, rows, J)
+        n = int(y.shape[0]) if rows is None else int(rows.numel())
+        dev = self.dev
+        theta, logw, u, logv = (torch.from_numpy(t).to(dev) for t in (theta_np, logw_np, u_np, logv_np))
+        col, sdim, tl_dev = (torch.from_numpy(plan[k]).to(dev) for k in ("col", "sdim", "tl_start"))
+        if params is None:
+            flat = lambda name: self.unconstrained(name).reshape(-1).contiguous()      # noqa: E731
+            params = (self.unconstrained("a").contiguous(), flat("b"), flat("c") if self.model in ("irt_3pl", "irt_4pl") else None,
+                      flat("d") if self.model == "irt_4pl" else None)
+        cfg = self.be.cfg(self.model, Dm, J, 0, self.Dc, 1.0, 0, 0, 0)
+        img = torch.empty(self.be.grid_bifactor_image_bytes(len(theta_np), KC), dtype=torch.uint8, device=dev)
+        # slot -> column of the responses, the padding slots to one more column of 254 ("outside the problem")
+        src = torch.where(col >= 0, col, torch.full_like(col, J)).long()
+        slab = bifactor_slab_persons(KC)
+
+        def fill():
+            self.be.grid_table_bifactor(cfg, theta, u, st["general"], col, sdim, KC, *params, img)
+
+        def slabs():
+            for s0 in range(0, n, slab):
+                s1 = min(n, s0 + slab)
+                ys = y[s0:s1] if rows is None else y[rows[s0:s1]]
+                yield s0, s1, torch.cat([ys, torch.full((s1 - s0, 1), 254, dtype=torch.uint8, device=dev)], 1)[:, src].contiguous()
+
+        return BifactorCall(st=st, plan=plan, n=n, J=J, KC=KC, Gg=len(theta_np), Gh=len(u_np), theta=theta, logw=logw, u=u, logv=logv,
+                            u_np=u_np, logv_np=logv_np, col=col, tl_dev=tl_dev, img=img, fill=fill, slabs=slabs)
+
+    def _bifactor_estep(self, bf, buf):
+        """One E-step over a filled BifactorCall into the buffers of _bifactor_buffers: per slab of persons vx_grid_bifactor with
+        fws, then vx_grid_bifactor_counts (the first slab writes the tables, the others add to them, in person order); the
+        float32 device sum of loglik, as _em_loop takes it, into buf["total"][0]."""
+        be, plan = self.be, bf.plan
+        for k, (s0, s1, yp) in enumerate(bf.slabs()):
+            nb = s1 - s0
+            fws = buf["fws"][:be.grid_bifactor_workspace(nb, bf.Gg)]
+            ll = buf["loglik"][s0:s1]
+            be.grid_bifactor(yp, nb, bf.KC, plan["tl_start"], bf.tl_dev, bf.img, bf.logw, bf.theta, bf.logv, bf.u, ll,
+                             buf["mean"][s0:s1], buf["sd"][s0:s1], buf["node"][s0:s1], fws)
+            ws = buf["ws"][:be.grid_bifactor_counts_workspace(nb, bf.KC, bf.Gg, len(plan["tl_column"]))]
+            be.grid_bifactor_counts(yp, nb, bf.KC, bf.Gg, plan["tl_start"], bf.tl_dev, bf.col, bf.J, bf.img, bf.logv, ll, fws, k > 0,
+                                    buf["n1"], buf["n0"], buf["mass"], buf["mass_s"], ws)
+        be.sum_into(buf["loglik"], bf.n, 1.0, buf["total"][:1], buf["sum_ws"])
+
+    def _bifactor_buffers(self, bf):
+        """Every buffer of _bifactor_estep, made once: sized for the largest slab of persons (the first)."""
+        be = self.be
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        nb, n_tl, GG = min(bf.n, bifactor_slab_persons(bf.KC)), len(bf.plan["tl_column"]), bf.Gg * bf.Gh
+        return {"loglik": torch.empty(bf.n, **f32), "mean": torch.empty(bf.n, **f32), "sd": torch.empty(bf.n, **f32),
+                "node": torch.empty(bf.n, dtype=torch.int32, device=self.dev),
+                "fws": torch.empty(be.grid_bifactor_workspace(nb, bf.Gg), **f32),
+                "ws": torch.empty(be.grid_bifactor_counts_workspace(nb, bf.KC, bf.Gg, n_tl), **f32),
+                "n1": torch.empty(bf.J, GG, **f32), "n0": torch.empty(bf.J, GG, **f32), "mass": torch.empty(bf.Gg, **f32),
+                "mass_s": torch.empty(n_tl, GG, **f32), "total": torch.zeros(2, **f32), "sum_ws": torch.empty(1024, **f32)}
+
+    def expected_counts_bifactor(self, y_u8=None, rows=None, nodes=(41, 21), span=(6.0, 4.0), general=0):
+        """The expected-count tables of a bifactor / testlet model (the Bock-Aitkin E-step over the grid of score_bifactor): given
+        the general node the posterior of a testlet over (theta_g, u_h) is a two-dimensional table and every item belongs to one
+        testlet, so an item's counts live on the Gg x Gh grid of its own testlet whatever x_feature is.  Returns device tensors
+        `n1`, `n0` [J][Gg][Gh] = the posterior mass at (general node g, node h of the item's own specific dimension) of the
+        persons who answered item j correctly / wrongly (an item that loads on the general dimension alone: post(g) v_h), `prob`
+        [J][Gg][Gh] = P(y_j = 1 | theta_g, u_h) as the operand image holds it, `mass` [Gg] the general marginal posterior mass,
+        `mass_specific` [S][Gg][Gh] the joint mass of (theta, u_s) by column of specific_dims (a dimension without items: the grid
+        prior times `mass`), `loglik` (the float32 device sum of the persons' marginal log-likelihoods) and `theta`, `logw`,
+        `u`, `logv`, the axes.  Inputs, limits and refusals as score_bifactor; one rank only.  Deterministic: the same call
+        gives the same bits (vx_grid_bifactor_counts)."""
+        self._one_rank_only("expected_counts_bifactor over a process group: the tables are the sums over the local shard's "
+                            "persons and the cross-rank sum is not built")
+        bf = self._bifactor_call(y_u8, rows, nodes, span, general)
+        bf.fill()
+        buf = self._bifactor_buffers(bf)
+        self._bifactor_estep(bf, buf)
+        J, Gg, Gh, S, plan = bf.J, bf.Gg, bf.Gh, len(bf.st["specific_dims"]), bf.plan
+        # P(y = 1) out of the image: the general node in the place of the node tile, h in the place of the node in it, by slot
+        slot = np.empty(J, np.int64)
+        slot[plan["col"][plan["col"] >= 0]] = np.flatnonzero(plan["col"] >= 0)
+        prob = grid_image_prob(bf.img, 16 * bf.KC, 32 * Gg).view(16 * bf.KC, Gg, 32)[torch.from_numpy(slot).to(self.dev)][:, :, :Gh]
+        v = torch.exp(bf.logv.to(torch.float64))
+        mass_specific = (buf["mass"].to(torch.float64)[None, :, None] * v[None, None, :]).to(torch.float32).repeat(S, 1, 1)
+        real = np.flatnonzero(plan["tl_column"] >= 0)
+        if real.size:
+            mass_specific[torch.from_numpy(plan["tl_column"][real]).to(self.dev)] = buf["mass_s"].view(-1, Gg, Gh)[
+                torch.from_numpy(real).to(self.dev)]
+        return {"n1": buf["n1"].view(J, Gg, Gh), "n0": buf["n0"].view(J, Gg, Gh), "prob": prob.contiguous(), "mass": buf["mass"],
+                "mass_specific": mass_specific, "loglik": buf["total"][0].clone(), "theta": bf.theta, "logw": bf.logw, "u": bf.u,
+                "logv": bf.logv}
+
+    def fit_em_bifactor(self, max_iter=100, tol=1e-6, newton=4, nodes=(41, 21), span=(6.0, 4.0), general=0, prior=None,
+                        progress=False):
+        """Marginal maximum likelihood of a bifactor / testlet model (bifactor_structure(general)), any x_feature >= 2, by
+        Bock-Aitkin EM over the grid of score_bifactor: each iteration tabulates the items as they stand (vx_grid_table_bifactor),
+        scores the training responses (vx_grid_bifactor), takes the expected counts of every item on the Gg x Gh grid of its
+        own testlet (vx_grid_bifactor_counts) and refits the item to them by `newton` Newton steps of fit_em's M-step with TWO
+        dimensions -- the general loading and the item's own specific loading (vx_grid_mstep_irt; with `prior`
+        vx_grid_mstep_irt_map) -- so nodes[0] * nodes[1] <= 1024, the M-step's node limit.  Stopping rule, return ({"loglik",
+        "iterations", "converged"}, with `prior` also "logpost"), and what is left alone (the guide, Adam's state, the step
+        count) as fit_em; loglik[0] is the sum of score_bifactor(nodes=, span=)["loglik"] before the call.  The loadings follow
+        the engine's free mask; the specific rows of the other testlets stay 0.
+        prior: fit_em's (irt_3pl / irt_4pl need it, with fit_em's rules); a prior on "a" shaped like the leaf is gathered like
+        the loadings.  A testlet of ONE item has no identified specific loading: ValueError unless prior["a"] has a finite sd
+        on it.  One rank only."""
+        self._em_refusals(max_iter, newton)
+        st = self.bifactor_structure(general)
+        if prior is None and self.model != "irt_2pl":
+            raise NotImplementedError("fit_em_bifactor for %s: %s" % (self.model, self._UNPENALISED_ONLY))
+        Gg, Gh = (len(v) for v in bifactor_grid(nodes, span)[0::2])
+        if Gg * Gh > BIFACTOR_EM_NODES:
+            raise ValueError("fit_em_bifactor takes nodes[0] * nodes[1] <= %d, the node limit of the M-step (got %d x %d = %d); "
+                             "(41, 21) is the default" % (BIFACTOR_EM_NODES, Gg, Gh, Gg * Gh))
+        J, Dm, dev = self.J_items, self.D_model, self.dev
+        sd_np, has_np = bifactor_em_index(st)
+        pr_np = None if prior is None else bifactor_em_prior(prior, self.model, Dm, J, st["general"], sd_np, has_np)
+        for s in np.flatnonzero(st["sizes"] == 1):
+            j = int(np.flatnonzero(st["testlet"] == s)[0])
+            if pr_np is None or not pr_np[1, 2, j] > 0:
+                raise ValueError("dimension %d has ONE item (item %d): a testlet of one item has no identified specific loading -- "
+                                 "free the item from it, or pass prior={'a': (mean, sd)} with a finite sd"
+                                 % (int(st["specific_dims"][s]), j))
+        a = self.unconstrained("a").contiguous().clone()
+        b = self.unconstrained("b").reshape(-1).contiguous().clone()
+        c = self.unconstrained("c").reshape(-1).contiguous().clone() if self.model in ("irt_3pl", "irt_4pl") else None
+        d = self.unconstrained("d").reshape(-1).contiguous().clone() if self.model == "irt_4pl" else None
+        sd, has = torch.from_numpy(sd_np).to(dev), torch.from_numpy(has_np).to(dev)
+        free2 = bifactor_gather(self.unconstrained("a", self.free).contiguous(), st["general"], sd, has)
+        pr = None if pr_np is None else torch.from_numpy(pr_np).to(dev)
+        lprior = None if prior is None else torch.zeros(J, dtype=torch.float32, device=dev)
+        bf = self._bifactor_call(None, None, nodes, span, general, params=(a, b, c, d))
+        buf = self._bifactor_buffers(bf)
+        theta2 = torch.stack([bf.theta[:, None].expand(Gg, Gh), bf.u[None, :].expand(Gg, Gh)], 2).reshape(Gg * Gh, 2).contiguous()
+        cfg2 = self.be.cfg(self.model, 2, J, 0, self.Dc, 1.0, 0, 0, 0)
+
+        def iteration():
+            bf.fill()
+            self._bifactor_estep(bf, buf)
+            a2 = bifactor_gather(a, st["general"], sd, has)
+            if prior is None:
+                self.be.grid_mstep_irt(cfg2, theta2, Gg * Gh, buf["n1"], buf["n0"], free2, a2, b, newton)
+            else:
+                self.be.grid_mstep_irt_map(cfg2, theta2, Gg * Gh, buf["n1"], buf["n0"], free2, a2, b, c, d, pr, newton, lprior)
+            bifactor_scatter(a, a2, st["general"], sd, has)
+
+        leaves = {k: v for k, v in (("a", a), ("b", b), ("c", c), ("d", d)) if v is not None}
+        return self._em_history(iteration, buf["total"], buf["sum_ws"], leaves, max_iter, tol, progress, lprior)
 
     def _population_call(self, y_u8, rows, nodes, span, covariates):
         """The GridCall of a conditioned score: the nodes of score() with the log-weights of engine.population's Sigma, the tilt
@@ -2565,7 +2716,7 @@ class CcdmEngine(GridMixin, _EngineBase):
         raise NotImplementedError("%s has no score_bifactor: a bifactor / testlet structure is one of continuous dimensions "
                                   "(IrtEngine with x_feature >= 2); the attribute patterns are scored by score()" % type(self).__name__)
 
-    bifactor_structure = score_bifactor
+    bifactor_structure = expected_counts_bifactor = fit_em_bifactor = score_bifactor
 
     def _group_refusals(self, covariates, impact):
         if covariates is not None or impact:

@@ -169,6 +169,64 @@ def bifactor_slab_persons(KC):
     return int(max(256, min(BIFACTOR_SLAB_PERSONS, BIFACTOR_SLAB_BYTES // (16 * int(KC)) // 256 * 256)))
 
 
+class BifactorCall(namedtuple("BifactorCall", "st plan n J KC Gg Gh theta logw u logv u_np logv_np col tl_dev img fill slabs")):
+    """What one call of the bifactor family works on (IrtEngine._bifactor_call): the structure `st`, the layout `plan`, n, J, KC,
+    Gg, Gh, the axes on the device (theta, logw, u, logv) and on the host (u_np, logv_np), col and tl_dev (plan["col"] /
+    plan["tl_start"] on the device), the operand image `img`, fill() (tabulate the parameters into it) and slabs() (yields s0, s1
+    and the responses of the persons s0 .. s1 - 1 in the testlet layout)."""
+    __slots__ = ()
+
+
+BIFACTOR_EM_NODES = 1024         # GP_MAXG: nodes of the M-step (vipsy_amd/csrc/k_grid_mstep.hip), Gg Gh here
+
+
+def bifactor_em_index(st):
+    """The rows of the two-dimensional M-step of fit_em_bifactor, from bifactor_structure(): (`sd` int64 [J], the model dimension
+    of the item's specific loading -- the general dimension, as a placeholder, for an item that has none; `has` bool [J], whether
+    it has one)."""
+    testlet = np.asarray(st["testlet"], np.int64)
+    has = testlet >= 0
+    sd = np.where(has, np.asarray(st["specific_dims"], np.int64)[np.where(has, testlet, 0)], int(st["general"]))
+    return sd.astype(np.int64), has
+
+
+def bifactor_gather(a, general, sd, has):
+    """[D][J] (loadings, their free mask) -> [2][J]: row 0 the general dimension's, row 1 the item's own specific dimension's, 0
+    where it has none.  torch, on a's device; sd int64 [J] and has bool [J] (bifactor_em_index) on it as well."""
+    j = torch.arange(a.shape[1], device=a.device)
+    return torch.stack([a[general], torch.where(has, a[sd, j], torch.zeros_like(a[general]))]).contiguous()
+
+
+def bifactor_scatter(a, a2, general, sd, has):
+    """bifactor_gather undone, in place: a2 [2][J] back into the two rows of a [D][J] it came from; nothing else of a is written
+    (the specific rows of the other testlets stay as they are: 0)."""
+    j = torch.arange(a.shape[1], device=a.device)
+    a[general] = a2[0]
+    a[sd[has], j[has]] = a2[1][has]
+    return a
+
+
+def bifactor_em_prior(prior, model, D, J, general, sd, has):
+    """fit_em_bifactor's `prior` as the two-dimensional M-step takes it (em_prior with D = 2, whose rules and error texts hold): a
+    prior on "a" -- (mean, sd), each a scalar or shaped like the leaf, [D][J] -- is gathered like the loadings, row 1 of
+    em_prior's layout from the general dimension and row 2 from the item's own specific dimension (no prior, sd = inf, where it
+    has none)."""
+    if isinstance(prior, dict) and "a" in prior and isinstance(prior["a"], (tuple, list)) and len(prior["a"]) == 2:
+        pair = []
+        for what, v, none in (("mean", prior["a"][0], 0.0), ("sd", prior["a"][1], np.inf)):
+            try:
+                v = np.asarray(v, np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("prior['a']: %s must be a number or an array shaped like the leaf" % what)
+            if v.shape not in ((), (D, J)):
+                raise ValueError("prior['a']: %s must be a scalar or shaped like the leaf, %s (got %s)" % (what, (D, J), v.shape))
+            if v.shape == (D, J):
+                v = np.stack([v[general], np.where(has, v[sd, np.arange(J)], none)])
+            pair.append(v)
+        prior = dict(prior, a=tuple(pair))
+    return em_prior(prior, model, 2, J)
+
+
 EM_PRIOR_ROWS = 6                # GM_ROWS (vipsy_amd/csrc/k_grid_mstep.hip): b, a_0 .. a_2, c_un, d_un
 EM_PRIOR_KEYS = {"irt_1pl": ("b",), "irt_2pl": ("a", "b"), "irt_3pl": ("a", "b", "c"), "irt_4pl": ("a", "b", "c", "d")}
 
@@ -1112,6 +1170,21 @@ class GridMixin(object):
         n1, n0, mass = torch.empty(J, G, **f32), torch.empty(J, G, **f32), torch.empty(G, **f32)
         ws = torch.empty(be.grid_counts_workspace(n, J, G), **f32)
         total, sum_ws = torch.zeros(2, **f32), torch.empty(1024, **f32)      # vx_sum_workspace_floats(); not the step's
+
+        def iteration():
+            call.fill_tables(img)
+            be.grid_posterior(y, None, n, J, G, D, img, logw, theta, loglik, mean, sd, node)
+            be.sum_into(loglik, n, 1.0, total[:1], sum_ws)
+            be.grid_counts(y, None, n, J, G, img, logw, loglik, n1, n0, mass, ws)
+            mstep(n1, n0)
+
+        return self._em_history(iteration, total, sum_ws, leaves, max_iter, tol, progress, lprior)
+
+    def _em_history(self, iteration, total, sum_ws, leaves, max_iter, tol, progress, lprior=None):
+        """What every EM of the family does around its own E- and M-step: iteration() queues one of them on the caller's compact
+        copies and leaves the float32 sum of loglik in total[0]; here the log prior's sum into total[1] (lprior), the write-back
+        of the copies into the leaves ({name: copy}), the one host sync an iteration, the histories and the stopping rule."""
+        be = self.be
         bar = None
         if progress:
             try:
@@ -1121,13 +1194,9 @@ class GridMixin(object):
                 bar = None
         liks, hist, converged = [], [], False
         for _ in range(max_iter):
-            call.fill_tables(img)
-            be.grid_posterior(y, None, n, J, G, D, img, logw, theta, loglik, mean, sd, node)
-            be.sum_into(loglik, n, 1.0, total[:1], sum_ws)
-            be.grid_counts(y, None, n, J, G, img, logw, loglik, n1, n0, mass, ws)
-            mstep(n1, n0)
+            iteration()
             if lprior is not None:
-                be.sum_into(lprior, J, 1.0, total[1:], sum_ws)
+                be.sum_into(lprior, int(lprior.numel()), 1.0, total[1:], sum_ws)
             for name, t in leaves.items():
                 leaf = self.unconstrained(name)
                 leaf.copy_(t.reshape(leaf.shape))

@@ -220,6 +220,32 @@ class BasePsy(object):
         at x_feature = 3.  The other classes refuse; covariates= is not built."""
         return self.engine.score_bifactor(self._score_data(data), **kw)
 
+    def expected_counts_bifactor(self, data=None, **kw):
+        """The expected-count tables of a bifactor / testlet model over the grid of score_bifactor() -- models and structure as
+        there: device tensors n1, n0, prob [items][Gg][Gh] (every item on the grid of the general dimension and ITS OWN specific
+        dimension), mass [Gg], mass_specific [x_feature - 1][Gg][Gh], loglik (the sum) and the axes theta, logw, u, logv
+        (IrtEngine.expected_counts_bifactor: rows, nodes=(41, 21), span=(6.0, 4.0), general=0).  `data` None: the training
+        data.  One rank only; the other classes refuse."""
+        if self.world > 1:
+            raise NotImplementedError("expected_counts_bifactor with a group of %d ranks: the tables are the sums over the local "
+                                      "shard's persons; the cross-rank sum is not built" % self.world)
+        return self.engine.expected_counts_bifactor(self._score_data(data), **kw)
+
+    def fit_em_bifactor(self, max_iter=100, tol=1e-6, newton=4, nodes=(41, 21), span=(6.0, 4.0), general=0, prior=None,
+                        progress=False):
+        """Refit the items of a bifactor / testlet model by marginal maximum likelihood: Bock-Aitkin EM on the training data
+        over the grid of score_bifactor(), any x_feature >= 2 -- fit_em() itself stops at x_feature = 3.  Every iteration takes
+        each item's expected counts on the Gg x Gh grid of its own testlet and refits its intercept, general loading and specific
+        loading by fit_em's M-step in two dimensions (nodes[0] * nodes[1] <= 1024).  irt_2pl; irt_3pl / irt_4pl with `prior`
+        (fit_em's argument and rules).  A testlet of one item needs a prior with a finite sd on "a".  Return, stopping rule and
+        what is left alone as fit_em(): {"loglik", "iterations", "converged"} and, with `prior`, "logpost"
+        (IrtEngine.fit_em_bifactor).  One rank only; the other classes refuse."""
+        if self.world > 1:
+            raise NotImplementedError("fit_em_bifactor with a group of %d ranks: the expected counts are the local shard's sums; "
+                                      "the cross-rank sum is not built" % self.world)
+        return self.engine.fit_em_bifactor(max_iter=max_iter, tol=tol, newton=newton, nodes=nodes, span=span, general=general,
+                                           prior=prior, progress=progress)
+
     def bifactor_structure(self, general=0):
         """{"general", "specific_dims", "testlet" (per item: the column of specific_dims it loads on, -1: general only),
         "sizes"} as read from the model's free mask on the host (IrtEngine.bifactor_structure); ValueError naming the first
